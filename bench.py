@@ -56,7 +56,13 @@ def parse(argv=None):
     ap.add_argument("--no-configs4-extra", action="store_true",
                     help="default runs also time BASELINE configs[4] (the slab above, 2 steps) after the headline "
                          "workload and report it under the key `configs4_slab` of the same line; this skips it")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (solution vector, cell tags) as "
+                         "DIR/<name>.npy: a fixed, seeded sample of each array, at most 64 MB in all")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def hbm_in_use_gb():
@@ -158,6 +164,40 @@ def cpu_baseline(n, rtol):
 
 # every 8th SpMV launch of the timed region is bracketed by HIP events on the launch stream
 SPMV_EVENT_STRIDE = 8
+
+# --dump-outputs: bytes all ranks together may write (values + sample positions), below the 64 MB the option promises
+DUMP_BUDGET_BYTES = 48 << 20
+
+
+def sample_positions(n, k, seed):
+    """k increasing positions in [0, n) when n > k, one drawn uniformly from each of k consecutive strata (fixed seed:
+    the same positions on every run); all of them otherwise."""
+    import numpy as np
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    edges = np.arange(k + 1, dtype=np.int64) * n // k
+    u = np.random.default_rng(seed).random(k)
+    return edges[:-1] + (u * (edges[1:] - edges[:-1])).astype(np.int64)
+
+
+def dump_outputs(dirname, prob, rank, world):
+    """What the last timed step handed its caller: the solution vector in the full numbering (`prob.out`, inactive
+    DoFs at zero) and the cell tags it was assembled on, as DIR/<name>.npy with <name>_index.npy (float64) naming the
+    sampled positions.  Each rank writes its own slab (<name>_rank<r>) within its share of DUMP_BUDGET_BYTES."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    share = DUMP_BUDGET_BYTES // world // 2                     # half for the solution, half for the tags
+    out = prob.out
+    idx = sample_positions(out.numel(), share // 16, seed=1)    # f64 value + f64 position
+    sol = out[torch.from_numpy(idx).to(out.device)].cpu().numpy()
+    tags = prob.mesh.cell_tag_values()
+    tidx = sample_positions(tags.shape[0], share // 12, seed=2)  # f32 value + f64 position
+    arrays = {"solution": sol.astype(np.float64), "solution_index": idx.astype(np.float64),
+              "cell_tags": tags[tidx].astype(np.float32), "cell_tags_index": tidx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + sfx + ".npy"), a)
 
 
 def event_pair_overhead_us(mesh):
@@ -304,6 +344,8 @@ def main(argv=None):
             res = prob.step(profile_spmv=SPMV_EVENT_STRIDE)
         barrier()
         dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, prob, rank, world)
     ranks_seen, converged = 1, bool(res["converged"])
     if world > 1:
         # max time over ranks, DoFs summed, every rank counted, convergence agreed (MIN)

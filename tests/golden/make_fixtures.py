@@ -23,6 +23,8 @@ Outputs (small, committed):
                                    demo/weak-dirichlet/flower/data.py (pure numpy, so this one
                                    module of the reference IS importable here): golden vectors
                                    for the restatement in tests/flower_data.py (a13)
+  * tests/golden/xdmf/             the four meshes' .xdmf + .h5 files themselves, copied unchanged
+                                   (not written by this script): tests/test_io_xdmf.py reads them
 The known-answer values are plain numbers asserted by the reference's test; they are
 restated here as data.
 """

@@ -100,3 +100,28 @@ def test_watchdog_leaves_with_its_exit_code_and_marker(tmp_path):
     env2.pop("PHX_DIST_TIMEOUT_S", None)
     r2 = subprocess.run([sys.executable, "-c", code2], env=env2, capture_output=True, text=True, timeout=120)
     assert r2.returncode == 87 and mark.exists(), (r2.returncode, r2.stderr[-500:])
+
+
+def test_steps_sets_the_timed_steps_and_must_be_positive():
+    assert bench.parse(["--steps", "7", "--warmup", "2"]).steps == 7
+    import pytest
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_dump_sample_positions_are_fixed_and_within_the_budget():
+    """--dump-outputs samples at the same increasing positions on every run, covers the whole array, keeps short
+    arrays whole, and stays below 64 MB for the largest arrays of the default workload at every rank count."""
+    import numpy as np
+    nv, nc = 257 ** 3, 6 * 256 ** 3
+    k = bench.DUMP_BUDGET_BYTES // 2 // 16
+    a, b = bench.sample_positions(2 * nv, k, seed=1), bench.sample_positions(2 * nv, k, seed=1)
+    assert np.array_equal(a, b) and a.shape == (k,) and a.dtype == np.int64
+    assert a[0] >= 0 and a[-1] < 2 * nv and np.all(np.diff(a) > 0)
+    assert a[0] < 2 * nv // k and a[-1] >= 2 * nv - 2 * nv // k - 1
+    assert not np.array_equal(a, bench.sample_positions(2 * nv, k, seed=2))
+    assert np.array_equal(bench.sample_positions(10, 16, seed=1), np.arange(10))
+    for world in (1, 2, 3, 8):
+        share = bench.DUMP_BUDGET_BYTES // world // 2
+        per_rank = 16 * min(2 * nv, share // 16) + 12 * min(nc, share // 12)
+        assert world * per_rank <= 64 * 2 ** 20

@@ -362,6 +362,39 @@ def test_bench_rccl_on_one_device_fails_loudly():
     assert "need 2 GPUs" in r.stderr
 
 
+def test_bench_dump_outputs_repeat(tmp_path):
+    """`bench.py --dump-outputs DIR`: two runs with the same arguments sample the same positions of the same inputs and
+    write the same tags and (to the rounding of the atomic assembly) the same solution; the samples are what the timed
+    path computed; several ranks write one set each."""
+    import json
+    args = ["--cubes", "24", "--steps", "2", "--warmup", "1", "--rtol", "1e-11", "--no-cpu-baseline"]
+    got = []
+    for run in ("a", "b"):
+        r = _run_bench({}, *args, "--dump-outputs", str(tmp_path / run))
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["config"]["converged"]
+        d = {f[:-4]: np.load(str(tmp_path / run / f)) for f in os.listdir(str(tmp_path / run))}
+        assert sorted(d) == ["cell_tags", "cell_tags_index", "solution", "solution_index"]
+        assert d["solution"].dtype == np.float64 and d["cell_tags"].dtype == np.float32
+        assert sum(a.nbytes for a in d.values()) <= 64 * 2 ** 20
+        got.append(d)
+    a, b = got
+    assert np.array_equal(a["cell_tags"], b["cell_tags"]) and np.array_equal(a["solution_index"], b["solution_index"])
+    scale = np.abs(a["solution"]).max()
+    assert scale > 0 and np.abs(a["solution"] - b["solution"]).max() <= 1e-7 * scale
+    # a system this small is dumped whole: tags and solution of the same problem solved here on one mesh
+    mesh, _, wref, _ = _single_mesh(24, 1)
+    assert np.array_equal(a["solution_index"], np.arange(wref.shape[0]))
+    assert np.array_equal(a["cell_tags_index"], np.arange(mesh.nc))
+    assert np.array_equal(a["cell_tags"], mesh.cell_tag_values().astype(np.float32))
+    assert np.abs(a["solution"] - wref).max() <= 1e-6 * np.abs(wref).max()
+    r = _run_bench({"PHIFEM_DIST_BACKEND": "gloo"}, "--gpus", "2", *args, "--dump-outputs", str(tmp_path / "c"))
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert sorted(os.listdir(str(tmp_path / "c"))) == sorted(f"{k}_rank{i}.npy" for i in (0, 1) for k in
+                                                             ("cell_tags", "cell_tags_index", "solution", "solution_index"))
+
+
 # ---------------------------------------------------------------------------------------------------
 # A CALLER-SUPPLIED Kuhn box, partitioned (ArraySlabProblem): every rank gets the whole vertex array in the caller's
 # (here: shuffled) numbering, recognises the lattice, works on its own slab and hands its owned part back in the caller's

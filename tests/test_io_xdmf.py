@@ -126,15 +126,15 @@ def test_errors(tmp_path):
         XIO.read_xdmf(str(p))
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/tests/tests_data/square_quad.xdmf"),
-                    reason="the reference's test data is only present in the build container")
 def test_reads_the_references_xdmf_hdf5_meshes():
-    """XDMFFile.read_mesh (tests/test_compute_meshtags.py:136-137) on the reference's own mesh files: HDF5 heavy data
-    through the package's own reader (dolfinx's contiguous files and meshio's chunked + deflate one); same cells as
-    the committed fixture (converted from the same files), coordinates equal to the fixture's."""
-    gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "meshes.npz"))
+    """XDMFFile.read_mesh (tests/test_compute_meshtags.py:136-137) on the reference's own mesh files, stored unchanged
+    under tests/golden/xdmf/: HDF5 heavy data through the package's own reader (dolfinx's contiguous files and meshio's
+    chunked + deflate one); same cells as the committed fixture (converted from the same files), coordinates equal to
+    the fixture's."""
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    gold = np.load(os.path.join(golden, "meshes.npz"))
     for name in ("disk", "square_tri", "square_quad", "coarse_square"):
-        d = XIO.read_xdmf(f"/root/reference/tests/tests_data/{name}.xdmf")
+        d = XIO.read_xdmf(os.path.join(golden, "xdmf", f"{name}.xdmf"))
         assert d["cell_type"] == str(gold[name + "_type"])
         gc = gold[name + "_cells"].astype(np.int64)
         if d["cell_type"] == "quadrilateral":
