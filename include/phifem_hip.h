@@ -103,6 +103,38 @@ int phx_levelset_eval_points(phx_mesh *m, int detection_degree, const double *no
                              double *out_device);
 int phx_detection_points_physical(phx_mesh *m, int detection_degree, double *out_device);
 
+/* Lagrange level-sets of degree 1, 2 and 3 -- the `discretize=True` input of tests/test_compute_meshtags.py:153-158,
+ * which interpolates phi into basix.ufl.element("Lagrange", cell, detection_degree) (dolfinx `Function.interpolate`,
+ * :157) before src/phifem/mesh_scripts.py:95-134 evaluates it at the detection points.
+ *
+ * Reference element: basix's default (GLL-warped) Lagrange nodes in basix's local order -- vertices; per edge (basix
+ * edge order; a quadrilateral's edges are its local facets) k - 1 nodes from its first to its second local vertex, at
+ * the Gauss-Lobatto-Legendre parameters (1 -+ 1/sqrt5)/2 for k = 3; then at k = 3 the triangle's centroid, the
+ * tetrahedron's 4 face centroids (face f opposite vertex f), the quadrilateral's 4 interior nodes (tensor product of
+ * the 1-D GLL points, x fastest).  The degree-1 and -2 tables are those of phx_tag_cells and phx_levelset_eval_points.
+ *
+ * Global DoF layout of a nodal level-set (`NodalFunction(values, degree)`):
+ *   degree 1  nv                  vertices
+ *   degree 2  nv + ne             vertices, edges (PHX_ARR_EDGES)                       (simplices)
+ *             nv + nf + nc        vertices, facets, cells                               (quadrilaterals)
+ *   degree 3  nv + 2 ne + nc      vertices, 2 per edge, 1 per cell                      (triangles)
+ *             nv + 2 ne + nf      vertices, 2 per edge, 1 per face (facet id)           (tetrahedra)
+ *             nv + 2 nf + 4 nc    vertices, 2 per facet, 4 per cell (interior order)    (quadrilaterals)
+ * The pair of an edge (facet) e is nodal[nv + 2e], nodal[nv + 2e + 1]: first the node nearer its LOWER global vertex.
+ * ne: phx_mesh_edge_count; nv, nc, nf: phx_mesh_counts.
+ *
+ * [host] phx_lagrange_nodes: the reference-cell nodes, out[n][tdim]; count-then-fill (out == NULL -> *n).
+ * [host] phx_lagrange_tabulate: the basis at npts reference points pts[npts][tdim], out[npts][ndof] (local order).
+ * phx_levelset_eval_points_deg: phx_levelset_eval_points for a nodal level-set of degree `levelset_degree` (1, 2 or
+ * 3, laid out as above, at `loc`); degree 2 IS phx_levelset_eval_points.  out_device: phx_levelset_points_count values.
+ * phx_lagrange_dof_points: physical coordinates of every global DoF of degree 1-3, out_device[ndofs][gdim] (the
+ * interpolation points of `Function.interpolate`); quadrilateral nodes through the bilinear geometry map. */
+int phx_lagrange_nodes(int cell_type, int degree, double *out, int64_t *n);
+int phx_lagrange_tabulate(int cell_type, int degree, int64_t npts, const double *pts, double *out);
+int phx_levelset_eval_points_deg(phx_mesh *m, int detection_degree, int levelset_degree, const double *nodal,
+                                 int loc, double *out_device);
+int phx_lagrange_dof_points(phx_mesh *m, int degree, double *out_device);
+
 /* [host] Facet numbering and connectivities of an unstructured mesh: stands in for dolfinx
  * create_connectivity (mesh_scripts.py:151-153,419-422) and locate_entities_boundary (:430).
  * c2f[nc*nfpc], f2c[(max)nc*nfpc*2] are caller buffers; *nf receives the facet count. */

@@ -2,6 +2,8 @@
 
 Host side (this package) mirrors the reference's interface for the path:
   * `phifem_amd.mesh_scripts.compute_tags_measures`  <- src/phifem/mesh_scripts.py:571-653
+  * `phifem_amd.interpolate`                         <- dolfinx `Function.interpolate` into Lagrange degree 1-3, the
+    level-set of the `discretize=True` leg of tests/test_compute_meshtags.py:153-158
   * `phifem_amd.solver.PhiFEMSolver`                 <- the "define form -> assemble -> solve"
     sequence of demo/weak-dirichlet/flower/main.py:102-186
   * `phifem_amd.solver.StrongDirichletSolver`        <- demo/strong-dirichlet/flower/main.py:83-182
@@ -14,6 +16,7 @@ declared in `include/phifem_hip.h`.  There is no CPU fallback.
 from . import _lib  # noqa: F401  (fails loudly when the HIP library is missing)
 from .mesh import Mesh, MeshTags, create_box, create_rectangle  # noqa: F401
 from . import io  # noqa: F401
-from .mesh_scripts import DeviceExpression, NodalFunction, Quadric, compute_tags_measures  # noqa: F401
+from .mesh_scripts import (DeviceExpression, NodalFunction, Quadric, compute_tags_measures,  # noqa: F401
+                           interpolate)
 from .solver import (InterfaceElasticitySolver, NeumannRobinSolver, PhiFEMSolver,  # noqa: F401
                      StrongDirichletSolver)

@@ -49,6 +49,10 @@ SIGNATURES = {
     "phx_levelset_points_count": ([_vp, _i, _pi64], _i),
     "phx_levelset_eval_points": ([_vp, _i, _vp, _i, _vp], _i),
     "phx_detection_points_physical": ([_vp, _i, _vp], _i),
+    "phx_lagrange_nodes": ([_i, _i, _vp, _pi64], _i),
+    "phx_lagrange_tabulate": ([_i, _i, _i64, _vp, _vp], _i),
+    "phx_levelset_eval_points_deg": ([_vp, _i, _i, _vp, _i, _vp], _i),
+    "phx_lagrange_dof_points": ([_vp, _i, _vp], _i),
     "phx_topology_build_host": ([_i, _i64, _i64, _vp, _vp, _vp, _pi64], _i),
     "phx_mesh_create": ([_i, _i, _i64, _vp, _i64, _vp, _i, C.POINTER(_vp)], _i),
     "phx_mesh_create_box": ([_i, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_vp)], _i),

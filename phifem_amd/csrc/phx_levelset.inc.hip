@@ -2,9 +2,12 @@
 //  * a degree-2 nodal level-set (P2 on simplices: vertex + edge values; Q2 on quadrilaterals: vertex + facet + cell
 //    values) evaluated at the detection points of every cell and of every background-boundary facet -- what the host
 //    shim computed with numpy in round 1 (phifem_amd/mesh_scripts.py `_evaluate_p2`, kept as the test reference);
+//  * a degree-1 or degree-3 nodal level-set (P1 / P3 on simplices, Q1 / Q3 on quadrilaterals: the reference's
+//    `discretize=True` input, tests/test_compute_meshtags.py:153-158) evaluated the same way by a tiled kernel;
 //  * the PHYSICAL detection points themselves, so that a caller's expression ("UFL expression" leg of
-//    /root/reference/tests/test_compute_meshtags.py:159-161) can be evaluated on device tensors.
-// Layout of both outputs: cells first ([nc][npts_cell]), then the boundary facets in ascending facet id
+//    tests/test_compute_meshtags.py:159-161) can be evaluated on device tensors;
+//  * the physical coordinates of the global degree-1/2/3 Lagrange DoFs (the interpolation points of a NodalFunction).
+// Layout of the point values: cells first ([nc][npts_cell]), then the boundary facets in ascending facet id
 // ([nbf][npts_facet]) -- the layout phx_tag_cells / phx_tag_facets read.
 
 // value = sum_d nodal[dof_d] tab[(lf npts + q) ndof + d], d ascending (fixed order)
@@ -190,5 +193,505 @@ extern "C" int phx_detection_points_physical(phx_mesh *m, int detection_degree, 
   PHX_HIP(hipGetLastError());
   PHX_HIP(hipStreamSynchronize(m->stream));
   PHX_HIP(phx_free(dtc)); PHX_HIP(phx_free(dtf));
+  return PHX_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Degree-1..3 Lagrange reference elements (host, double precision).
+//
+// Nodes are those of basix's default `gll_warped` variant (what basix.ufl.element("Lagrange", cell, k) gives dolfinx):
+// the vertices; on every edge k - 1 nodes at the interior Gauss-Lobatto-Legendre points of degree k, running from the
+// edge's first to its second local vertex -- at k = 3 the parameters A = (1 - 1/sqrt5)/2 and B = (1 + 1/sqrt5)/2, not
+// 1/3 and 2/3; at k = 3 one node per triangle (the cell itself, or a face of a tetrahedron).  The warped lattice is
+// invariant under every permutation of the barycentric coordinates, and a single node of a triangle fixed by all of
+// them can only be the point with equal barycentric coordinates: the centroid.  Quadrilaterals: the tensor product of
+// the 1-D points {0, A, B, 1} (2 nodes per edge, 4 interior nodes).
+//
+// Local order (basix's): vertices; the edges in basix's local edge order (triangle (1,2),(0,2),(0,1); tetrahedron
+// (2,3),(1,3),(1,2),(0,3),(0,2),(0,1); quadrilateral = the local facets (0,1),(0,2),(1,3),(2,3)), each edge's nodes
+// from its first to its second vertex; then the triangle's centroid / the tetrahedron's face centroids (face f
+// opposite vertex f) / the quadrilateral's interior nodes (A,A),(B,A),(A,B),(B,B) (x fastest, as the vertices).
+//
+// The P3 basis is written in closed form in the barycentric coordinates l_i (no Vandermonde solve); with
+// AB = 1/5, A + B = 1, B - A = 1/sqrt5 one checks the Kronecker property node by node:
+//   vertex i:              l_i (5 l_i^2 - 5 l_i + 1 + sum_{j<k; j,k != i} l_j l_k)
+//   edge (a,b), node near a:  5 sqrt5 l_a l_b (B l_a - A l_b - (1/sqrt5) sum_{c != a,b} l_c)   (and a <-> b for the
+//                             node near b): l_a l_b vanishes on every edge / face without both a and b, the linear
+//                             factor at the other node of the edge and at the centroids of the faces through it;
+//   triangle / face (a,b,c):  27 l_a l_b l_c.
+// The Q3 basis is the product of the 1-D cubic Lagrange polynomials on {0, A, B, 1}, also in closed form.
+// ------------------------------------------------------------------------------------------
+static inline double gll3_a() { return (1.0 - 1.0 / sqrt(5.0)) / 2.0; }
+static inline double gll3_b() { return (1.0 + 1.0 / sqrt(5.0)) / 2.0; }
+
+static const int kTriEdges[3][2] = {{1, 2}, {0, 2}, {0, 1}};
+static const int kTetEdges[6][2] = {{2, 3}, {1, 3}, {1, 2}, {0, 3}, {0, 2}, {0, 1}};
+static const int kQuadEdges[4][2] = {{0, 1}, {0, 2}, {1, 3}, {2, 3}};
+// 1-D node indices (into {0, A, B, 1}) of the 16 Q3 nodes in local order
+static const int kQ3Idx[16][2] = {{0, 0}, {3, 0}, {0, 3}, {3, 3}, {1, 0}, {2, 0}, {0, 1}, {0, 2},
+                                  {3, 1}, {3, 2}, {1, 3}, {2, 3}, {1, 1}, {2, 1}, {1, 2}, {2, 2}};
+
+static int lagrange_ndof(int cell_type, int degree) {
+  if (degree < 1 || degree > 3) return 0;
+  if (cell_type == PHX_TRIANGLE) return (degree + 1) * (degree + 2) / 2;
+  if (cell_type == PHX_QUADRILATERAL) return (degree + 1) * (degree + 1);
+  if (cell_type == PHX_TETRAHEDRON) return (degree + 1) * (degree + 2) * (degree + 3) / 6;
+  return 0;
+}
+
+static int lagrange_check(int cell_type, int degree) {
+  phx_cell_info ci;
+  PHX_CHECK(phx_get_cell_info(cell_type, &ci));
+  PHX_REQUIRE(degree >= 1 && degree <= 3, PHX_ERR_NOT_IMPLEMENTED,
+              "Lagrange elements of degree 1, 2 and 3 are implemented (got %d)", degree);
+  return PHX_OK;
+}
+
+static void p3_basis_row(int nvpc, const double *lam, double *N) {
+  const double r5 = 1.0 / sqrt(5.0), c5 = 5.0 * sqrt(5.0), A = gll3_a(), B = gll3_b();
+  for (int i = 0; i < nvpc; ++i) {
+    double pairs = 0.0;
+    for (int j = 0; j < nvpc; ++j)
+      for (int k = j + 1; k < nvpc; ++k)
+        if (j != i && k != i) pairs = pairs + lam[j] * lam[k];
+    N[i] = lam[i] * ((((5.0 * lam[i]) * lam[i] - 5.0 * lam[i]) + 1.0) + pairs);
+  }
+  const int ne = nvpc == 3 ? 3 : 6;
+  for (int k = 0; k < ne; ++k) {
+    const int a = nvpc == 3 ? kTriEdges[k][0] : kTetEdges[k][0], b = nvpc == 3 ? kTriEdges[k][1] : kTetEdges[k][1];
+    double rest = 0.0;
+    for (int c = 0; c < nvpc; ++c)
+      if (c != a && c != b) rest = rest + lam[c];
+    const double w = c5 * (lam[a] * lam[b]);
+    N[nvpc + 2 * k] = w * ((B * lam[a] - A * lam[b]) - r5 * rest);
+    N[nvpc + 2 * k + 1] = w * ((B * lam[b] - A * lam[a]) - r5 * rest);
+  }
+  if (nvpc == 3) N[9] = 27.0 * lam[0] * lam[1] * lam[2];
+  else
+    for (int f = 0; f < 4; ++f) {     // face f opposite vertex f
+      double p = 27.0;
+      for (int c = 0; c < 4; ++c)
+        if (c != f) p = p * lam[c];
+      N[16 + f] = p;
+    }
+}
+
+static void l_gll3(double t, double *l) {
+  const double c5 = 5.0 * sqrt(5.0), A = gll3_a(), B = gll3_b();
+  l[0] = -5.0 * ((t - A) * (t - B)) * (t - 1.0);
+  l[1] = c5 * t * (t - B) * (t - 1.0);
+  l[2] = -c5 * t * (t - A) * (t - 1.0);
+  l[3] = 5.0 * t * (t - A) * (t - B);
+}
+
+static void q3_basis_row(double px, double py, double *N) {
+  double lx[4], ly[4];
+  l_gll3(px, lx);
+  l_gll3(py, ly);
+  for (int d = 0; d < 16; ++d) N[d] = lx[kQ3Idx[d][0]] * ly[kQ3Idx[d][1]];
+}
+
+// one row of the degree-k table at reference point X (tdim coordinates); simplices through the barycentric
+// coordinates l_0 = 1 - sum X (as the P1 shape table), so degrees 1 and 2 are the existing tables bit for bit
+static void lagrange_row(int cell_type, int degree, const double *X, double *N) {
+  if (cell_type == PHX_QUADRILATERAL) {
+    const double px = X[0], py = X[1];
+    if (degree == 1) {
+      N[0] = (1.0 - px) * (1.0 - py); N[1] = px * (1.0 - py); N[2] = (1.0 - px) * py; N[3] = px * py;
+    } else if (degree == 2) q2_basis_row(px, py, N);
+    else q3_basis_row(px, py, N);
+    return;
+  }
+  const int tdim = cell_type == PHX_TRIANGLE ? 2 : 3, nvpc = tdim + 1;
+  double lam[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int a = 0; a < tdim; ++a) lam[a + 1] = X[a];
+  lam[0] = tdim == 2 ? (1.0 - X[0]) - X[1] : ((1.0 - X[0]) - X[1]) - X[2];
+  if (degree == 1) for (int i = 0; i < nvpc; ++i) N[i] = lam[i];
+  else if (degree == 2) p2_basis_row(nvpc, lam, N);
+  else p3_basis_row(nvpc, lam, N);
+}
+
+static void lagrange_nodes(int cell_type, int degree, std::vector<double> &p) {
+  p.clear();
+  const double A = gll3_a(), B = gll3_b();
+  const double w[3][2][2] = {{{0, 0}, {0, 0}}, {{0.5, 0.5}, {0, 0}}, {{B, A}, {A, B}}};   // [degree-1][node][a,b]
+  if (cell_type == PHX_QUADRILATERAL) {
+    const double t2[3] = {0.0, 0.5, 1.0}, t3[4] = {0.0, A, B, 1.0};
+    if (degree == 1) { p = {0, 0, 1, 0, 0, 1, 1, 1}; return; }
+    if (degree == 2) {
+      static const int idx[9][2] = {{0, 0}, {2, 0}, {0, 2}, {2, 2}, {1, 0}, {0, 1}, {2, 1}, {1, 2}, {1, 1}};
+      for (int d = 0; d < 9; ++d) { p.push_back(t2[idx[d][0]]); p.push_back(t2[idx[d][1]]); }
+      return;
+    }
+    for (int d = 0; d < 16; ++d) { p.push_back(t3[kQ3Idx[d][0]]); p.push_back(t3[kQ3Idx[d][1]]); }
+    return;
+  }
+  const int tdim = cell_type == PHX_TRIANGLE ? 2 : 3, nvpc = tdim + 1;
+  double v[4][3] = {{0, 0, 0}, {1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+  for (int i = 0; i < nvpc; ++i) for (int a = 0; a < tdim; ++a) p.push_back(v[i][a]);
+  if (degree == 1) return;
+  const int ne = nvpc == 3 ? 3 : 6;
+  for (int k = 0; k < ne; ++k) {
+    const int a = nvpc == 3 ? kTriEdges[k][0] : kTetEdges[k][0], b = nvpc == 3 ? kTriEdges[k][1] : kTetEdges[k][1];
+    for (int j = 0; j < degree - 1; ++j)
+      for (int c = 0; c < tdim; ++c) p.push_back(w[degree - 1][j][0] * v[a][c] + w[degree - 1][j][1] * v[b][c]);
+  }
+  if (degree == 2) return;
+  if (nvpc == 3) { p.push_back(1.0 / 3.0); p.push_back(1.0 / 3.0); return; }
+  for (int f = 0; f < 4; ++f) {
+    int fv[3], n = 0;
+    for (int c = 0; c < 4; ++c) if (c != f) fv[n++] = c;
+    for (int c = 0; c < 3; ++c) p.push_back(((v[fv[0]][c] + v[fv[1]][c]) + v[fv[2]][c]) / 3.0);
+  }
+}
+
+extern "C" int phx_lagrange_nodes(int cell_type, int degree, double *out, int64_t *n) {
+  PHX_CHECK(lagrange_check(cell_type, degree));
+  std::vector<double> p;
+  lagrange_nodes(cell_type, degree, p);
+  *n = lagrange_ndof(cell_type, degree);
+  if (out) memcpy(out, p.data(), p.size() * sizeof(double));
+  return PHX_OK;
+}
+
+extern "C" int phx_lagrange_tabulate(int cell_type, int degree, int64_t npts, const double *pts, double *out) {
+  PHX_CHECK(lagrange_check(cell_type, degree));
+  PHX_REQUIRE(npts >= 0 && (npts == 0 || (pts && out)), PHX_ERR_VALUE, "phx_lagrange_tabulate: bad point buffer");
+  const int tdim = cell_type == PHX_TETRAHEDRON ? 3 : 2, ndof = lagrange_ndof(cell_type, degree);
+  for (int64_t q = 0; q < npts; ++q) lagrange_row(cell_type, degree, pts + q * tdim, out + q * ndof);
+  return PHX_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// Degree-1 / degree-3 nodal level-set at the detection points.
+//
+// Global layout of a degree-3 NodalFunction (include/phifem_hip.h): triangles nv + 2 ne + nc, tetrahedra
+// nv + 2 ne + nf, quadrilaterals nv + 2 nf + 4 nc.  Slot nv + 2 e + s of edge (or quadrilateral facet) e is the
+// node nearer the LOWER global vertex for s = 0.  A cell's local edge (a,b) runs from a to b; its local node j sits
+// in slot s = j when cells[a] < cells[b] and s = 1 - j otherwise -- decided from the global vertex ids, never from
+// which cell numbered the edge.
+//
+// One block per tile of LS_TILE entities (cells, or boundary facets with their (cell, local facet) pairs):
+//  1. one thread per entity reads its vertex ids once, derives the edge orientations from them and gathers its ndof
+//     nodal values into LDS (row stride NDOF | 1: odd, so the rows start in different banks);
+//  2. the tile's (entity, point) outputs, consecutive threads on consecutive points, sum_d v_d T[lf][d][q] with d
+//     ascending, written as contiguous runs of the output.  Each thread keeps one point q for the whole tile, so on
+//     cells its table column lives in registers and only the nodal values are read from LDS.  128^3 Kuhn box, detection
+//     degree 3 (1.26e7 cells x 20 points, 2.0 GB written): 1.23 ms; reading the table from LDS for every output as
+//     well took 1.63 ms; the degree-2 k_eval_nodal_points above (one thread per point, ndof gathers each) 4.1 ms.
+// ------------------------------------------------------------------------------------------
+#define LS_TILE 256
+
+struct LsLayout {
+  int kind;       // PHX_TRIANGLE / PHX_QUADRILATERAL / PHX_TETRAHEDRON
+  int degree;     // 1 or 3
+  int nvpc, nx;   // vertices and edges (quadrilateral: facets) per cell
+  uint32_t ev;    // local edge k -> local vertices (bits 4k..4k+1, 4k+2..4k+3): a register, not an indexed array
+  int64_t nv, n2; // vertices; edges (simplices) or facets (quadrilaterals)
+};
+
+// v[i] without a dynamically indexed private array (which would live in scratch memory)
+__device__ __forceinline__ int32_t pick4(const int32_t *v, int i) {
+  return i == 0 ? v[0] : (i == 1 ? v[1] : (i == 2 ? v[2] : v[3]));
+}
+
+template <int NDOF>
+__global__ void __launch_bounds__(LS_TILE)
+k_eval_lagrange_tiled(int64_t nent, int npts, int ntab, const double *__restrict__ tab, LsLayout L,
+                      const int32_t *__restrict__ cells, const int32_t *__restrict__ c2x,
+                      const int32_t *__restrict__ c2f, const int32_t *__restrict__ ent,
+                      const double *__restrict__ nodal, double *__restrict__ out) {
+  constexpr int LD = NDOF | 1;
+  extern __shared__ double lds[];
+  double *vals = lds;                                   // [LS_TILE][LD]
+  double *T = lds + LS_TILE * LD;                       // [ntab][NDOF][npts]
+  int *lfs = (int *)(T + (size_t)ntab * NDOF * npts);   // [LS_TILE]
+  const int64_t base = (int64_t)blockIdx.x * LS_TILE;
+  const int ntile = (int)min((int64_t)LS_TILE, nent - base);
+  for (int i = threadIdx.x; i < ntab * NDOF * npts; i += blockDim.x) T[i] = tab[i];
+  const int t = threadIdx.x;
+  if (t < ntile) {
+    const int64_t e = base + t;
+    const int64_t c = ent ? ent[2 * e] : e;
+    lfs[t] = ent ? ent[2 * e + 1] : 0;
+    int32_t v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = k < L.nvpc ? cells[c * L.nvpc + k] : 0;
+    double *row = vals + t * LD;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (k < L.nvpc) row[k] = nodal[v[k]];
+    if (L.degree == 3) {
+      int d = L.nvpc;
+      for (int k = 0; k < L.nx; ++k) {
+        const int64_t slot = L.nv + 2 * (int64_t)c2x[c * L.nx + k];
+        const int flip = pick4(v, (L.ev >> (4 * k)) & 3) > pick4(v, (L.ev >> (4 * k + 2)) & 3) ? 1 : 0;
+        row[d++] = nodal[slot + flip];
+        row[d++] = nodal[slot + (1 - flip)];
+      }
+      if (L.kind == PHX_TRIANGLE) row[d] = nodal[L.nv + 2 * L.n2 + c];
+      else if (L.kind == PHX_TETRAHEDRON)
+        for (int f = 0; f < 4; ++f) row[d + f] = nodal[L.nv + 2 * L.n2 + c2f[c * 4 + f]];
+      else
+        for (int r = 0; r < 4; ++r) row[d + r] = nodal[L.nv + 2 * L.n2 + 4 * c + r];
+    }
+  }
+  __syncthreads();
+  // thread t keeps point q = t % npts and walks the tile's entities t / npts, t / npts + per, ...: one sweep of the
+  // block writes per * npts consecutive outputs; on cells (one table) the column T[.][q] stays in registers
+  const int per = (int)blockDim.x / npts, q = t % npts;
+  if (t >= per * npts) return;
+  double *o = out + base * npts;
+  if (ntab == 1) {
+    double col[NDOF];
+#pragma unroll
+    for (int d = 0; d < NDOF; ++d) col[d] = T[d * npts + q];
+    for (int el = t / npts; el < ntile; el += per) {
+      const double *r = vals + el * LD;
+      double acc = 0.0;
+#pragma unroll
+      for (int d = 0; d < NDOF; ++d) acc = acc + r[d] * col[d];
+      o[el * npts + q] = acc;
+    }
+  } else {
+    for (int el = t / npts; el < ntile; el += per) {
+      const double *Tq = T + (size_t)lfs[el] * NDOF * npts + q;
+      const double *r = vals + el * LD;
+      double acc = 0.0;
+#pragma unroll
+      for (int d = 0; d < NDOF; ++d) acc = acc + r[d] * Tq[d * npts];
+      o[el * npts + q] = acc;
+    }
+  }
+}
+
+template <int NDOF>
+static int launch_eval_tiled(phx_mesh *m, int64_t nent, int npts, int ntab, const double *dtab, const LsLayout &L,
+                             const int32_t *c2x, const int32_t *ent, const double *dnodal, double *out) {
+  if (nent <= 0) return PHX_OK;
+  const size_t lds = sizeof(double) * ((size_t)LS_TILE * (NDOF | 1) + (size_t)ntab * NDOF * npts) + sizeof(int) * LS_TILE;
+  PHX_REQUIRE(lds <= 65536, PHX_ERR_NOT_IMPLEMENTED, "detection degree too large for the level-set table (%zu B)", lds);
+  k_eval_lagrange_tiled<NDOF><<<dim3((unsigned)phx_div_up(nent, LS_TILE)), dim3(LS_TILE), lds, m->stream>>>(
+      nent, npts, ntab, dtab, L, m->cells, c2x, m->c2f, ent, dnodal, out);
+  PHX_HIP(hipGetLastError());
+  return PHX_OK;
+}
+
+static int launch_eval_ndof(phx_mesh *m, int ndof, int64_t nent, int npts, int ntab, const double *dtab,
+                            const LsLayout &L, const int32_t *c2x, const int32_t *ent, const double *dnodal,
+                            double *out) {
+  switch (ndof) {
+    case 3: return launch_eval_tiled<3>(m, nent, npts, ntab, dtab, L, c2x, ent, dnodal, out);
+    case 4: return launch_eval_tiled<4>(m, nent, npts, ntab, dtab, L, c2x, ent, dnodal, out);
+    case 10: return launch_eval_tiled<10>(m, nent, npts, ntab, dtab, L, c2x, ent, dnodal, out);
+    case 16: return launch_eval_tiled<16>(m, nent, npts, ntab, dtab, L, c2x, ent, dnodal, out);
+    case 20: return launch_eval_tiled<20>(m, nent, npts, ntab, dtab, L, c2x, ent, dnodal, out);
+  }
+  phx_set_error("no level-set kernel for %d nodal values per cell", ndof);
+  return PHX_ERR_NOT_IMPLEMENTED;
+}
+
+static int lagrange_global_count(phx_mesh *m, int degree, int64_t *n) {
+  const bool quad = m->cell_type == PHX_QUADRILATERAL;
+  if (degree >= 2 && !quad) PHX_CHECK(phx_mesh_build_edges(m));
+  if (degree == 1) *n = m->nv;
+  else if (quad) *n = degree == 2 ? m->nv + m->nf + m->nc : m->nv + 2 * m->nf + 4 * m->nc;
+  else if (degree == 2) *n = m->nv + m->ne;
+  else *n = m->nv + 2 * m->ne + (m->cell_type == PHX_TRIANGLE ? m->nc : m->nf);
+  return PHX_OK;
+}
+
+extern "C" int phx_levelset_eval_points_deg(phx_mesh *m, int detection_degree, int levelset_degree,
+                                            const double *nodal, int loc, double *out_device) {
+  PHX_HIP(hipSetDevice(m->device));
+  PHX_CHECK(lagrange_check(m->cell_type, levelset_degree));
+  if (levelset_degree == 2) return phx_levelset_eval_points(m, detection_degree, nodal, loc, out_device);
+  const bool quad = m->cell_type == PHX_QUADRILATERAL;
+  const int nvpc = m->ci.nvpc, tdim = m->ci.tdim, nfpc = m->ci.nfpc, nvpf = m->ci.nvpf;
+  const int ndof = lagrange_ndof(m->cell_type, levelset_degree);
+  int nptc, nptf;
+  PHX_CHECK(levelset_counts(m, detection_degree, &nptc, &nptf));
+  PHX_REQUIRE(nptc <= PHX_MAX_PTS, PHX_ERR_NOT_IMPLEMENTED, "detection degree %d too large", detection_degree);
+  std::vector<double> pc((size_t)nptc * tdim), pf((size_t)nptf * (tdim - 1));
+  int64_t n = nptc;
+  PHX_CHECK(phx_detection_points(m->cell_type, detection_degree, 0, pc.data(), &n));
+  n = nptf;
+  PHX_CHECK(phx_detection_points(m->cell_type, detection_degree, 1, pf.data(), &n));
+  int64_t nnodal = 0;
+  PHX_CHECK(lagrange_global_count(m, levelset_degree, &nnodal));
+  LsLayout L;
+  memset(&L, 0, sizeof(L));
+  L.kind = m->cell_type; L.degree = levelset_degree; L.nvpc = nvpc; L.nv = m->nv;
+  L.nx = quad ? 4 : (nvpc == 3 ? 3 : 6);
+  L.n2 = quad ? m->nf : m->ne;
+  for (int k = 0; k < L.nx; ++k)
+    for (int j = 0; j < 2; ++j)
+      L.ev |= (uint32_t)(quad ? kQuadEdges[k][j] : (nvpc == 3 ? kTriEdges[k][j] : kTetEdges[k][j])) << (4 * k + 2 * j);
+  const int32_t *c2x = levelset_degree == 1 ? nullptr : (quad ? m->c2f : m->c2e);
+  // transposed tables: cells [ndof][nptc]; facets [nfpc][ndof][nptf]
+  std::vector<double> row(ndof), tc((size_t)ndof * nptc), tf((size_t)nfpc * ndof * nptf);
+  for (int q = 0; q < nptc; ++q) {
+    lagrange_row(m->cell_type, levelset_degree, &pc[(size_t)q * tdim], row.data());
+    for (int d = 0; d < ndof; ++d) tc[(size_t)d * nptc + q] = row[d];
+  }
+  for (int lf = 0; lf < nfpc; ++lf)
+    for (int q = 0; q < nptf; ++q) {
+      if (quad) {
+        static const double vx[4] = {0.0, 1.0, 0.0, 1.0}, vy[4] = {0.0, 0.0, 1.0, 1.0};
+        const int a = m->ci.fv[lf][0], b = m->ci.fv[lf][1];
+        const double s = pf[q];
+        const double X[2] = {vx[a] == vx[b] ? vx[a] : s, vy[a] == vy[b] ? vy[a] : s};
+        lagrange_row(m->cell_type, levelset_degree, X, row.data());
+      } else {
+        // barycentric coordinates of the facet point, the cell's other ones exactly 0
+        double mu[3] = {0.0, 0.0, 0.0};
+        if (nvpf == 2) { mu[0] = 1.0 - pf[q]; mu[1] = pf[q]; }
+        else { mu[1] = pf[2 * q]; mu[2] = pf[2 * q + 1]; mu[0] = (1.0 - mu[1]) - mu[2]; }
+        double lam[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int j = 0; j < nvpf; ++j) lam[m->ci.fv[lf][j]] = mu[j];
+        if (levelset_degree == 1) for (int i = 0; i < nvpc; ++i) row[i] = lam[i];
+        else p3_basis_row(nvpc, lam, row.data());
+      }
+      for (int d = 0; d < ndof; ++d) tf[((size_t)lf * ndof + d) * nptf + q] = row[d];
+    }
+  double *dtc = nullptr, *dtf = nullptr, *dn = nullptr;
+  PHX_HIP(phx_malloc(&dtc, sizeof(double) * tc.size()));
+  PHX_HIP(phx_malloc(&dtf, sizeof(double) * tf.size()));
+  PHX_HIP(hipMemcpyAsync(dtc, tc.data(), sizeof(double) * tc.size(), hipMemcpyHostToDevice, m->stream));
+  PHX_HIP(hipMemcpyAsync(dtf, tf.data(), sizeof(double) * tf.size(), hipMemcpyHostToDevice, m->stream));
+  const double *dnodal = nodal;
+  if (loc != PHX_DEVICE) {
+    PHX_HIP(phx_malloc(&dn, sizeof(double) * (size_t)nnodal));
+    PHX_HIP(hipMemcpyAsync(dn, nodal, sizeof(double) * (size_t)nnodal, hipMemcpyHostToDevice, m->stream));
+    dnodal = dn;
+  }
+  int rc = launch_eval_ndof(m, ndof, m->nc, nptc, 1, dtc, L, c2x, nullptr, dnodal, out_device);
+  if (rc == PHX_OK)
+    rc = launch_eval_ndof(m, ndof, m->nbf, nptf, nfpc, dtf, L, c2x, m->bfacets, dnodal,
+                          out_device + m->nc * (int64_t)nptc);
+  PHX_HIP(hipStreamSynchronize(m->stream));   // the host tables and the staged copy go out of scope
+  PHX_HIP(phx_free(dtc)); PHX_HIP(phx_free(dtf));
+  if (dn) PHX_HIP(phx_free(dn));
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------------
+// Physical coordinates of the global Lagrange DoFs (layout above; degree 2 as p2_dof_points / q2_dof_points).
+// One written formula per node kind, restated in numpy by Mesh.lagrange_dof_points (the two agree bit for bit):
+//   vertex                      x_v
+//   edge / facet node (p < q the global vertices, weights (w0, w1) = (B, A) for slot 0, (A, B) for slot 1,
+//                     (0.5, 0.5) at degree 2)                   w0 x_p + w1 x_q   (on a quadrilateral: the bilinear
+//                                                               map restricted to the facet)
+//   triangle centroid           ((x_0 + x_1) + x_2) / 3, local vertex order
+//   tetrahedron face centroid   ((x_p + x_q) + x_r) / 3, p < q < r
+//   quadrilateral interior node (xi, eta) with 1-D weights (1 - xi, xi) written as constants ((B, A) at A, (A, B) at
+//                               B, (0.5, 0.5) at 1/2): the bilinear map
+//                               ((u0 v0 x_0 + u1 v0 x_1) + u0 v1 x_2) + u1 v1 x_3   (each weight product first)
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_dof_edge_nodes(int64_t n, const int32_t *__restrict__ pairs, int gdim, const double *__restrict__ x, int nper,
+                 double w0a, double w1a, double w0b, double w1b, double *__restrict__ out) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t p = pairs[2 * i], q = pairs[2 * i + 1];
+  for (int s = 0; s < nper; ++s) {
+    const double w0 = s == 0 ? w0a : w0b, w1 = s == 0 ? w1a : w1b;
+    for (int a = 0; a < gdim; ++a) out[(i * nper + s) * gdim + a] = w0 * x[p * gdim + a] + w1 * x[q * gdim + a];
+  }
+}
+
+// facet -> its vertices, ascending (read from its first cell)
+__global__ void __launch_bounds__(256)
+k_facet_vertices(int64_t nf, const int32_t *__restrict__ f2c, const int32_t *__restrict__ c2f,
+                 const int32_t *__restrict__ cells, FacetVerts fvs, int nvpc, int32_t *__restrict__ fverts) {
+  const int64_t f = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (f >= nf) return;
+  const int64_t c = f2c[2 * f];
+  int lf = 0;
+  for (int k = 0; k < fvs.nfpc; ++k)
+    if (c2f[c * fvs.nfpc + k] == f) lf = k;
+  int32_t v[3];
+  for (int j = 0; j < fvs.nvpf; ++j) v[j] = cells[c * nvpc + fvs.fv[lf][j]];
+  for (int j = 1; j < fvs.nvpf; ++j)
+    for (int k = j; k > 0 && v[k - 1] > v[k]; --k) { const int32_t t = v[k]; v[k] = v[k - 1]; v[k - 1] = t; }
+  for (int j = 0; j < fvs.nvpf; ++j) fverts[f * fvs.nvpf + j] = v[j];
+}
+
+__global__ void __launch_bounds__(256)
+k_dof_face_centroids(int64_t nf, const int32_t *__restrict__ fverts, const double *__restrict__ x,
+                     double *__restrict__ out) {
+  const int64_t f = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (f >= nf) return;
+  const int64_t p = fverts[3 * f], q = fverts[3 * f + 1], r = fverts[3 * f + 2];
+  for (int a = 0; a < 3; ++a) out[f * 3 + a] = ((x[p * 3 + a] + x[q * 3 + a]) + x[r * 3 + a]) / 3.0;
+}
+
+// triangle centroids (nper = 1, kind 0) or quadrilateral interior nodes (nper = 1 at degree 2, 4 at degree 3)
+__global__ void __launch_bounds__(256)
+k_dof_cell_nodes(int64_t nc, const int32_t *__restrict__ cells, int nvpc, int gdim, const double *__restrict__ x,
+                 int nper, double ua, double ub, double *__restrict__ out) {
+  const int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  const int64_t v0 = cells[c * nvpc], v1 = cells[c * nvpc + 1], v2 = cells[c * nvpc + 2];
+  if (nvpc == 3) {
+    for (int a = 0; a < gdim; ++a)
+      out[c * gdim + a] = ((x[v0 * gdim + a] + x[v1 * gdim + a]) + x[v2 * gdim + a]) / 3.0;
+    return;
+  }
+  const int64_t v3 = cells[c * nvpc + 3];
+  for (int r = 0; r < nper; ++r) {
+    // 1-D weights (1 - xi, xi): node index 0 -> (ub, ua), 1 -> (ua, ub)
+    const double u0 = (r & 1) ? ua : ub, u1 = (r & 1) ? ub : ua;
+    const double v0w = (r & 2) ? ua : ub, v1w = (r & 2) ? ub : ua;
+    const double n0 = u0 * v0w, n1 = u1 * v0w, n2 = u0 * v1w, n3 = u1 * v1w;
+    for (int a = 0; a < gdim; ++a)
+      out[(c * nper + r) * gdim + a] =
+          ((n0 * x[v0 * gdim + a] + n1 * x[v1 * gdim + a]) + n2 * x[v2 * gdim + a]) + n3 * x[v3 * gdim + a];
+  }
+}
+
+extern "C" int phx_lagrange_dof_points(phx_mesh *m, int degree, double *out_device) {
+  PHX_HIP(hipSetDevice(m->device));
+  PHX_CHECK(lagrange_check(m->cell_type, degree));
+  int64_t total = 0;
+  PHX_CHECK(lagrange_global_count(m, degree, &total));   // builds the edges the layout needs
+  const int gdim = m->gdim;
+  const bool quad = m->cell_type == PHX_QUADRILATERAL, tet = m->cell_type == PHX_TETRAHEDRON;
+  const dim3 block(256);
+  PHX_HIP(hipMemcpyAsync(out_device, m->x, sizeof(double) * (size_t)m->nv * gdim, hipMemcpyDeviceToDevice, m->stream));
+  if (degree > 1) {
+    const double A = gll3_a(), B = gll3_b();
+    const double w0a = degree == 2 ? 0.5 : B, w1a = degree == 2 ? 0.5 : A;
+    const int nper = degree - 1;
+    double *o = out_device + m->nv * gdim;
+    int32_t *fverts = nullptr;
+    if (quad || tet) {
+      FacetVerts fvs;
+      fvs.nfpc = m->ci.nfpc; fvs.nvpf = m->ci.nvpf;
+      for (int f = 0; f < 4; ++f) for (int k = 0; k < 3; ++k) fvs.fv[f][k] = m->ci.fv[f][k];
+      PHX_HIP(phx_malloc(&fverts, sizeof(int32_t) * (size_t)(m->nf > 0 ? m->nf : 1) * fvs.nvpf));
+      if (m->nf > 0)
+        k_facet_vertices<<<dim3((unsigned)phx_div_up(m->nf, 256)), block, 0, m->stream>>>(
+            m->nf, m->f2c, m->c2f, m->cells, fvs, m->ci.nvpc, fverts);
+    }
+    const int64_t nedge = quad ? m->nf : m->ne;
+    const int32_t *pairs = quad ? fverts : m->edges;
+    if (nedge > 0)
+      k_dof_edge_nodes<<<dim3((unsigned)phx_div_up(nedge, 256)), block, 0, m->stream>>>(
+          nedge, pairs, gdim, m->x, nper, w0a, w1a, w1a, w0a, o);
+    o += nedge * nper * gdim;
+    if (quad && m->nc > 0)
+      k_dof_cell_nodes<<<dim3((unsigned)phx_div_up(m->nc, 256)), block, 0, m->stream>>>(
+          m->nc, m->cells, 4, gdim, m->x, degree == 2 ? 1 : 4, degree == 2 ? 0.5 : A, degree == 2 ? 0.5 : B, o);
+    else if (degree == 3 && tet && m->nf > 0)
+      k_dof_face_centroids<<<dim3((unsigned)phx_div_up(m->nf, 256)), block, 0, m->stream>>>(m->nf, fverts, m->x, o);
+    else if (degree == 3 && !tet && m->nc > 0)
+      k_dof_cell_nodes<<<dim3((unsigned)phx_div_up(m->nc, 256)), block, 0, m->stream>>>(
+          m->nc, m->cells, 3, gdim, m->x, 1, 0.0, 0.0, o);
+    PHX_HIP(hipGetLastError());
+    PHX_HIP(hipStreamSynchronize(m->stream));
+    if (fverts) PHX_HIP(phx_free(fverts));
+  }
+  PHX_HIP(hipStreamSynchronize(m->stream));
   return PHX_OK;
 }

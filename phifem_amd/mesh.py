@@ -167,6 +167,74 @@ class Mesh:
             fverts[c2f[:, lf]] = cells[:, lfv[lf]]
         return np.concatenate([x, 0.5 * (x[fverts[:, 0]] + x[fverts[:, 1]]), x[cells].mean(axis=1)], axis=0)
 
+    def lagrange_ndofs(self, degree):
+        """Number of global DoFs of a degree-1/2/3 Lagrange function in the library's layout (`NodalFunction`)."""
+        if degree not in (1, 2, 3):
+            raise NotImplementedError("Lagrange functions of degree 1, 2 and 3 are implemented")
+        if degree == 1:
+            return self.nv
+        if self.cell_type == "quadrilateral":
+            return self.nv + self.nf + self.nc if degree == 2 else self.nv + 2 * self.nf + 4 * self.nc
+        if degree == 2:
+            return self.nv + self.ne
+        return self.nv + 2 * self.ne + (self.nc if self.cell_type == "triangle" else self.nf)
+
+    def _facet_vertices(self):
+        """(nf, nvpf) global vertices of every facet, ascending (read from the facet's first cell)."""
+        from .mesh_scripts import _FACET_VERTS
+        cells, c2f, f2c = self.cells, self.c2f, self.f2c
+        c0 = f2c[:, 0]
+        lf = np.argmax(c2f[c0] == np.arange(self.nf)[:, None], axis=1)
+        return np.sort(cells[c0[:, None], _FACET_VERTS[self.cell_type][lf]], axis=1)
+
+    def lagrange_dof_points(self, degree, device=False):
+        """Coordinates (ndofs, gdim) of the global DoFs of a degree-1/2/3 Lagrange function, in the layout of
+        `NodalFunction` -- the points `interpolate` evaluates at.  device=False: numpy, computed here (the readable
+        statement of the formulas); device=True: a float64 tensor on the mesh's GPU from `phx_lagrange_dof_points`,
+        bit for bit the same numbers.  Formulas (include/phifem_hip.h; A, B = (1 -+ 1/sqrt5)/2):
+          edge / facet pair of (p < q):  B x_p + A x_q, then A x_p + B x_q  (degree 2: 0.5 x_p + 0.5 x_q)
+          triangle centroid:             ((x_0 + x_1) + x_2) / 3, face centroid of (p < q < r): ((x_p + x_q) + x_r) / 3
+          quadrilateral interior nodes:  bilinear map at (A,A), (B,A), (A,B), (B,B) (degree 2: at (1/2, 1/2))."""
+        n = self.lagrange_ndofs(degree)
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            out = torch.empty((n, self.gdim), dtype=torch.float64, device=dev)
+            L.sync_torch_stream(dev)
+            L.check(L.lib.phx_lagrange_dof_points(self._h, degree, C.c_void_p(out.data_ptr())))
+            return out
+        x = self.x
+        if degree == 1:
+            return x
+        A = (1.0 - 1.0 / np.sqrt(5.0)) / 2.0
+        B = (1.0 + 1.0 / np.sqrt(5.0)) / 2.0
+        quad = self.cell_type == "quadrilateral"
+        pairs = self._facet_vertices() if quad else self.edges
+        xp, xq = x[pairs[:, 0]], x[pairs[:, 1]]
+        if degree == 2:
+            edge_nodes = 0.5 * xp + 0.5 * xq
+        else:
+            edge_nodes = np.stack([B * xp + A * xq, A * xp + B * xq], axis=1).reshape(-1, self.gdim)
+        parts = [x, edge_nodes]
+        cells = self.cells
+        if quad:
+            xc = x[cells]                                   # (nc, 4, gdim)
+            ts = [(0.5, 0.5)] if degree == 2 else [(B, A), (A, B)]      # 1-D weights (1 - xi, xi)
+            nodes = []
+            order = [(0, 0)] if degree == 2 else [(0, 0), (1, 0), (0, 1), (1, 1)]
+            for i, j in order:
+                u0, u1 = ts[i]
+                w0, w1 = ts[j]
+                n0, n1, n2, n3 = u0 * w0, u1 * w0, u0 * w1, u1 * w1
+                nodes.append(((n0 * xc[:, 0] + n1 * xc[:, 1]) + n2 * xc[:, 2]) + n3 * xc[:, 3])
+            parts.append(np.stack(nodes, axis=1).reshape(-1, self.gdim))
+        elif degree == 3 and self.cell_type == "triangle":
+            parts.append(((x[cells[:, 0]] + x[cells[:, 1]]) + x[cells[:, 2]]) / 3.0)
+        elif degree == 3:
+            fv = self._facet_vertices()
+            parts.append(((x[fv[:, 0]] + x[fv[:, 1]]) + x[fv[:, 2]]) / 3.0)
+        return np.ascontiguousarray(np.concatenate(parts, axis=0))
+
     def cell_tag_values(self):
         return self._get(L.ARR_CELL_TAGS, (self.nc,), np.int32)
 

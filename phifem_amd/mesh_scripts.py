@@ -20,19 +20,50 @@ _ZERO_DEN_MSG = ("The detection function is zero everywhere on a cell. We mark i
 
 
 class NodalFunction:
-    """A P1 function on a mesh given by its vertex values (stands in for a
-    `dolfinx.fem.Function` in a first-order Lagrange space).  `values` may be a numpy array or
-    a torch tensor living on the mesh's GPU."""
+    """A Lagrange function of degree 1, 2 or 3 on a mesh given by its nodal values (stands in for a
+    `dolfinx.fem.Function` in a Lagrange space).  `values` may be a numpy array or a torch tensor living on the
+    mesh's GPU; `interpolate(mesh, f, degree)` builds one from an expression."""
 
     def __init__(self, values, degree=1):
-        """degree 1: one value per vertex.  degree 2: vertex values then edge-midpoint values
-        (`mesh.p2_dof_points()`; quadrilaterals: `mesh.q2_dof_points()`), numpy or a torch tensor on the
-        mesh's GPU; evaluated at the detection points by the library on the device
-        (`phx_levelset_eval_points`) and classified there (PHX_PHI_POINTS)."""
-        if degree not in (1, 2):
-            raise NotImplementedError("level-set functions of degree 1 and 2 are implemented")
+        """Nodal layout (`mesh.lagrange_ndofs(degree)` values, coordinates `mesh.lagrange_dof_points(degree)`):
+          degree 1: one value per vertex;
+          degree 2: vertex values, then one per edge (`mesh.p2_dof_points()`); quadrilaterals: vertices, one per
+                    facet, one per cell (`mesh.q2_dof_points()`);
+          degree 3: vertex values, then two per edge -- the node nearer the edge's lower global vertex first --,
+                    then one per cell (triangles) or one per face in facet order (tetrahedra); quadrilaterals:
+                    vertices, two per facet (same rule), four per cell (interior nodes (A,A), (B,A), (A,B), (B,B)
+                    of the reference square, A, B = (1 -+ 1/sqrt5)/2).
+        Degrees 2 and 3 are evaluated at the detection points by the library on the device
+        (`phx_levelset_eval_points_deg`) and classified there (PHX_PHI_POINTS); the level-set degree is independent
+        of the detection degree."""
+        if degree not in (1, 2, 3):
+            raise NotImplementedError("level-set functions of degree 1, 2 and 3 are implemented")
         self.values = values
         self.degree = degree
+
+
+def interpolate(mesh, f, degree):
+    """The NodalFunction of degree 1, 2 or 3 that interpolates `f` -- dolfinx `Function.interpolate` into
+    `Lagrange(cell, degree)`, as tests/test_compute_meshtags.py:153-158 does for its `discretize=True` leg.
+    `f`: a numpy callable x -> phi (x of shape (gdim, n)), evaluated at `mesh.lagrange_dof_points(degree)` on the host,
+    or a `DeviceExpression`, evaluated on the device at `mesh.lagrange_dof_points(degree, device=True)`."""
+    if degree not in (1, 2, 3):
+        raise NotImplementedError("interpolation into Lagrange spaces of degree 1, 2 and 3 is implemented")
+    if isinstance(f, DeviceExpression):
+        import torch
+        xq = mesh.lagrange_dof_points(degree, device=True)
+        vals = f.f(xq.t())
+        if not hasattr(vals, "data_ptr") or not vals.is_cuda or vals.numel() != xq.shape[0]:
+            raise ValueError("a DeviceExpression must return one value per point as a tensor on the mesh's GPU")
+        return NodalFunction(vals.reshape(-1).to(torch.float64).contiguous(), degree)
+    if callable(f):
+        x = mesh.lagrange_dof_points(degree)
+        with np.errstate(all="ignore"):
+            vals = np.asarray(f(x.T), dtype=np.float64).reshape(-1)
+        if vals.shape[0] != x.shape[0]:
+            raise ValueError("the callable must return one value per point")
+        return NodalFunction(np.ascontiguousarray(vals), degree)
+    raise TypeError("interpolate takes a numpy callable x -> phi or a DeviceExpression")
 
 
 class DeviceExpression:
@@ -88,8 +119,8 @@ class BoundaryMeasure:
 
 def _levelset_args(mesh, levelset, degree):
     """-> (phi_kind, pointer, loc, keepalive)."""
-    if isinstance(levelset, NodalFunction) and levelset.degree == 2:
-        return _device_points(mesh, degree, nodal=levelset.values)
+    if isinstance(levelset, NodalFunction) and levelset.degree in (2, 3):
+        return _device_points(mesh, degree, nodal=levelset.values, nodal_degree=levelset.degree)
     if isinstance(levelset, DeviceExpression):
         return _device_points(mesh, degree, expr=levelset.f)
     if isinstance(levelset, NodalFunction):
@@ -119,21 +150,23 @@ def _levelset_args(mesh, levelset, degree):
     raise TypeError("discrete_levelset must be a NodalFunction, a Quadric or a callable x -> phi")
 
 
-def _device_points(mesh, degree, nodal=None, expr=None):
-    """PHX_PHI_POINTS values produced on the device: a degree-2 nodal level-set tabulated by the library, or a
-    caller's torch expression at the physical detection points."""
+def _device_points(mesh, degree, nodal=None, expr=None, nodal_degree=2):
+    """PHX_PHI_POINTS values produced on the device: a degree-2 or degree-3 nodal level-set tabulated by the library,
+    or a caller's torch expression at the physical detection points."""
     import torch
     dev = torch.device("cuda", mesh.device)
-    cnt = C.c_int64(0)
-    L.check(L.lib.phx_levelset_points_count(mesh._h, degree, C.byref(cnt)))
-    out = torch.empty(cnt.value, dtype=torch.float64, device=dev)
     if nodal is not None:
-        if mesh.cell_type == "quadrilateral":
-            want, what = mesh.nv + mesh.nf + mesh.nc, "a Q2 level-set has one value per vertex, per facet and per cell"
-        elif mesh.cell_type in _EDGE_VERTS:
-            want, what = mesh.nv + mesh.ne, "a P2 level-set has one value per vertex and per edge"
+        # validated before anything is allocated or launched
+        if mesh.cell_type not in ("triangle", "quadrilateral", "tetrahedron"):
+            raise NotImplementedError("nodal level-sets are implemented on simplices and quadrilaterals")
+        want = mesh.lagrange_ndofs(nodal_degree)
+        if nodal_degree == 2 and mesh.cell_type == "quadrilateral":
+            what = "a Q2 level-set has one value per vertex, per facet and per cell"
+        elif nodal_degree == 2:
+            what = "a P2 level-set has one value per vertex and per edge"
         else:
-            raise NotImplementedError("P2 level-sets are implemented on simplices and quadrilaterals")
+            what = (f"a degree-3 level-set on a {mesh.cell_type} mesh has {want} values "
+                    "(layout: NodalFunction, mesh.lagrange_dof_points(3))")
         v = nodal
         if hasattr(v, "data_ptr"):
             if v.dtype != torch.float64 or not v.is_contiguous():
@@ -143,12 +176,20 @@ def _device_points(mesh, degree, nodal=None, expr=None):
             n = v.numel()
         else:
             v = np.ascontiguousarray(v, dtype=np.float64)
-            n = v.shape[0]
+            n = v.shape[0] if v.ndim == 1 else -1
         if n != want:
             raise ValueError(what)
+    cnt = C.c_int64(0)
+    L.check(L.lib.phx_levelset_points_count(mesh._h, degree, C.byref(cnt)))
+    out = torch.empty(cnt.value, dtype=torch.float64, device=dev)
+    if nodal is not None:
         p, loc = L.ptr(v)
         L.sync_torch_stream(dev)        # `out` was allocated (and possibly recycled) on torch's stream
-        L.check(L.lib.phx_levelset_eval_points(mesh._h, degree, p, loc, C.c_void_p(out.data_ptr())))
+        if nodal_degree == 2:
+            L.check(L.lib.phx_levelset_eval_points(mesh._h, degree, p, loc, C.c_void_p(out.data_ptr())))
+        else:
+            L.check(L.lib.phx_levelset_eval_points_deg(mesh._h, degree, nodal_degree, p, loc,
+                                                       C.c_void_p(out.data_ptr())))
         return L.PHI_POINTS, C.c_void_p(out.data_ptr()), L.DEVICE, (out, v)
     xq = torch.empty((cnt.value, mesh.gdim), dtype=torch.float64, device=dev)
     L.sync_torch_stream(dev)
@@ -346,8 +387,9 @@ def compute_tags_measures(mesh, discrete_levelset, detection_degree, box_mode=Fa
 
     Args:
         mesh: a `phifem_amd.Mesh`.
-        discrete_levelset: `NodalFunction` (P1 values), `Quadric`, or a callable x -> phi in
-            the reference's numpy convention (x[0], x[1], ...), evaluated like a UFL expression.
+        discrete_levelset: `NodalFunction` (Lagrange values of degree 1, 2 or 3, e.g. from `interpolate`),
+            `Quadric`, `DeviceExpression`, or a callable x -> phi in the reference's numpy convention
+            (x[0], x[1], ...), evaluated like a UFL expression.
         detection_degree: degree of the boundary-point detection rule.
         box_mode: False -> tags on the sub-mesh of cells tagged 1/2; True -> on the input mesh.
         single_layer_cut: force a single layer of cut cells.
