@@ -391,6 +391,10 @@ int phx_krylov_precond_disable(phx_system *s);
  * the box, sampled average seconds of one y-pass launch of the sine transforms (PHX_OPT_PROFILE_SPMV),
  * launches sampled, bytes per lattice value (4: f32 transforms, 8: f64)}. */
 int phx_precond_info(phx_system *s, double *out);
+/* After phx_solve: *on = 1 when the solve ran the identity loop (structured P1 system with the f64 lattice
+ * preconditioner: SpMVs over the stored rows only, A K_box^-1 = I on the stencil rows), 0 for the standard loop.
+ * PHX_KR_IDENTITY=0 in the environment forces the standard loop. */
+int phx_krylov_identity_loop(const phx_system *s, int *on);
 /* phase 0 begin, 1 begin2, 2 v=A phat, 3 s-update, 4 t=A shat, 5 x/r-update, 6 p-update + roll,
  * 7 phat = P p, 8 shat = P s (no-ops without a preconditioner); with the slab-exact preconditioner
  * (phx_precond_setup_global) 7 / 8 run its first half and 9 / 10 the second, the driver all-gathering the

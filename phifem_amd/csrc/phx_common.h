@@ -293,9 +293,14 @@ struct phx_system {
   struct phx_coarse *cc = nullptr; // coarse correction on top of the vertex blocks (phx_coarse.inc.hip)
   bool cc_tried = false;
   // PHX_OPT_DETERMINISTIC: every block of a dot-product kernel leaves its partial sum in its own entry of `dpart`
-  // ([2][dpart_cap]) instead of adding it to a slot atomically; k_fold_partials sums them in a fixed order
+  // ([4][dpart_cap]) instead of adding it to a slot atomically; k_fold_partials sums them in a fixed order
   double *dpart = nullptr;
   int64_t dpart_cap = 0, dpart_used = 0;
+  // Identity loop of the native solve (phx_solve.hip, kr_identity): on the rows the stencil applies, A K_box^-1 is the
+  // identity, so the SpMVs of an iteration cover the stored rows only and the vector passes stand in for the rest
+  int kr_ident_coef = -1;          // -1 not checked; 1: the stencil row equals the lattice row of the preconditioner
+  bool kr_ident_used = false;      // the last phx_solve ran the identity loop
+  uint32_t *kr_cmask = nullptr;    // [ceil(n / 32)] bit q: solver position q is applied by the stencil blocks
   // system assembled on the `inner` box of a caller-supplied mesh: vertex of s->mesh -> vertex of the caller's mesh
   // (applied where full DoF indices leave the library: the solution vector, phx_system_export's dof map)
   const int32_t *out_vertex = nullptr;

@@ -921,13 +921,15 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 // PHX_OPT_DETERMINISTIC: where the blocks of a dot-product kernel leave their partial sums (p0 == nullptr: atomics)
-struct DotPart { double *p0, *p1; };
-// fixed-order sum of nb partials per quantity into slot 0 of its slot set (the other slots stay zero: no atomics ran)
-__global__ void __launch_bounds__(1024) k_fold_partials(int64_t nb, DotPart part, double *out0, double *out1) {
+struct DotPart { double *p0, *p1, *p2 = nullptr, *p3 = nullptr; };
+// fixed-order sum of nb partials per quantity into slot 0 of its slot set (the other slots stay zero: no atomics ran);
+// add = 1: added to what slot 0 holds (a quantity the identity loop accumulates in two launches)
+__global__ void __launch_bounds__(1024) k_fold_partials(int64_t nb, DotPart part, double *out0, double *out1,
+                                                         double *out2, double *out3, int add) {
   __shared__ double red[1024];
-  for (int q = 0; q < 2; ++q) {
-    const double *p = q == 0 ? part.p0 : part.p1;
-    double *out = q == 0 ? out0 : out1;
+  for (int q = 0; q < 4; ++q) {
+    const double *p = q == 0 ? part.p0 : q == 1 ? part.p1 : q == 2 ? part.p2 : part.p3;
+    double *out = q == 0 ? out0 : q == 1 ? out1 : q == 2 ? out2 : out3;
     if (!p || !out) continue;
     double a = 0.0;
     for (int64_t i = threadIdx.x; i < nb; i += 1024) a += p[i];
@@ -937,7 +939,7 @@ __global__ void __launch_bounds__(1024) k_fold_partials(int64_t nb, DotPart part
       if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
       __syncthreads();
     }
-    if (threadIdx.x == 0) *out = red[0];
+    if (threadIdx.x == 0) *out = add ? *out + red[0] : red[0];
     __syncthreads();
   }
 }
@@ -960,7 +962,7 @@ k_spmv_sell(int64_t n, int64_t nslices, const int64_t *__restrict__ slice_ptr,
             const uint8_t *__restrict__ own, const double *__restrict__ d0,
             double *__restrict__ out0, double *__restrict__ out1, int xcd_group,
             const uint8_t *__restrict__ kind, const int32_t *__restrict__ rows, int64_t nb_sell, StencilArgs sa,
-            const uint8_t *__restrict__ bnd, DotPart part) {
+            const uint8_t *__restrict__ bnd, DotPart part, const double *__restrict__ d1, double *__restrict__ out2) {
   // bnd (nullable, multi-GPU): rows flagged here reference halo entries that are still in flight; this launch
   // leaves them (no store, no dot-product share) to k_spmv_bnd, which runs after the halo has been unpacked
   __shared__ double vi_dict[4][VI_MAX];
@@ -982,9 +984,10 @@ k_spmv_sell(int64_t n, int64_t nslices, const int64_t *__restrict__ slice_ptr,
   const int64_t s = bid * (int64_t)(blockDim.x >> 6) + (threadIdx.x >> 6);
   double acc = 0.0;
   int64_t row = -1;
-  double p0 = 0.0, p1 = 0.0;   // this lane's share of (y, d0) and (y, y)
+  double p0 = 0.0, p1 = 0.0, p2 = 0.0;   // this lane's share of (y, d0), (y, y) and (y, d1)
 #define PHX_DOT_ACC(a_, r_) \
-  do { if (DOTS > 0) { p0 = __builtin_fma((a_), d0[(r_)], p0); if (DOTS > 1) p1 = __builtin_fma((a_), (a_), p1); } } while (0)
+  do { if (DOTS > 0) { p0 = __builtin_fma((a_), d0[(r_)], p0); if (DOTS > 1) p1 = __builtin_fma((a_), (a_), p1); \
+                       if (DOTS > 2) p2 = __builtin_fma((a_), d1[(r_)], p2); } } while (0)
   if (blockIdx.x >= nb_sell) {
     // ---- rows of C0 of a structured system (blocks behind the SELL blocks of the same launch):
     // y_i = d x_i + cx (x_{i-1} + x_{i+1}) + cy (x_{i+oy+} + x_{i+oy-}) + cz (x_{i+oz+} + x_{i+oz-}), the row of the
@@ -1173,22 +1176,26 @@ k_spmv_sell(int64_t n, int64_t nslices, const int64_t *__restrict__ slice_ptr,
   }
 #undef PHX_DOT_ACC
   if (DOTS > 0) {
-    // DOTS == 1: out0 += (y, d0);  DOTS == 2: also out1 += (y, y)
-    __shared__ double red[2][4];
+    // DOTS == 1: out0 += (y, d0);  DOTS == 2: also out1 += (y, y);  DOTS == 3: also out2 += (y, d1)
+    __shared__ double red[3][4];
     p0 = wave_sum(p0);
     if (DOTS > 1) p1 = wave_sum(p1);
+    if (DOTS > 2) p2 = wave_sum(p2);
     const int w = threadIdx.x >> 6;
-    if (lane == 0) { red[0][w] = p0; red[1][w] = p1; }
+    if (lane == 0) { red[0][w] = p0; red[1][w] = p1; red[2][w] = p2; }
     __syncthreads();
     if (threadIdx.x == 0) {
       const double s0 = red[0][0] + red[0][1] + red[0][2] + red[0][3], s1 = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+      const double s2 = red[2][0] + red[2][1] + red[2][2] + red[2][3];
       if (part.p0) {   // PHX_OPT_DETERMINISTIC: one entry per block, summed in a fixed order by k_fold_partials
         part.p0[blockIdx.x] = s0;
         if (DOTS > 1) part.p1[blockIdx.x] = s1;
+        if (DOTS > 2) part.p2[blockIdx.x] = s2;
       } else {
         const int slot = (blockIdx.x & (NSLOT - 1)) * SLOT_STRIDE;
         unsafeAtomicAdd(out0 + slot, s0);
         if (DOTS > 1) unsafeAtomicAdd(out1 + slot, s1);
+        if (DOTS > 2) unsafeAtomicAdd(out2 + slot, s2);
       }
     }
   }
@@ -1347,8 +1354,12 @@ enum { R_RV = 0, R_TS = 1, R_TT = 2, R_SS = 3, R_RHO = 4, R_RR = 5 };
 // fold the 64 slots themselves -- no reduce / roll launches; the slot sets alternate with the
 // iteration parity so that a set is cleared while nobody reads it.
 
+// q >= 8: a further quantity in element q / 8 of the 64-byte slot lines of quantity q % 8 (identity loop)
 __host__ __device__ __forceinline__ double *slot_base(double *S, int par, int q) {
-  return S + P_OFF + ((par * 8 + q) * NSLOT) * SLOT_STRIDE;
+  return S + P_OFF + ((par * 8 + (q & 7)) * NSLOT) * SLOT_STRIDE + (q >> 3);
+}
+__host__ __device__ __forceinline__ const double *slot_base(const double *S, int par, int q) {
+  return slot_base(const_cast<double *>(S), par, q);
 }
 
 __device__ __forceinline__ void block_atomic_sum(double v, double *out, double *part = nullptr) {
@@ -1368,7 +1379,7 @@ __device__ __forceinline__ void block_atomic_sum(double v, double *out, double *
 // same bits from one load per lane (a serial 64-term sum per thread cost ~4 us per kernel).
 __device__ __forceinline__ double dotv(const double *S, int par, int q) {
   if (S[S_MODE] != 0.0) return S[R_OFF + q];
-  const double *p = S + P_OFF + ((par * 8 + q) * NSLOT) * SLOT_STRIDE;
+  const double *p = slot_base(S, par, q);
   return wave_sum(p[(threadIdx.x & (NSLOT - 1)) * SLOT_STRIDE]);
 }
 
@@ -1400,21 +1411,26 @@ struct RestOut {
   }
 };
 
-// r = rhat = p = own ? b : 0; y = 0; R_RHO += (b,b)
+__device__ __forceinline__ bool cmask_bit(const uint32_t *cmask, int64_t i) { return (cmask[i >> 5] >> (i & 31)) & 1u; }
+
+// r = rhat = p = own ? b : 0; y = 0; R_RHO += (b,b).  cmask (identity loop): also R_RV += (b,b) over the stencil rows,
+// the share of (rhat, A K_box^-1 p) of the first iteration that its SpMV no longer forms
 __global__ void __launch_bounds__(256)
 k_kr_begin(int64_t n, const int32_t *__restrict__ perm, const double *__restrict__ rhs,
            const uint8_t *__restrict__ own, double *__restrict__ b, double *__restrict__ r,
            double *__restrict__ rhat, double *__restrict__ p, double *__restrict__ y,
-           double *__restrict__ S, RestOut ro, DotPart part) {
-  double acc = 0.0;
+           double *__restrict__ S, RestOut ro, DotPart part, const uint32_t *__restrict__ cmask) {
+  double acc = 0.0, accc = 0.0;
   GRID_STRIDE(i, n) {
     const bool mine = !own || own[i];
     const double bi = mine ? rhs[perm[i]] : 0.0;
     b[i] = bi; r[i] = bi; rhat[i] = bi; p[i] = bi; y[i] = 0.0;
     ro.put(i, bi);
     acc += bi * bi;
+    if (cmask && cmask_bit(cmask, i)) accc += bi * bi;
   }
   block_atomic_sum(acc, slot_base(S, 0, R_RHO), part.p0);
+  if (cmask) block_atomic_sum(accc, slot_base(S, 0, R_RV), part.p1);
 }
 
 // Multi-GPU: the preconditioner must be chosen by ALL ranks together.  Phase 0 leaves this rank's veto (1: the
@@ -1546,23 +1562,27 @@ static inline dim3 vec_grid(int64_t n) { return dim3((unsigned)std::max<int64_t>
 // PHX_OPT_DETERMINISTIC: `nb` entries per quantity for the blocks of the next dot-product launch, behind the ones handed
 // out since the last fold (a product may take several launches: SELL + stencil blocks, interior + halo rows)
 static int det_part(phx_system *s, int64_t nb, DotPart *out) {
-  out->p0 = out->p1 = nullptr;
+  out->p0 = out->p1 = out->p2 = out->p3 = nullptr;
   if (!s->mesh->deterministic) return PHX_OK;
   if (!s->dpart) {
     s->dpart_cap = phx_div_up(s->nslices, 4) + phx_div_up(s->nstencil_pos, 1024) + 8 * s->st_chunk + 16384;
-    PHX_HIP(phx_malloc(&s->dpart, sizeof(double) * 2 * (size_t)s->dpart_cap));
+    PHX_HIP(phx_malloc(&s->dpart, sizeof(double) * 4 * (size_t)s->dpart_cap));
     s->dpart_used = 0;
   }
   PHX_REQUIRE(s->dpart_used + nb <= s->dpart_cap, PHX_ERR_HIP, "deterministic dot products: %lld partial sums exceed the buffer",
               (long long)(s->dpart_used + nb));
   out->p0 = s->dpart + s->dpart_used;
   out->p1 = s->dpart + s->dpart_cap + s->dpart_used;
+  out->p2 = s->dpart + 2 * s->dpart_cap + s->dpart_used;
+  out->p3 = s->dpart + 3 * s->dpart_cap + s->dpart_used;
   s->dpart_used += nb;
   return PHX_OK;
 }
-static int det_fold(phx_system *s, double *out0, double *out1) {
+static int det_fold(phx_system *s, double *out0, double *out1, double *out2 = nullptr, double *out3 = nullptr, int add = 0) {
   if (!s->mesh->deterministic || s->dpart_used == 0) return PHX_OK;
-  k_fold_partials<<<1, 1024, 0, s->mesh->stream>>>(s->dpart_used, DotPart{s->dpart, s->dpart + s->dpart_cap}, out0, out1);
+  const int64_t c = s->dpart_cap;
+  k_fold_partials<<<1, 1024, 0, s->mesh->stream>>>(s->dpart_used, DotPart{s->dpart, s->dpart + c, s->dpart + 2 * c, s->dpart + 3 * c},
+                                                   out0, out1, out2, out3, add);
   PHX_HIP(hipGetLastError());
   s->dpart_used = 0;
   return PHX_OK;
@@ -1621,11 +1641,11 @@ static int launch_spmv(phx_system *s, const double *vals, const double *x, doubl
   if (dots > 0 && nb > 0) PHX_CHECK(det_part(s, nb, &dp));
   if (nb == 0) {}
   else if (dots == 0)
-    k_spmv_sell<0><<<g2, block, 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, vals, x, y, own, d0, o0, o1, xg2, kinds, rows, nb_sell, sa, bnd, dp);
+    k_spmv_sell<0><<<g2, block, 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, vals, x, y, own, d0, o0, o1, xg2, kinds, rows, nb_sell, sa, bnd, dp, nullptr, nullptr);
   else if (dots == 1)
-    k_spmv_sell<1><<<g2, block, 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, vals, x, y, own, d0, o0, o1, xg2, kinds, rows, nb_sell, sa, bnd, dp);
+    k_spmv_sell<1><<<g2, block, 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, vals, x, y, own, d0, o0, o1, xg2, kinds, rows, nb_sell, sa, bnd, dp, nullptr, nullptr);
   else
-    k_spmv_sell<2><<<g2, block, 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, vals, x, y, own, d0, o0, o1, xg2, kinds, rows, nb_sell, sa, bnd, dp);
+    k_spmv_sell<2><<<g2, block, 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, vals, x, y, own, d0, o0, o1, xg2, kinds, rows, nb_sell, sa, bnd, dp, nullptr, nullptr);
   PHX_HIP(hipGetLastError());
   if (s->p2s && s->p2s->nrun > 0 && part_of == 0 && part != 1) {
     // structured P2: the interior rows from the eight class stencils, one wavefront per run
@@ -1781,17 +1801,128 @@ k_true_residual(int64_t n, const uint8_t *__restrict__ own, const double *__rest
   block_atomic_sum(acc, slot_base(S, 0, R_RR), part.p0);
 }
 
-// restart of the recurrences from r (x keeps its value): rhat = p = r, rho = (r, r) = S[R_OFF + R_RR]
+// restart of the recurrences from r (x keeps its value): rhat = p = r, rho = (r, r) = S[R_OFF + R_RR].
+// cmask (identity loop): (r, r) over the stencil rows into R_RV of slot set `par` (see k_kr_begin)
 __global__ void __launch_bounds__(256)
 k_restart_from_r(int64_t n, const double *__restrict__ r, double *__restrict__ rhat, double *__restrict__ p,
-                 double *__restrict__ S, RestOut ro) {
-  GRID_STRIDE(i, n) { const double ri = r[i]; rhat[i] = ri; p[i] = ri; ro.put(i, ri); }
+                 double *__restrict__ S, RestOut ro, const uint32_t *__restrict__ cmask = nullptr, int par = 0,
+                 DotPart part = DotPart{nullptr, nullptr}) {
+  double accc = 0.0;
+  GRID_STRIDE(i, n) {
+    const double ri = r[i]; rhat[i] = ri; p[i] = ri; ro.put(i, ri);
+    if (cmask && cmask_bit(cmask, i)) accc += ri * ri;
+  }
+  if (cmask) block_atomic_sum(accc, slot_base(S, par, R_RV), part.p0);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     const double rr = S[R_OFF + R_RR];
     S[S_RHO] = rr; S[S_RHO_NEXT] = rr; S[S_RR] = rr; S[S_RR0] = rr; S[S_RR0 + 1] = rr;
     S[S_ALPHA] = 1.0; S[S_OMEGA] = 1.0;
     S[S_RESTARTS] += 1.0;
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Identity loop of the native solve (kr_identity).  On a structured P1 system with unscaled u columns and the f64
+// lattice preconditioner M = R K_box^-1 R^T, a row the stencil blocks apply IS the lattice row of K_box and all of its
+// columns are active lattice points, so (A M p)_i = p_i and (A M s)_i = s_i there ("C rows", bit i of cmask).  The
+// two SpMVs of an iteration then cover the stored rows only ("B rows"); v and t are never formed on C rows, and the
+// vector passes supply the C-row shares of the dot products from the data they touch anyway:
+//   (rhat, v)_C = (rhat, p)_C               by the producer of p (begin, restart, k_ident_xrp) into R_RV
+//   (t, s)_C = (t, t)_C = (s, s)_C, (rhat, t)_C = (rhat, s)_C     by k_ident_s
+// and rho_new = (rhat, s) - omega (rhat, t) is known before r is formed, so x, r and p are updated in ONE pass.
+// Quantities of a slot set (I_RT_B sits in element 1 of the slot lines of R_RV):
+enum { I_RV = R_RV, I_TS_B = R_TS, I_TT_B = R_TT, I_SS = R_SS, I_RS = R_RHO, I_RR = R_RR, I_SS_C = 6, I_RS_C = 7,
+       I_RT_B = 8 };
+
+// bits of the solver positions of the stencil runs (one thread per run, one atomic per touched word)
+__global__ void k_ident_mask(int32_t nseg, const int32_t *__restrict__ seg, uint32_t *__restrict__ cmask) {
+  const int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (k >= nseg) return;
+  const int64_t a = seg[6 * k], e = seg[6 * k + 1];
+  for (int64_t w = a >> 5; w << 5 < e; ++w) {
+    const int64_t lo = std::max<int64_t>(a, w << 5) - (w << 5), hi = std::min<int64_t>(e, (w + 1) << 5) - (w << 5);
+    const uint32_t bits = (hi - lo == 32 ? 0xffffffffu : ((1u << (hi - lo)) - 1u)) << lo;
+    atomicOr(&cmask[w], bits);
+  }
+}
+
+// s = r - alpha v (C rows: v = p); (rhat, s), (s, s), and over the C rows (s, s), (rhat, s).  Block 0 clears the
+// other slot set (read for the last time by the previous iteration; k_ident_xrp of this one starts filling it)
+__global__ void __launch_bounds__(256)
+k_ident_s(int64_t n, int par, const uint32_t *__restrict__ cmask, const double *__restrict__ r,
+          const double *__restrict__ v, const double *__restrict__ p, const double *__restrict__ rhat,
+          double *__restrict__ sv, double *__restrict__ S, RestOut ro, DotPart part) {
+  const double rho = S[S_RHO_NEXT];
+  const double alpha = rho / dotv(S, par, I_RV);
+  double rs = 0.0, ss = 0.0, ssc = 0.0, rsc = 0.0;
+  GRID_STRIDE(i, n) {
+    const bool c = cmask_bit(cmask, i);
+    const double si = r[i] - alpha * (c ? p[i] : v[i]);
+    sv[i] = si;
+    ro.put(i, si);
+    const double hi = rhat[i];
+    rs += hi * si;
+    ss += si * si;
+    if (c) { ssc += si * si; rsc += hi * si; }
+  }
+  if (blockIdx.x == 0) {
+    double *nxt = slot_base(S, par ^ 1, 0);
+    for (int k = threadIdx.x; k < 8 * NSLOT * SLOT_STRIDE; k += blockDim.x) nxt[k] = 0.0;
+    if (threadIdx.x == 0) { S[S_ALPHA] = alpha; S[S_RHO] = rho; }
+  }
+  block_atomic_sum(rs, slot_base(S, par, I_RS), part.p0);
+  block_atomic_sum(ss, slot_base(S, par, I_SS), part.p1);
+  block_atomic_sum(ssc, slot_base(S, par, I_SS_C), part.p2);
+  block_atomic_sum(rsc, slot_base(S, par, I_RS_C), part.p3);
+}
+
+// omega = (t, s) / (t, t), rho_new = (rhat, s) - omega (rhat, t), beta as k_update_p; the breakdown test of kr_restart
+// on rho_new and (r, r) = (s, s) - 2 omega (t, s) + omega^2 (t, t).  Then, per row (C rows: t = s, v = p):
+//   x += alpha phat + omega shat,  r = s - omega t,  p = r + beta (p - omega v)   (restart: p = rhat = r)
+// accumulating (r, r) for the host check and (rhat, p)_C into R_RV of the next slot set
+__global__ void __launch_bounds__(256)
+k_ident_xrp(int64_t n, int par, const uint32_t *__restrict__ cmask, const double *__restrict__ phat,
+            const double *__restrict__ shat, const double *__restrict__ sv, const double *__restrict__ t,
+            const double *__restrict__ v, double *__restrict__ rhat, double *__restrict__ x, double *__restrict__ r,
+            double *__restrict__ p, double *__restrict__ S, RestOut ro, DotPart part) {
+  const double alpha = S[S_ALPHA];
+  const double ssc = dotv(S, par, I_SS_C);
+  const double ts = dotv(S, par, I_TS_B) + ssc, tt = dotv(S, par, I_TT_B) + ssc;
+  const double omega = ts / tt;
+  const double rho_new = dotv(S, par, I_RS) - omega * (dotv(S, par, I_RT_B) + dotv(S, par, I_RS_C));
+  const double rr = fmax(0.0, dotv(S, par, I_SS) - 2.0 * omega * ts + omega * omega * tt);
+  const double beta = (rho_new / S[S_RHO]) * (alpha / omega);
+  const bool restart = !(fabs(beta) <= 1.0e300) || !(fabs(rho_new) > 1.0e-14 * rr);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    S[S_OMEGA] = omega;
+    S[S_RHO_NEXT] = restart ? rr : rho_new;
+    S[S_RR] = rr;
+    if (restart) S[S_RESTARTS] += 1.0;
+    S[S_RR0 + (par ^ 1)] = restart ? rr : S[S_RR0 + par];
+  }
+  double arr = 0.0, apc = 0.0;
+  GRID_STRIDE(i, n) {
+    const bool c = cmask_bit(cmask, i);
+    x[i] += alpha * phat[i] + omega * shat[i];
+    const double si = sv[i];
+    const double ri = si - omega * (c ? si : t[i]);
+    r[i] = ri;
+    arr += ri * ri;
+    double pi;
+    if (restart) {
+      pi = ri;
+      rhat[i] = ri;
+      if (c) apc += ri * ri;
+    } else {
+      const double po = p[i];
+      pi = ri + beta * (po - omega * (c ? po : v[i]));
+      if (c) apc += rhat[i] * pi;
+    }
+    p[i] = pi;
+    ro.put(i, pi);
+  }
+  block_atomic_sum(arr, slot_base(S, par, I_RR), part.p0);
+  block_atomic_sum(apc, slot_base(S, par ^ 1, I_RV), part.p1);
 }
 
 struct KrVecs {
@@ -1809,6 +1940,61 @@ static inline KrVecs kr_vecs(phx_system *s) {
   return V;
 }
 static inline double *kr_scal(phx_system *s) { return s->kr_scal ? s->kr_scal : s->scal; }
+
+// Identity loop in force for this solve?  Native single-rank loop only (PHX_KR_IDENTITY=0 forces the standard one):
+// structured P1 system, unscaled u columns, the f64 lattice preconditioner of one rank, stencil rows present, and
+// the stencil row equal to the lattice row {2 (cx + cy + cz), -cx, -cy, -cz} of K_box (read once per system).
+static int kr_identity(phx_system *s, bool *on) {
+  *on = false;
+  static const int env = getenv("PHX_KR_IDENTITY") ? atoi(getenv("PHX_KR_IDENTITY")) : 1;
+  if (!env || !s->structured || !s->u_unscaled || s->u_weighted || s->p2s || s->precond_state != 1 || !s->precond ||
+      s->precond->f32 || s->precond->dist || s->own || s->kr_work || s->bnd || s->nseg <= 0 || s->n == 0)
+    return PHX_OK;
+  hipStream_t st = s->mesh->stream;
+  if (s->kr_ident_coef < 0) {
+    double h[4];
+    PHX_HIP(hipMemcpyAsync(h, s->stencil, sizeof(h), hipMemcpyDeviceToHost, st));
+    PHX_HIP(hipStreamSynchronize(st));
+    const double *c = s->precond->g.c;
+    const double d = 2.0 * (c[0] + c[1] + c[2]), tol = 1.0e-14 * fabs(d);
+    s->kr_ident_coef = d > 0.0 && fabs(h[0] - d) <= tol && fabs(h[1] + c[0]) <= tol && fabs(h[2] + c[1]) <= tol &&
+                       fabs(h[3] + c[2]) <= tol ? 1 : 0;
+  }
+  if (s->kr_ident_coef != 1) return PHX_OK;
+  if (!s->kr_cmask) {
+    const int64_t nw = phx_div_up(s->n, 32);
+    PHX_HIP(phx_malloc(&s->kr_cmask, sizeof(uint32_t) * (size_t)nw));
+    PHX_HIP(hipMemsetAsync(s->kr_cmask, 0, sizeof(uint32_t) * (size_t)nw, st));
+    k_ident_mask<<<dim3((unsigned)phx_div_up(s->nseg, 256)), dim3(256), 0, st>>>(s->nseg, s->seg, s->kr_cmask);
+    PHX_HIP(hipGetLastError());
+  }
+  *on = true;
+  return PHX_OK;
+}
+
+// SpMV of the identity loop: the SELL-16 blocks of the stored rows alone (the rows of the stencil blocks are left
+// unwritten).  dots 1: o0 += (y, d0);  dots 3: o0 += (y, d0), o1 += (y, y), o2 += (y, d1).  PHX_OPT_DETERMINISTIC:
+// the partial sums are ADDED to slot 0 (R_RV already holds the C-row share there).
+static int launch_spmv_stored(phx_system *s, const double *x, double *y, int dots, const double *d0, const double *d1,
+                              double *o0, double *o1, double *o2) {
+  hipStream_t st = s->mesh->stream;
+  const int64_t nb = (phx_div_up(s->nslices, 4) + 7) & ~(int64_t)7;   // a multiple of 8, as launch_spmv
+  if (nb == 0) return PHX_OK;
+  static const int xg_env = getenv("PHX_SPMV_XCD_GROUP") ? atoi(getenv("PHX_SPMV_XCD_GROUP")) : -1;
+  const int xg = xg_env >= 0 ? xg_env : s->mesh->spmv_xcd_group;
+  const StencilArgs sa{0, nullptr, 0, nullptr, nullptr, 0, nullptr};
+  DotPart dp{nullptr, nullptr};
+  PHX_CHECK(det_part(s, nb, &dp));
+  if (dots == 1)
+    k_spmv_sell<1><<<dim3((unsigned)nb), dim3(256), 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, s->sell_val, x, y, nullptr,
+                                                             d0, o0, nullptr, xg, s->sell_kind, s->sell_rows, nb, sa, nullptr, dp,
+                                                             nullptr, nullptr);
+  else
+    k_spmv_sell<3><<<dim3((unsigned)nb), dim3(256), 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, s->sell_val, x, y, nullptr,
+                                                             d0, o0, o1, xg, s->sell_kind, s->sell_rows, nb, sa, nullptr, dp, d1, o2);
+  PHX_HIP(hipGetLastError());
+  return det_fold(s, o0, dots == 3 ? o1 : nullptr, dots == 3 ? o2 : nullptr, nullptr, 1);
+}
 
 // phases: 0 begin (local (b,b) -> R_RHO), 1 begin2 (after all-reduce), 2 v = A p (+R_RV),
 // 3 s-update, 4 t = A s (+R_TS, R_TT), 5 x/r-update (+R_RHO, R_RR), 6 p-update + roll.
@@ -1837,6 +2023,9 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
       if (!s->pvec) PHX_HIP(phx_malloc(&s->pvec, sizeof(double) * (size_t)n * 2));
       PHX_HIP(hipMemsetAsync(s->pvec, 0, sizeof(double) * (size_t)n * 2, st));
     }
+    bool ident = false;
+    if (mode == 0) PHX_CHECK(kr_identity(s, &ident));
+    s->kr_ident_used = ident;
   }
   const KrVecs V = kr_vecs(s);
   double *S = kr_scal(s);
@@ -1851,8 +2040,9 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
       {
         DotPart dp{nullptr, nullptr};
         PHX_CHECK(det_part(s, vec_grid(n).x, &dp));
-        k_kr_begin<<<vec_grid(n), block, 0, st>>>(n, s->perm, s->rhs, s->own, V.b, V.r, V.rhat, V.p, V.y, S, rop, dp);
-        PHX_CHECK(det_fold(s, slot_base(S, 0, R_RHO), nullptr));
+        const uint32_t *cm = s->kr_ident_used ? s->kr_cmask : nullptr;
+        k_kr_begin<<<vec_grid(n), block, 0, st>>>(n, s->perm, s->rhs, s->own, V.b, V.r, V.rhat, V.p, V.y, S, rop, dp, cm);
+        PHX_CHECK(det_fold(s, slot_base(S, 0, R_RHO), cm ? slot_base(S, 0, R_RV) : nullptr));
       }
       k_reduce_slots<<<1, 64, 0, st>>>(S, 0, R_RHO, 1, 1);
       if (mode) k_set_scalar<<<1, 1, 0, st>>>(S + R_OFF + R_RR, s->precond_veto ? 1.0 : 0.0);
@@ -1939,6 +2129,37 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
     case 13:
       k_restart_from_r<<<vec_grid(n), block, 0, st>>>(n, V.r, V.rhat, V.p, S, rop);
       break;
+    // --- identity loop (kr_identity; native loop only): 52 v = A phat on the stored rows, 53 s pass, 54 t = A shat on the
+    // stored rows, 55 x / r / p pass (replaces 5 and 6)
+    case 52:
+      PHX_CHECK(prof_begin(s));
+      PHX_CHECK(launch_spmv_stored(s, V.phat, V.v, 1, V.rhat, nullptr, slot_base(S, par, I_RV), nullptr, nullptr));
+      PHX_CHECK(prof_end(s));
+      break;
+    case 53:
+      {
+        DotPart dp{nullptr, nullptr};
+        PHX_CHECK(det_part(s, vec_grid(n).x, &dp));
+        k_ident_s<<<vec_grid(n), block, 0, st>>>(n, par, s->kr_cmask, V.r, V.v, V.p, V.rhat, V.sv, S, ros, dp);
+        PHX_CHECK(det_fold(s, slot_base(S, par, I_RS), slot_base(S, par, I_SS), slot_base(S, par, I_SS_C),
+                           slot_base(S, par, I_RS_C)));
+      }
+      break;
+    case 54:
+      PHX_CHECK(prof_begin(s));
+      PHX_CHECK(launch_spmv_stored(s, V.shat, V.t, 3, V.sv, V.rhat, slot_base(S, par, I_TS_B), slot_base(S, par, I_TT_B),
+                                   slot_base(S, par, I_RT_B)));
+      PHX_CHECK(prof_end(s));
+      break;
+    case 55:
+      {
+        DotPart dp{nullptr, nullptr};
+        PHX_CHECK(det_part(s, vec_grid(n).x, &dp));
+        k_ident_xrp<<<vec_grid(n), block, 0, st>>>(n, par, s->kr_cmask, V.phat, V.shat, V.sv, V.t, V.v, V.rhat, V.y, V.r, V.p,
+                                                   S, rop, dp);
+        PHX_CHECK(det_fold(s, slot_base(S, par, I_RR), slot_base(S, par ^ 1, I_RV), nullptr, nullptr, 1));
+      }
+      break;
     case 9:   // slab-exact preconditioner: second half of phase 7, after the all-gather of the carries
       if (s->precond_state == 1 && s->precond->dist) PHX_CHECK(box_precond_apply(s, V.p, V.phat, 2));
       break;
@@ -1986,6 +2207,12 @@ extern "C" int phx_krylov_finish(phx_system *s, double *x_out, int loc) {
 extern "C" int phx_krylov_precond_active(const phx_system *s, int *active) {
   // 1: the SpMV inputs are phat / shat (box preconditioner, or the u-block Jacobi of a structured system)
   *active = (s->precond_state == 1 || s->u_unscaled || s->bj) ? 1 : 0;
+  return PHX_OK;
+}
+
+// 1 when the last phx_solve of `s` ran the identity loop (kr_identity), 0 for the standard loop
+extern "C" int phx_krylov_identity_loop(const phx_system *s, int *on) {
+  *on = s->kr_ident_used ? 1 : 0;
   return PHX_OK;
 }
 
@@ -2076,6 +2303,7 @@ extern "C" int phx_solve(phx_system *s, int method, double rtol, int64_t max_ite
   // observed convergence rate: half of the predicted remaining iterations ahead (at most 12, at least 2) -- near the
   // end every 2nd iteration, so no iteration is wasted on a late check (28 -> ~9 drains over 56 iterations).
   const bool pc = s->precond_state == 1;
+  const bool ident = s->kr_ident_used;   // decided by phase 0 (kr_identity)
   PHX_CHECK(kr_phase(s, 1, 0, 0));
   PHX_HIP(hipMemcpyAsync(s->scal_h, S, sizeof(double) * 16, hipMemcpyDeviceToHost, st));
   PHX_HIP(hipStreamSynchronize(st));
@@ -2091,8 +2319,8 @@ extern "C" int phx_solve(phx_system *s, int method, double rtol, int64_t max_ite
   for (;;) {
     while (bb != 0.0 && it < max_iter) {
       const int par = (int)(it & 1);
-      static const int seq[6] = {7, 2, 3, 8, 4, 5};
-      for (int ph : seq) PHX_CHECK(kr_phase(s, ph, 0, par));
+      static const int seq[6] = {7, 2, 3, 8, 4, 5}, seq_ident[6] = {7, 52, 53, 8, 54, 55};
+      for (int ph : ident ? seq_ident : seq) PHX_CHECK(kr_phase(s, ph, 0, par));
       spmvs += 2;
       ++it;
       if (it >= next_check || it == max_iter) {
@@ -2121,7 +2349,7 @@ extern "C" int phx_solve(phx_system *s, int method, double rtol, int64_t max_ite
         last_relres = relres;
         next_check = it + step;
       }
-      PHX_CHECK(kr_phase(s, 6, 0, par));
+      if (!ident) PHX_CHECK(kr_phase(s, 6, 0, par));
     }
     if (rc != PHX_OK || bb == 0.0 || !(relres <= rtol)) break;
     // verify
@@ -2145,7 +2373,14 @@ extern "C" int phx_solve(phx_system *s, int method, double rtol, int64_t max_ite
     {
       const bool rest_out = s->precond_state == 1 && V.phat != V.p;
       const RestOut rop{rest_out ? V.phat : nullptr, s->structured ? nullptr : s->perm, s->nu};
-      k_restart_from_r<<<vec_grid(s->n), dim3(256), 0, st>>>(s->n, V.r, V.rhat, V.p, S, rop);
+      if (ident) {   // (r, r) over the stencil rows = (rhat, A phat)_C of the next iteration, parity it & 1
+        DotPart dp{nullptr, nullptr};
+        PHX_CHECK(det_part(s, vec_grid(s->n).x, &dp));
+        k_restart_from_r<<<vec_grid(s->n), dim3(256), 0, st>>>(s->n, V.r, V.rhat, V.p, S, rop, s->kr_cmask, (int)(it & 1), dp);
+        PHX_CHECK(det_fold(s, slot_base(S, (int)(it & 1), R_RV), nullptr));
+      } else {
+        k_restart_from_r<<<vec_grid(s->n), dim3(256), 0, st>>>(s->n, V.r, V.rhat, V.p, S, rop);
+      }
     }
     last_relres = relres;
     last_check = it;

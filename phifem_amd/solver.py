@@ -202,6 +202,9 @@ class PhiFEMSolver:
         self.stats = {"iterations": int(st[0]), "relres": st[1], "seconds": st[2],
                       "spmv": int(st[3]), "spmv_avg_s": st[4], "spmv_timed": int(st[5]),
                       "converged": bool(st[6]), "restarts": int(st[7])}
+        ident = C.c_int(0)
+        L.check(L.lib.phx_krylov_identity_loop(self._sys, C.byref(ident)))
+        self.stats["identity_loop"] = bool(ident.value)
         self.stats.update(self.precond_info())
         check_converged(self.stats, rtol, strict)
         return out
