@@ -395,13 +395,18 @@ int phx_precond_info(phx_system *s, double *out);
  * preconditioner: SpMVs over the stored rows only, A K_box^-1 = I on the stencil rows), 0 for the standard loop.
  * PHX_KR_IDENTITY=0 in the environment forces the standard loop. */
 int phx_krylov_identity_loop(const phx_system *s, int *on);
-/* phase 0 begin, 1 begin2, 2 v=A phat, 3 s-update, 4 t=A shat, 5 x/r-update, 6 p-update + roll,
- * 7 phat = P p, 8 shat = P s (no-ops without a preconditioner); with the slab-exact preconditioner
- * (phx_precond_setup_global) 7 / 8 run its first half and 9 / 10 the second, the driver all-gathering the
- * carry buffer in between.  Multi-GPU overlap: 20 | 21 (40 | 41) = phase 2 (4) in two launches -- the rows that
- * read no halo entry, then (after the driver has unpacked the halo) the rows that do; they need the row flags
- * phx_solve_distributed builds.  True-residual verification: 11 t = A y (after a halo exchange of y), 12 r = b - t and
- * (r, r) -> scal[8 + 5] (all-reduced by the driver), 13 restart of the recurrences from r. */
+/* Phases (the KrPhase names of phx_solve.hip): 0 KR_BEGIN, 1 KR_BEGIN2, 2 KR_SPMV_P v = A phat, 3 KR_UPDATE_S
+ * s-update, 4 KR_SPMV_S t = A shat, 5 KR_UPDATE_XR x/r-update, 6 KR_UPDATE_P p-update + roll, 7 KR_PRECOND_P phat = P p,
+ * 8 KR_PRECOND_S shat = P s (no-ops without a preconditioner); with the slab-exact preconditioner
+ * (phx_precond_setup_global) 7 / 8 run its first half and 9 KR_EXACT_P / 10 KR_EXACT_S the second, the driver
+ * all-gathering the carry buffer in between.  Multi-GPU overlap: 20 KR_SPMV_P_INNER | 21 KR_SPMV_P_HALO
+ * (40 KR_SPMV_S_INNER | 41 KR_SPMV_S_HALO) = phase 2 (4) in two launches -- the rows that read no halo entry, then
+ * (after the driver has unpacked the halo) the rows that do; they need the row flags phx_solve_distributed builds.
+ * True-residual verification: 11 KR_TRUE_SPMV t = A y (after a halo exchange of y), 12 KR_TRUE_RESIDUAL r = b - t and
+ * (r, r) -> scal[8 + 5] (all-reduced by the driver), 13 KR_RESTART restart of the recurrences from r.  Partitioned
+ * coarse correction: 30 KR_CC_RESTRICT_P / 32 KR_CC_RESTRICT_S restrict p / s, 31 KR_CC_ADD_P / 33 KR_CC_ADD_S add the
+ * prolonged correction.  52-55 (KR_ID_SPMV_P, KR_ID_UPDATE_S, KR_ID_SPMV_S, KR_ID_UPDATE_XRP) belong to the identity
+ * loop of phx_solve and are not meant for this API. */
 int phx_krylov_phase(phx_system *s, int phase);
 int phx_krylov_finish(phx_system *s, double *x, int loc);
 /* reset != 0: arm the SpMV event profile; else collect {average seconds, launches timed}. */

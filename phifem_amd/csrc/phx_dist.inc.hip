@@ -218,11 +218,13 @@ static int allgather_carries(phx_system *s, phx_comm *c) {
   return PHX_OK;
 }
 
-static int allreduce_R(phx_system *s, phx_comm *c, int lo, int hi) {
+static int allreduce_sum(phx_comm *c, double *buf, size_t count, hipStream_t st) {
   if (c->nranks == 1) return PHX_OK;
-  double *R = kr_scal(s) + R_OFF + lo;
-  PHX_NCCL(g_nccl.AllReduce(R, R, (size_t)(hi - lo), PHX_NCCL_FLOAT64, PHX_NCCL_SUM, c->comm, s->mesh->stream));
+  PHX_NCCL(g_nccl.AllReduce(buf, buf, count, PHX_NCCL_FLOAT64, PHX_NCCL_SUM, c->comm, st));
   return PHX_OK;
+}
+static int allreduce_R(phx_system *s, phx_comm *c, int lo, int hi) {
+  return allreduce_sum(c, kr_scal(s) + R_OFF + lo, (size_t)(hi - lo), s->mesh->stream);
 }
 
 // Watchdog of the host synchronisations inside the distributed loop: a collective whose partner never arrives would
@@ -253,6 +255,18 @@ static int stream_sync_watchdog(hipStream_t st, const char *what) {
   }
 }
 
+// What the BiCGStab driver of phx_solve.hip (kr_drive) needs to run mode 1: nullptr there means the single-rank loop.
+struct KrDist {
+  phx_comm *c;
+  const HaloSpec *H;
+  bool overlap;   // halo exchanges overlapped with the rows of the SpMV that read no halo entry
+  bool exact;     // slab-exact preconditioner: all-gather of the carries between its two halves
+  bool coarse;    // partitioned coarse correction: all-reduce of the coarse vector
+  bool pc_all;    // every rank kept the box preconditioner (check schedule, stats[7])
+};
+static int kr_drive(phx_system *s, const KrDist *d, double rtol, int64_t max_iter, double *x_out, int loc,
+                    double *stats);
+
 // peers[npeers], counts[2*npeers] = {nsend, nrecv} per peer, idx[2*npeers] device pointers
 // {send_idx, recv_idx} (int64 solver positions), work/scal/own as phx_krylov_attach (already
 // attached).  stats[8] as phx_solve: relres / converged refer to the TRUE residual b - A x (verified with one more
@@ -281,8 +295,6 @@ extern "C" int phx_solve_distributed(phx_system *s, phx_comm *c, int npeers, con
   static const bool overlap_env = !(getenv("PHX_DIST_OVERLAP") && atoi(getenv("PHX_DIST_OVERLAP")) == 0);
   // a local matter: sends and receives pair up whatever stream each side issues them on
   const bool overlap = overlap_env && c->overlap_ok && c->nranks > 1 && npeers > 0 && c->cs != nullptr;
-  double *S = kr_scal(s);
-  int rc = PHX_OK;
   auto body = [&]() -> int {
     if (overlap) {
       const int64_t *rl[2] = {H.recv_idx[0], H.recv_idx[1]};
@@ -291,10 +303,10 @@ extern "C" int phx_solve_distributed(phx_system *s, phx_comm *c, int npeers, con
     }
     PHX_CHECK(prof_reset(s));
     PHX_CHECK(phx_begin_timing(m));
-    PHX_CHECK(phx_krylov_phase(s, 0));
+    PHX_CHECK(kr_phase(s, KR_BEGIN, 1, 0));
     PHX_CHECK(allreduce_R(s, c, R_RHO, R_RR + 1));  // (b, b) and the preconditioner vetoes
-    PHX_CHECK(phx_krylov_phase(s, 1));
-    PHX_HIP(hipMemcpyAsync(s->scal_h, S, sizeof(double) * 16, hipMemcpyDeviceToHost, st));
+    PHX_CHECK(kr_phase(s, KR_BEGIN2, 1, 0));
+    PHX_HIP(hipMemcpyAsync(s->scal_h, kr_scal(s), sizeof(double) * 16, hipMemcpyDeviceToHost, st));
     PHX_CHECK(stream_sync_watchdog(st, "start of the distributed solve"));
     // the preconditioner is a COLLECTIVE choice: one veto and every rank iterates with Jacobi, so that all
     // ranks exchange the same vectors and test convergence at the same iterations
@@ -304,115 +316,14 @@ extern "C" int phx_solve_distributed(phx_system *s, phx_comm *c, int npeers, con
     // a rank without rows of its own still joins the reductions
     if (s->el_nblk > 0 && m->precond != 0 && !s->cc && !s->cc_tried) {
       s->cc_tried = true;
-      const CcReduce red = [&](double *buf, size_t count) -> int {
-        if (c->nranks == 1) return PHX_OK;
-        PHX_NCCL(g_nccl.AllReduce(buf, buf, count, PHX_NCCL_FLOAT64, PHX_NCCL_SUM, c->comm, st));
-        return PHX_OK;
-      };
+      const CcReduce red = [&](double *buf, size_t count) -> int { return allreduce_sum(c, buf, count, st); };
       PHX_CHECK(coarse_build(s, s->el_nblk, &s->cc, &red));
     }
-    const bool coarse = s->cc != nullptr && s->cc->dist;
-    auto coarse_step = [&](int ph_restrict, int ph_add) -> int {
-      PHX_CHECK(phx_krylov_phase(s, ph_restrict));
-      if (c->nranks > 1) PHX_NCCL(g_nccl.AllReduce(s->cc->gc, s->cc->gc, (size_t)s->cc->nc, PHX_NCCL_FLOAT64, PHX_NCCL_SUM, c->comm, st));
-      return phx_krylov_phase(s, ph_add);
-    };
-    const KrVecs V = kr_vecs(s);  // after the vote: the preconditioner decides where phat / shat live
-    const bool exact = s->precond_state == 1 && s->precond->dist;   // the same on every rank (set up from all-reduced numbers)
-    const double bb = s->scal_h[S_BB];
-    // convergence checks as in phx_solve: scheduled from the observed rate (every rank reads the same all-reduced
-    // numbers, so every rank schedules the same checks)
-    int64_t it = 0, spmvs = 0, next_check = pc_all ? 2 : 8, last_check = 0;
-    double relres = bb == 0.0 ? 0.0 : 1.0, last_relres = 1.0;
-    int verifications = 0;
-    for (;;) {
-      while (bb != 0.0 && it < max_iter) {
-        PHX_CHECK(phx_krylov_phase(s, 7));
-        if (exact) { PHX_CHECK(allgather_carries(s, c)); PHX_CHECK(phx_krylov_phase(s, 9)); }
-        if (coarse) PHX_CHECK(coarse_step(30, 31));
-        if (overlap) {
-          PHX_CHECK(halo_begin(s, c, H, V.phat, true));
-          PHX_CHECK(phx_krylov_phase(s, 20));
-          PHX_CHECK(halo_end(s, c, H, V.phat, true));
-          PHX_CHECK(phx_krylov_phase(s, 21));
-        } else {
-          PHX_CHECK(halo_exchange(s, c, H, V.phat));
-          PHX_CHECK(phx_krylov_phase(s, 2));
-        }
-        PHX_CHECK(allreduce_R(s, c, R_RV, R_RV + 1));
-        PHX_CHECK(phx_krylov_phase(s, 3));
-        PHX_CHECK(phx_krylov_phase(s, 8));
-        if (exact) { PHX_CHECK(allgather_carries(s, c)); PHX_CHECK(phx_krylov_phase(s, 10)); }
-        if (coarse) PHX_CHECK(coarse_step(32, 33));
-        if (overlap) {
-          PHX_CHECK(halo_begin(s, c, H, V.shat, true));
-          PHX_CHECK(phx_krylov_phase(s, 40));
-          PHX_CHECK(halo_end(s, c, H, V.shat, true));
-          PHX_CHECK(phx_krylov_phase(s, 41));
-        } else {
-          PHX_CHECK(halo_exchange(s, c, H, V.shat));
-          PHX_CHECK(phx_krylov_phase(s, 4));
-        }
-        PHX_CHECK(allreduce_R(s, c, R_TS, R_TT + 1));
-        PHX_CHECK(phx_krylov_phase(s, 5));
-        PHX_CHECK(allreduce_R(s, c, R_RHO, R_RR + 1));
-        spmvs += 2;
-        ++it;
-        if (it >= next_check || it == max_iter) {
-          PHX_HIP(hipMemcpyAsync(s->scal_h, S, sizeof(double) * 16, hipMemcpyDeviceToHost, st));
-          PHX_CHECK(stream_sync_watchdog(st, "convergence check of the distributed solve"));
-          const double rr = s->scal_h[R_OFF + R_RR];
-          relres = sqrt(rr / bb);
-          if (!(rr == rr) || !(fabs(rr) <= 1.0e300)) {
-            phx_set_error("BiCGStab breakdown at iteration %lld (rr=%g)", (long long)it, rr);
-            return PHX_ERR_BREAKDOWN;
-          }
-          if (relres <= rtol) break;
-          int64_t step = pc_all ? 2 : 8;
-          if (pc_all && relres < last_relres && relres > 0.0) {
-            const double rate = log(last_relres / relres) / (double)(it - last_check);
-            const double remaining = log(relres / rtol) / rate;
-            step = std::max<int64_t>(2, std::min<int64_t>(12, (int64_t)(0.5 * remaining)));
-            step &= ~(int64_t)1;
-          }
-          last_check = it;
-          last_relres = relres;
-          next_check = it + step;
-        }
-        PHX_CHECK(phx_krylov_phase(s, 6));
-      }
-      if (bb == 0.0 || !(relres <= rtol)) break;
-      // the recurrences say converged: verify b - A y (one halo exchange, one SpMV, one all-reduce), restart from it
-      // should it miss the tolerance
-      PHX_CHECK(halo_exchange(s, c, H, V.y));
-      PHX_CHECK(phx_krylov_phase(s, 11));
-      PHX_CHECK(phx_krylov_phase(s, 12));
-      PHX_CHECK(allreduce_R(s, c, R_RR, R_RR + 1));
-      PHX_HIP(hipMemcpyAsync(s->scal_h, S, sizeof(double) * 16, hipMemcpyDeviceToHost, st));
-      PHX_CHECK(stream_sync_watchdog(st, "true-residual check of the distributed solve"));
-      spmvs += 1;
-      const double rr_true = s->scal_h[R_OFF + R_RR];
-      if (!(rr_true == rr_true)) { phx_set_error("non-finite true residual"); return PHX_ERR_BREAKDOWN; }
-      relres = sqrt(rr_true / bb);
-      if (relres <= rtol || ++verifications > 8 || it >= max_iter) break;
-      PHX_CHECK(phx_krylov_phase(s, 13));
-      last_relres = relres;
-      last_check = it;
-      next_check = it + 2;
-    }
-    PHX_CHECK(phx_krylov_finish(s, x_out, loc));
-    PHX_CHECK(phx_end_timing(m, 3));
-    double pavg = 0.0;
-    int pcount = 0;
-    PHX_CHECK(prof_collect(s, &pavg, &pcount));
-    if (stats) {
-      stats[0] = (double)it; stats[1] = relres; stats[2] = m->timings[3];
-      stats[3] = (double)spmvs; stats[4] = pavg; stats[5] = (double)pcount;
-      stats[6] = relres <= rtol ? 1.0 : 0.0; stats[7] = pc_all ? 1.0 : 0.0;
-    }
-    return PHX_OK;
+    // after the vote: the same on every rank (set up from all-reduced numbers)
+    const KrDist d{c, &H, overlap, s->precond_state == 1 && s->precond->dist, s->cc != nullptr && s->cc->dist, pc_all};
+    return kr_drive(s, &d, rtol, max_iter, x_out, loc, stats);
   };
-  rc = body();
+  const int rc = body();
   if (rc != PHX_ERR_TIMEOUT) {   // a wedged stream would block here for ever
     (void)hipStreamSynchronize(st);
     if (c->cs) (void)hipStreamSynchronize(c->cs);

@@ -1996,15 +1996,43 @@ static int launch_spmv_stored(phx_system *s, const double *x, double *y, int dot
   return det_fold(s, o0, dots == 3 ? o1 : nullptr, dots == 3 ? o2 : nullptr, nullptr, 1);
 }
 
-// phases: 0 begin (local (b,b) -> R_RHO), 1 begin2 (after all-reduce), 2 v = A p (+R_RV),
-// 3 s-update, 4 t = A s (+R_TS, R_TT), 5 x/r-update (+R_RHO, R_RR), 6 p-update + roll.
+// Phases of kr_phase.  The numbers are ABI (phx_krylov_phase; dist_solver.py names them alike).
+enum KrPhase {
+  KR_BEGIN = 0,            // preconditioner (re)build, local (b, b) -> R_RHO (+ the veto in mode 1)
+  KR_BEGIN2 = 1,           // after the all-reduce of R_RHO .. R_RR
+  KR_SPMV_P = 2,           // v = A phat (+R_RV)
+  KR_UPDATE_S = 3,         // s = r - alpha v
+  KR_SPMV_S = 4,           // t = A shat (+R_TS, R_TT)
+  KR_UPDATE_XR = 5,        // x, r update (+R_RHO, R_RR)
+  KR_UPDATE_P = 6,         // p update + roll
+  KR_PRECOND_P = 7,        // phat = P p (slab-exact: first half)
+  KR_PRECOND_S = 8,        // shat = P s (slab-exact: first half)
+  KR_EXACT_P = 9,          // slab-exact: second half of KR_PRECOND_P, after the all-gather of the carries
+  KR_EXACT_S = 10,         // ... of KR_PRECOND_S
+  KR_TRUE_SPMV = 11,       // t = A y (after the halo exchange of y)
+  KR_TRUE_RESIDUAL = 12,   // r = own ? b - t : 0, (r, r) -> R_RR
+  KR_RESTART = 13,         // restart of the recurrences from r
+  KR_SPMV_P_INNER = 20,    // KR_SPMV_P in two launches: the rows that read no halo entry ...
+  KR_SPMV_P_HALO = 21,     // ... and, once the halo is unpacked, the rows that do
+  KR_CC_RESTRICT_P = 30,   // coarse correction of a partitioned system: restrict p (the driver all-reduces)
+  KR_CC_ADD_P = 31,        // add the prolonged correction to phat
+  KR_CC_RESTRICT_S = 32,   // restrict s
+  KR_CC_ADD_S = 33,        // add the prolonged correction to shat
+  KR_SPMV_S_INNER = 40,    // KR_SPMV_S in two launches, as 20 / 21
+  KR_SPMV_S_HALO = 41,
+  KR_ID_SPMV_P = 52,       // identity loop: v = A phat on the stored rows
+  KR_ID_UPDATE_S = 53,     // s pass
+  KR_ID_SPMV_S = 54,       // t = A shat on the stored rows
+  KR_ID_UPDATE_XRP = 55,   // x / r / p pass (replaces 5 and 6)
+};
+
 // mode 1 (phase API, multi-GPU): every dot product is folded into R right after its producer so
 // the driver can all-reduce it; mode 0 (native loop): consumers fold the slots, `par` alternates.
 static int kr_phase(phx_system *s, int phase, int mode, int par) {
   phx_mesh *m = s->mesh;
   const int64_t n = s->n;
   hipStream_t st = m->stream;
-  if (phase == 0) {
+  if (phase == KR_BEGIN) {
     // (re)build the preconditioner for this system and ownership mask
     if (s->precond_state == 1 && s->precond->own_ptr != s->own) {
       phx_box_precond_destroy(s->precond);
@@ -2035,7 +2063,7 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
   const int32_t *rperm = s->structured ? nullptr : s->perm;
   const RestOut rop{rest_out ? V.phat : nullptr, rperm, s->nu}, ros{rest_out ? V.shat : nullptr, rperm, s->nu};
   switch (phase) {
-    case 0:
+    case KR_BEGIN:
       PHX_HIP(hipMemsetAsync(S, 0, sizeof(double) * PHX_SCAL_DOUBLES, st));
       {
         DotPart dp{nullptr, nullptr};
@@ -2047,25 +2075,25 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
       k_reduce_slots<<<1, 64, 0, st>>>(S, 0, R_RHO, 1, 1);
       if (mode) k_set_scalar<<<1, 1, 0, st>>>(S + R_OFF + R_RR, s->precond_veto ? 1.0 : 0.0);
       break;
-    case 1:
+    case KR_BEGIN2:
       k_kr_begin2<<<1, 1, 0, st>>>(S, mode);
       break;
-    case 2:
+    case KR_SPMV_P:
       PHX_CHECK(prof_begin(s));
       PHX_CHECK(launch_spmv(s, s->sell_val, V.phat, V.v, 1, V.rhat, slot_base(S, par, R_RV), nullptr));
       PHX_CHECK(prof_end(s));
       if (mode) k_reduce_slots<<<1, 64, 0, st>>>(S, par, R_RV, 1, 1);
       break;
-    case 3:
+    case KR_UPDATE_S:
       k_update_s<<<vec_grid(n), block, 0, st>>>(n, par, s->own, V.r, V.v, V.sv, S, ros);
       break;
-    case 4:
+    case KR_SPMV_S:
       PHX_CHECK(prof_begin(s));
       PHX_CHECK(launch_spmv(s, s->sell_val, V.shat, V.t, 2, V.sv, slot_base(S, par, R_TS), slot_base(S, par, R_TT)));
       PHX_CHECK(prof_end(s));
       if (mode) k_reduce_slots<<<1, 64, 0, st>>>(S, par, R_TS, 2, 1);
       break;
-    case 5:
+    case KR_UPDATE_XR:
       {
         DotPart dp{nullptr, nullptr};
         PHX_CHECK(det_part(s, vec_grid(n).x, &dp));
@@ -2074,50 +2102,45 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
       }
       if (mode) k_reduce_slots<<<1, 64, 0, st>>>(S, par, R_RHO, 2, 1);
       break;
-    case 6:
+    case KR_UPDATE_P:
       k_update_p<<<vec_grid(n), block, 0, st>>>(n, par, s->own, V.r, V.v, V.p, V.rhat, S, kr_drop2(s), rop);
       break;
-    case 7:  // phat = P p   (before the halo exchange of phat and phase 2)
+    case KR_PRECOND_P:
       if (s->precond_state == 1) PHX_CHECK(box_precond_apply(s, V.p, V.phat, s->precond->dist ? 1 : 0));
       else if (s->bj) { PHX_CHECK(blockjac_apply(s, s->bj, V.p, V.phat)); PHX_CHECK(coarse_apply_add(s, s->cc, V.p, V.phat)); }
       else if (s->u_unscaled && n > 0) k_jacobi_u<<<vec_grid(n), block, 0, st>>>(n, s->nu, s->perm, s->diag, V.p, V.phat);
       break;
-    case 8:  // shat = P s   (before the halo exchange of shat and phase 4)
+    case KR_PRECOND_S:
       if (s->precond_state == 1) PHX_CHECK(box_precond_apply(s, V.sv, V.shat, s->precond->dist ? 1 : 0));
       else if (s->bj) { PHX_CHECK(blockjac_apply(s, s->bj, V.sv, V.shat)); PHX_CHECK(coarse_apply_add(s, s->cc, V.sv, V.shat)); }
       else if (s->u_unscaled && n > 0) k_jacobi_u<<<vec_grid(n), block, 0, st>>>(n, s->nu, s->perm, s->diag, V.sv, V.shat);
       break;
-    // --- coarse correction of a partitioned elasticity system: 30 / 32 restrict p / s (the driver all-reduces the coarse
-    // vector), 31 / 33 add the prolonged correction to phat / shat
-    case 30: if (s->cc) PHX_CHECK(coarse_restrict(s, s->cc, V.p)); break;
-    case 31: if (s->cc) PHX_CHECK(coarse_apply_end(s, s->cc, V.phat)); break;
-    case 32: if (s->cc) PHX_CHECK(coarse_restrict(s, s->cc, V.sv)); break;
-    case 33: if (s->cc) PHX_CHECK(coarse_apply_end(s, s->cc, V.shat)); break;
-    // --- multi-GPU overlap: phases 2 / 4 in two launches (rows that read no halo entry | the rows that do)
-    case 20:
+    case KR_CC_RESTRICT_P: if (s->cc) PHX_CHECK(coarse_restrict(s, s->cc, V.p)); break;
+    case KR_CC_ADD_P: if (s->cc) PHX_CHECK(coarse_apply_end(s, s->cc, V.phat)); break;
+    case KR_CC_RESTRICT_S: if (s->cc) PHX_CHECK(coarse_restrict(s, s->cc, V.sv)); break;
+    case KR_CC_ADD_S: if (s->cc) PHX_CHECK(coarse_apply_end(s, s->cc, V.shat)); break;
+    case KR_SPMV_P_INNER:
       PHX_CHECK(prof_begin(s));
       PHX_CHECK(launch_spmv(s, s->sell_val, V.phat, V.v, 1, V.rhat, slot_base(S, par, R_RV), nullptr, 1));
       PHX_CHECK(prof_end(s));
       break;
-    case 21:
+    case KR_SPMV_P_HALO:
       PHX_CHECK(launch_spmv(s, s->sell_val, V.phat, V.v, 1, V.rhat, slot_base(S, par, R_RV), nullptr, 2));
       if (mode) k_reduce_slots<<<1, 64, 0, st>>>(S, par, R_RV, 1, 1);
       break;
-    case 40:
+    case KR_SPMV_S_INNER:
       PHX_CHECK(prof_begin(s));
       PHX_CHECK(launch_spmv(s, s->sell_val, V.shat, V.t, 2, V.sv, slot_base(S, par, R_TS), slot_base(S, par, R_TT), 1));
       PHX_CHECK(prof_end(s));
       break;
-    case 41:
+    case KR_SPMV_S_HALO:
       PHX_CHECK(launch_spmv(s, s->sell_val, V.shat, V.t, 2, V.sv, slot_base(S, par, R_TS), slot_base(S, par, R_TT), 2));
       if (mode) k_reduce_slots<<<1, 64, 0, st>>>(S, par, R_TS, 2, 1);
       break;
-    // --- verification of the TRUE residual (as phx_solve): 11: t = A y (the driver has exchanged the halo of y),
-    // 12: r = own ? b - t : 0 and (r, r) -> R[R_RR] (all-reduced by the driver), 13: restart of the recurrences from r
-    case 11:
+    case KR_TRUE_SPMV:
       PHX_CHECK(launch_spmv(s, s->sell_val, V.y, V.t, 0, nullptr, nullptr, nullptr));
       break;
-    case 12:
+    case KR_TRUE_RESIDUAL:
       if (n > 0) {
         DotPart dp{nullptr, nullptr};
         PHX_CHECK(det_part(s, vec_grid(n).x, &dp));
@@ -2126,17 +2149,23 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
       }
       k_reduce_slots<<<1, 64, 0, st>>>(S, 0, R_RR, 1, 1);
       break;
-    case 13:
-      k_restart_from_r<<<vec_grid(n), block, 0, st>>>(n, V.r, V.rhat, V.p, S, rop);
+    case KR_RESTART:
+      if (s->kr_ident_used) {   // (r, r) over the stencil rows = (rhat, A phat)_C of the next iteration, parity `par`
+        DotPart dp{nullptr, nullptr};
+        PHX_CHECK(det_part(s, vec_grid(n).x, &dp));
+        k_restart_from_r<<<vec_grid(n), block, 0, st>>>(n, V.r, V.rhat, V.p, S, rop, s->kr_cmask, par, dp);
+        PHX_CHECK(det_fold(s, slot_base(S, par, R_RV), nullptr));
+      } else {
+        k_restart_from_r<<<vec_grid(n), block, 0, st>>>(n, V.r, V.rhat, V.p, S, rop);
+      }
       break;
-    // --- identity loop (kr_identity; native loop only): 52 v = A phat on the stored rows, 53 s pass, 54 t = A shat on the
-    // stored rows, 55 x / r / p pass (replaces 5 and 6)
-    case 52:
+    // --- identity loop (kr_identity; native loop only)
+    case KR_ID_SPMV_P:
       PHX_CHECK(prof_begin(s));
       PHX_CHECK(launch_spmv_stored(s, V.phat, V.v, 1, V.rhat, nullptr, slot_base(S, par, I_RV), nullptr, nullptr));
       PHX_CHECK(prof_end(s));
       break;
-    case 53:
+    case KR_ID_UPDATE_S:
       {
         DotPart dp{nullptr, nullptr};
         PHX_CHECK(det_part(s, vec_grid(n).x, &dp));
@@ -2145,13 +2174,13 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
                            slot_base(S, par, I_RS_C)));
       }
       break;
-    case 54:
+    case KR_ID_SPMV_S:
       PHX_CHECK(prof_begin(s));
       PHX_CHECK(launch_spmv_stored(s, V.shat, V.t, 3, V.sv, V.rhat, slot_base(S, par, I_TS_B), slot_base(S, par, I_TT_B),
                                    slot_base(S, par, I_RT_B)));
       PHX_CHECK(prof_end(s));
       break;
-    case 55:
+    case KR_ID_UPDATE_XRP:
       {
         DotPart dp{nullptr, nullptr};
         PHX_CHECK(det_part(s, vec_grid(n).x, &dp));
@@ -2160,10 +2189,10 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
         PHX_CHECK(det_fold(s, slot_base(S, par, I_RR), slot_base(S, par ^ 1, I_RV), nullptr, nullptr, 1));
       }
       break;
-    case 9:   // slab-exact preconditioner: second half of phase 7, after the all-gather of the carries
+    case KR_EXACT_P:
       if (s->precond_state == 1 && s->precond->dist) PHX_CHECK(box_precond_apply(s, V.p, V.phat, 2));
       break;
-    case 10:  // ... of phase 8
+    case KR_EXACT_S:
       if (s->precond_state == 1 && s->precond->dist) PHX_CHECK(box_precond_apply(s, V.sv, V.shat, 2));
       break;
     default:
@@ -2288,46 +2317,85 @@ extern "C" int phx_precond_info(phx_system *s, double *out) {
   return PHX_OK;
 }
 
-extern "C" int phx_solve(phx_system *s, int method, double rtol, int64_t max_iter, double *x_out,
-                         int loc, double *stats) {
+#include "phx_dist.inc.hip"
+
+// The BiCGStab loop of phx_solve (d == nullptr: mode 0, the slot sets alternate with the parity of the iteration) and of
+// phx_solve_distributed (d: mode 1, one slot set; the halo of phat / shat / y is exchanged before each SpMV, or
+// overlapped with it, the dot products are all-reduced after their producers, the carries of the slab-exact
+// preconditioner all-gathered, the coarse vector all-reduced, and host waits are bounded by the watchdog).  The caller
+// has run phases 0 and 1 and read the head of the scalars ((b, b)) into scal_h; the driver runs everything from the
+// first iteration to phx_krylov_finish and stats.
+//
+// The host looks at the residual every 8th iteration with Jacobi (cheap iterations).  With the box preconditioner
+// (few, expensive iterations) a check drains the pipeline for ~30 us, so the next one is scheduled from the
+// observed convergence rate: half of the predicted remaining iterations ahead (at most 12, at least 2) -- near the
+// end every 2nd iteration, so no iteration is wasted on a late check (28 -> ~9 drains over 56 iterations).  In mode 1
+// every rank reads the same all-reduced numbers, so every rank schedules the same checks and takes the same branches.
+// Outer loop: when the recurrences report convergence, the TRUE residual b - A y is computed once (one SpMV) and,
+// should it not meet the tolerance -- after thousands of iterations the recursive residual drifts away from it
+// (3-D P2 systems, cond 1e8: observed 1e-5 instead of 1e-11) --, the iteration restarts from it.  The relres that
+// is returned, and stats[6], refer to the true residual.
+static int kr_drive(phx_system *s, const KrDist *d, double rtol, int64_t max_iter, double *x_out, int loc,
+                    double *stats) {
   phx_mesh *m = s->mesh;
-  PHX_HIP(hipSetDevice(m->device));
-  PHX_REQUIRE(method == PHX_BICGSTAB_JACOBI, PHX_ERR_NOT_IMPLEMENTED, "unknown method %d", method);
   hipStream_t st = m->stream;
+  const int mode = d ? 1 : 0;
   double *S = kr_scal(s);
-  PHX_CHECK(prof_reset(s));
-  PHX_CHECK(phx_begin_timing(m));
-  PHX_CHECK(kr_phase(s, 0, 0, 0));
-  // The host looks at the residual every 8th iteration with Jacobi (cheap iterations).  With the box preconditioner
-  // (few, expensive iterations) a check drains the pipeline for ~30 us, so the next one is scheduled from the
-  // observed convergence rate: half of the predicted remaining iterations ahead (at most 12, at least 2) -- near the
-  // end every 2nd iteration, so no iteration is wasted on a late check (28 -> ~9 drains over 56 iterations).
-  const bool pc = s->precond_state == 1;
-  const bool ident = s->kr_ident_used;   // decided by phase 0 (kr_identity)
-  PHX_CHECK(kr_phase(s, 1, 0, 0));
-  PHX_HIP(hipMemcpyAsync(s->scal_h, S, sizeof(double) * 16, hipMemcpyDeviceToHost, st));
-  PHX_HIP(hipStreamSynchronize(st));
+  const KrVecs V = kr_vecs(s);
+  const bool ident = s->kr_ident_used;   // decided by phase 0 (kr_identity; never in mode 1)
+  const bool pc = d ? d->pc_all : s->precond_state == 1;
   const double bb = s->scal_h[S_BB];
+  auto read_head = [&](const char *what) -> int {
+    PHX_HIP(hipMemcpyAsync(s->scal_h, S, sizeof(double) * 16, hipMemcpyDeviceToHost, st));
+    if (d) return stream_sync_watchdog(st, what);
+    PHX_HIP(hipStreamSynchronize(st));
+    return PHX_OK;
+  };
+  auto allreduce = [&](int lo, int hi) -> int { return d ? allreduce_R(s, d->c, lo, hi) : PHX_OK; };
+  // phat = P p / shat = P s
+  auto precond = [&](int ph, int ph_exact, int ph_restrict, int ph_add) -> int {
+    PHX_CHECK(kr_phase(s, ph, mode, 0));
+    if (d && d->exact) { PHX_CHECK(allgather_carries(s, d->c)); PHX_CHECK(kr_phase(s, ph_exact, mode, 0)); }
+    if (d && d->coarse) {
+      PHX_CHECK(kr_phase(s, ph_restrict, mode, 0));
+      PHX_CHECK(allreduce_sum(d->c, s->cc->gc, (size_t)s->cc->nc, st));
+      PHX_CHECK(kr_phase(s, ph_add, mode, 0));
+    }
+    return PHX_OK;
+  };
+  // v = A phat / t = A shat (ph), after the halo exchange of `in` or overlapped with it (ph_inner | ph_halo)
+  auto spmv = [&](int ph, int ph_inner, int ph_halo, double *in, int par) -> int {
+    if (d && d->overlap) {
+      PHX_CHECK(halo_begin(s, d->c, *d->H, in, true));
+      PHX_CHECK(kr_phase(s, ph_inner, mode, par));
+      PHX_CHECK(halo_end(s, d->c, *d->H, in, true));
+      return kr_phase(s, ph_halo, mode, par);
+    }
+    if (d) PHX_CHECK(halo_exchange(s, d->c, *d->H, in));
+    return kr_phase(s, ph, mode, par);
+  };
   int64_t it = 0, spmvs = 0, next_check = pc ? 2 : 8, last_check = 0;
   double relres = bb == 0.0 ? 0.0 : 1.0, last_relres = 1.0;
   int rc = PHX_OK;
-  // Outer loop: when the recurrences report convergence, the TRUE residual b - A y is computed once (one SpMV) and,
-  // should it not meet the tolerance -- after thousands of iterations the recursive residual drifts away from it
-  // (3-D P2 systems, cond 1e8: observed 1e-5 instead of 1e-11) --, the iteration restarts from it.  The relres that
-  // is returned, and stats[6], refer to the true residual.
   int verifications = 0;
   for (;;) {
     while (bb != 0.0 && it < max_iter) {
-      const int par = (int)(it & 1);
-      static const int seq[6] = {7, 2, 3, 8, 4, 5}, seq_ident[6] = {7, 52, 53, 8, 54, 55};
-      for (int ph : ident ? seq_ident : seq) PHX_CHECK(kr_phase(s, ph, 0, par));
+      const int par = d ? 0 : (int)(it & 1);
+      PHX_CHECK(precond(KR_PRECOND_P, KR_EXACT_P, KR_CC_RESTRICT_P, KR_CC_ADD_P));
+      PHX_CHECK(spmv(ident ? KR_ID_SPMV_P : KR_SPMV_P, KR_SPMV_P_INNER, KR_SPMV_P_HALO, V.phat, par));
+      PHX_CHECK(allreduce(R_RV, R_RV + 1));
+      PHX_CHECK(kr_phase(s, ident ? KR_ID_UPDATE_S : KR_UPDATE_S, mode, par));
+      PHX_CHECK(precond(KR_PRECOND_S, KR_EXACT_S, KR_CC_RESTRICT_S, KR_CC_ADD_S));
+      PHX_CHECK(spmv(ident ? KR_ID_SPMV_S : KR_SPMV_S, KR_SPMV_S_INNER, KR_SPMV_S_HALO, V.shat, par));
+      PHX_CHECK(allreduce(R_TS, R_TT + 1));
+      PHX_CHECK(kr_phase(s, ident ? KR_ID_UPDATE_XRP : KR_UPDATE_XR, mode, par));
+      PHX_CHECK(allreduce(R_RHO, R_RR + 1));
       spmvs += 2;
       ++it;
       if (it >= next_check || it == max_iter) {
-        // fold (r,r) and (rhat,r) of this iteration for the host, without clearing the slots
-        k_reduce_slots<<<1, 64, 0, st>>>(S, par, R_RHO, 2, 0);
-        PHX_HIP(hipMemcpyAsync(s->scal_h, S, sizeof(double) * 16, hipMemcpyDeviceToHost, st));
-        PHX_HIP(hipStreamSynchronize(st));
+        // mode 0: fold (r,r) and (rhat,r) of this iteration for the host, without clearing the slots
+        if (!d) k_reduce_slots<<<1, 64, 0, st>>>(S, par, R_RHO, 2, 0);
+        PHX_CHECK(read_head("convergence check of the distributed solve"));
         const double rr = s->scal_h[R_OFF + R_RR];
         const double omega = s->scal_h[S_OMEGA];
         relres = sqrt(rr / bb);
@@ -2349,39 +2417,22 @@ extern "C" int phx_solve(phx_system *s, int method, double rtol, int64_t max_ite
         last_relres = relres;
         next_check = it + step;
       }
-      if (!ident) PHX_CHECK(kr_phase(s, 6, 0, par));
+      if (!ident) PHX_CHECK(kr_phase(s, KR_UPDATE_P, mode, par));
     }
     if (rc != PHX_OK || bb == 0.0 || !(relres <= rtol)) break;
-    // verify
-    const KrVecs V = kr_vecs(s);
-    PHX_HIP(hipMemsetAsync(S + P_OFF, 0, sizeof(double) * (PHX_SCAL_DOUBLES - P_OFF), st));
-    PHX_CHECK(launch_spmv(s, s->sell_val, V.y, V.t, 0, nullptr, nullptr, nullptr));
-    {
-      DotPart dp{nullptr, nullptr};
-      PHX_CHECK(det_part(s, vec_grid(s->n).x, &dp));
-      k_true_residual<<<vec_grid(s->n), dim3(256), 0, st>>>(s->n, s->own, V.b, V.t, V.r, S, dp);
-      PHX_CHECK(det_fold(s, slot_base(S, 0, R_RR), nullptr));
-    }
-    k_reduce_slots<<<1, 64, 0, st>>>(S, 0, R_RR, 1, 1);
-    PHX_HIP(hipMemcpyAsync(s->scal_h, S, sizeof(double) * 16, hipMemcpyDeviceToHost, st));
-    PHX_HIP(hipStreamSynchronize(st));
+    // verify (mode 1: after one more halo exchange, with one more all-reduce)
+    if (d) PHX_CHECK(halo_exchange(s, d->c, *d->H, V.y));
+    else PHX_HIP(hipMemsetAsync(S + P_OFF, 0, sizeof(double) * (PHX_SCAL_DOUBLES - P_OFF), st));
+    PHX_CHECK(kr_phase(s, KR_TRUE_SPMV, mode, 0));
+    PHX_CHECK(kr_phase(s, KR_TRUE_RESIDUAL, mode, 0));
+    PHX_CHECK(allreduce(R_RR, R_RR + 1));
+    PHX_CHECK(read_head("true-residual check of the distributed solve"));
     spmvs += 1;
     const double rr_true = s->scal_h[R_OFF + R_RR];
     if (!(rr_true == rr_true)) { phx_set_error("non-finite true residual"); rc = PHX_ERR_BREAKDOWN; break; }
     relres = sqrt(rr_true / bb);
     if (relres <= rtol || ++verifications > 8 || it >= max_iter) break;
-    {
-      const bool rest_out = s->precond_state == 1 && V.phat != V.p;
-      const RestOut rop{rest_out ? V.phat : nullptr, s->structured ? nullptr : s->perm, s->nu};
-      if (ident) {   // (r, r) over the stencil rows = (rhat, A phat)_C of the next iteration, parity it & 1
-        DotPart dp{nullptr, nullptr};
-        PHX_CHECK(det_part(s, vec_grid(s->n).x, &dp));
-        k_restart_from_r<<<vec_grid(s->n), dim3(256), 0, st>>>(s->n, V.r, V.rhat, V.p, S, rop, s->kr_cmask, (int)(it & 1), dp);
-        PHX_CHECK(det_fold(s, slot_base(S, (int)(it & 1), R_RV), nullptr));
-      } else {
-        k_restart_from_r<<<vec_grid(s->n), dim3(256), 0, st>>>(s->n, V.r, V.rhat, V.p, S, rop);
-      }
-    }
+    PHX_CHECK(kr_phase(s, KR_RESTART, mode, d ? 0 : (int)(it & 1)));
     last_relres = relres;
     last_check = it;
     next_check = it + 2;   // (every slot is clear now: the parity the loop derives from `it` needs no care)
@@ -2400,12 +2451,25 @@ extern "C" int phx_solve(phx_system *s, int method, double rtol, int64_t max_ite
     stats[4] = pavg;
     stats[5] = (double)pcount;
     stats[6] = relres <= rtol ? 1.0 : 0.0;  // converged: the caller decides what an unconverged iterate is worth
-    stats[7] = s->scal_h[S_RESTARTS];
+    stats[7] = d ? (d->pc_all ? 1.0 : 0.0) : s->scal_h[S_RESTARTS];
   }
   return rc;
 }
 
-#include "phx_dist.inc.hip"
+extern "C" int phx_solve(phx_system *s, int method, double rtol, int64_t max_iter, double *x_out,
+                         int loc, double *stats) {
+  phx_mesh *m = s->mesh;
+  PHX_HIP(hipSetDevice(m->device));
+  PHX_REQUIRE(method == PHX_BICGSTAB_JACOBI, PHX_ERR_NOT_IMPLEMENTED, "unknown method %d", method);
+  hipStream_t st = m->stream;
+  PHX_CHECK(prof_reset(s));
+  PHX_CHECK(phx_begin_timing(m));
+  PHX_CHECK(kr_phase(s, KR_BEGIN, 0, 0));
+  PHX_CHECK(kr_phase(s, KR_BEGIN2, 0, 0));
+  PHX_HIP(hipMemcpyAsync(s->scal_h, kr_scal(s), sizeof(double) * 16, hipMemcpyDeviceToHost, st));
+  PHX_HIP(hipStreamSynchronize(st));
+  return kr_drive(s, nullptr, rtol, max_iter, x_out, loc, stats);
+}
 
 // y = A x in ORIGINAL active numbering (for tests and externally driven iterations)
 __global__ void k_scatter_perm(int64_t n, const int32_t *__restrict__ perm,

@@ -22,6 +22,11 @@ SCAL_DOUBLES = 16 + 2 * 8 * 64 * 8
 R_OFF = 8
 R_RV, R_TS, R_TT, R_RHO, R_RR = 0, 1, 2, 4, 5
 S_BB = 3
+# the phases of `phx_krylov_phase` this loop runs (named as KrPhase in phx_solve.hip)
+KR_BEGIN, KR_BEGIN2 = 0, 1
+KR_SPMV_P, KR_UPDATE_S, KR_SPMV_S, KR_UPDATE_XR, KR_UPDATE_P = 2, 3, 4, 5, 6
+KR_PRECOND_P, KR_PRECOND_S, KR_EXACT_P, KR_EXACT_S = 7, 8, 9, 10
+KR_TRUE_SPMV, KR_TRUE_RESIDUAL, KR_RESTART = 11, 12, 13
 
 
 class HipBackend:
@@ -256,9 +261,9 @@ class DistributedSolver:
             b.profile(True)
         b.synchronize()
         t0 = time.perf_counter()
-        b.phase(0)
+        b.phase(KR_BEGIN)
         self._allreduce(R_RHO, R_RR + 1)     # (b, b) and the preconditioner vetoes (phx_krylov_precond_disable)
-        b.phase(1)
+        b.phase(KR_BEGIN2)
         head = self.scal[:16].cpu()
         bb = float(head[S_BB])
         it, relres = 0, (0.0 if bb == 0.0 else 1.0)
@@ -282,23 +287,23 @@ class DistributedSolver:
         while True:
             while bb != 0.0 and it < self.max_iter:
                 if hat:
-                    b.phase(7)
+                    b.phase(KR_PRECOND_P)
                     if exact:
                         self._allgather_carries()
-                        b.phase(9)
+                        b.phase(KR_EXACT_P)
                 self.halo_exchange(vp)
-                b.phase(2)
+                b.phase(KR_SPMV_P)
                 self._allreduce(R_RV, R_RV + 1)
-                b.phase(3)
+                b.phase(KR_UPDATE_S)
                 if hat:
-                    b.phase(8)
+                    b.phase(KR_PRECOND_S)
                     if exact:
                         self._allgather_carries()
-                        b.phase(10)
+                        b.phase(KR_EXACT_S)
                 self.halo_exchange(vs)
-                b.phase(4)
+                b.phase(KR_SPMV_S)
                 self._allreduce(R_TS, R_TT + 1)
-                b.phase(5)
+                b.phase(KR_UPDATE_XR)
                 self._allreduce(R_RHO, R_RR + 1)
                 it += 1
                 if it >= next_check or it == self.max_iter:
@@ -314,13 +319,13 @@ class DistributedSolver:
                         remaining = math.log(relres / self.rtol) / rate
                         step = max(2, min(12, int(0.5 * remaining))) & ~1
                     last_check, last_relres, next_check = it, relres, it + step
-                b.phase(6)
+                b.phase(KR_UPDATE_P)
             if bb == 0.0 or not relres <= self.rtol:
                 break
             # the recurrences say converged: verify the TRUE residual b - A y, restart from it should it miss rtol
             self.halo_exchange(vy)
-            b.phase(11)
-            b.phase(12)
+            b.phase(KR_TRUE_SPMV)
+            b.phase(KR_TRUE_RESIDUAL)
             self._allreduce(R_RR, R_RR + 1)
             rr = float(self.scal[R_OFF + R_RR].item())
             if not np.isfinite(rr):
@@ -329,7 +334,7 @@ class DistributedSolver:
             verifications += 1
             if relres <= self.rtol or verifications > 8 or it >= self.max_iter:
                 break
-            b.phase(13)
+            b.phase(KR_RESTART)
             last_check, last_relres, next_check = it, relres, it + 2
         b.finish(out)
         b.synchronize()

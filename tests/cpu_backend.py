@@ -10,6 +10,8 @@ import torch
 
 from oracle import assembly as OA, meshgen, tagging as OT
 from oracle.topology import Topology
+from phifem_amd.dist_solver import (KR_BEGIN, KR_BEGIN2, KR_RESTART, KR_SPMV_P, KR_SPMV_S, KR_TRUE_RESIDUAL,
+                                    KR_TRUE_SPMV, KR_UPDATE_P, KR_UPDATE_S, KR_UPDATE_XR)
 
 R_OFF = 8
 S_RHO, S_ALPHA, S_OMEGA, S_BB, S_RR = 0, 1, 2, 3, 4
@@ -71,7 +73,7 @@ class CpuBackend:
 
     def phase(self, k):
         S, own = self.S, self.own
-        if k == 0:
+        if k == KR_BEGIN:
             S[:16] = 0.0
             bi = np.where(own, self.rhs, 0.0)
             for vec in (self.bv, self.r, self.rhat, self.p):
@@ -79,27 +81,27 @@ class CpuBackend:
             self.y[:] = 0.0
             S[R_OFF + R_RHO] = bi @ bi
             S[R_OFF + R_RR] = 1.0   # veto: this stand-in has no box preconditioner (phx_krylov_precond_disable)
-        elif k == 1:
+        elif k == KR_BEGIN2:
             S[S_RHO] = S[S_BB] = S[S_RR] = S[R_OFF + R_RHO]
-        elif k == 2:
+        elif k == KR_SPMV_P:
             self.v[:] = np.where(own, self.As @ self.p, 0.0)
             S[R_OFF + R_RV] = self.v @ self.rhat
-        elif k == 3:
+        elif k == KR_UPDATE_S:
             alpha = S[S_RHO] / S[R_OFF + R_RV]
             self.s[:] = np.where(own, self.r - alpha * self.v, 0.0)
             S[S_ALPHA] = alpha
-        elif k == 4:
+        elif k == KR_SPMV_S:
             self.t[:] = np.where(own, self.As @ self.s, 0.0)
             S[R_OFF + R_TS] = self.t @ self.s
             S[R_OFF + R_TT] = self.t @ self.t
-        elif k == 5:
+        elif k == KR_UPDATE_XR:
             alpha, omega = S[S_ALPHA], S[R_OFF + R_TS] / S[R_OFF + R_TT]
             self.y[own] += alpha * self.p[own] + omega * self.s[own]
             self.r[:] = np.where(own, self.s - omega * self.t, 0.0)
             S[R_OFF + R_RHO] = self.rhat @ self.r
             S[R_OFF + R_RR] = self.r @ self.r
             S[S_OMEGA] = omega
-        elif k == 6:
+        elif k == KR_UPDATE_P:
             with np.errstate(all="ignore"):
                 beta = (S[R_OFF + R_RHO] / S[S_RHO]) * (S[S_ALPHA] / S[S_OMEGA])
             restart = not (abs(beta) <= 1e300) or not (abs(S[R_OFF + R_RHO]) > 1e-14 * S[R_OFF + R_RR])
@@ -111,12 +113,12 @@ class CpuBackend:
                 self.p[:] = np.where(own, self.r + beta * (self.p - S[S_OMEGA] * self.v), 0.0)
                 S[S_RHO] = S[R_OFF + R_RHO]
             S[S_RR] = S[R_OFF + R_RR]
-        elif k == 11:   # true-residual verification: t = A y
+        elif k == KR_TRUE_SPMV:   # true-residual verification: t = A y
             self.t[:] = np.where(own, self.As @ self.y, 0.0)
-        elif k == 12:   # r = b - t, (r, r)
+        elif k == KR_TRUE_RESIDUAL:   # r = b - t, (r, r)
             self.r[:] = np.where(own, self.bv - self.t, 0.0)
             S[R_OFF + R_RR] = self.r @ self.r
-        elif k == 13:   # restart from r (k_restart_from_r)
+        elif k == KR_RESTART:   # restart from r (k_restart_from_r)
             self.p[:] = self.r
             self.rhat[:] = self.r
             S[S_RHO] = S[S_RR] = S[R_OFF + R_RR]
