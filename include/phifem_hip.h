@@ -213,6 +213,12 @@ enum phx_option {
                                plane on (default 32768: three planes of the vector no longer fit an XCD's L2 next to the
                                streams) the stencil blocks of the SpMV walk the k-th eighth of EVERY plane on XCD k
                                instead of the k-th eighth of all rows; 0: never.  Placement only: same product   */
+  PHX_OPT_P2_COARSE = 12, /* two-level preconditioner of P2 weak-Dirichlet systems on generated Kuhn boxes (one rank):
+                               the additive Galerkin correction R Ac^-1 R^T (multilinear functions of spacing H = value * h,
+                               one set per field, Ac = R^T A R probed through the solver's own operator) on top of the
+                               h/2-lattice sine transform on u and Jacobi on p.  0 (default): off; -1: automatic (ratio
+                               and on/off chosen by the library); >= 5: this ratio; 1..4: PHX_ERR_VALUE.
+                               Built on the first solve of a system; phx_coarse_info reports it            */
   PHX_OPT_ALLOW_EMPTY = 6, /* 1: phx_assemble_poisson_wd returns an EMPTY system (n_active = 0) when no cell
                                is tagged 1 / 2 instead of PHX_ERR_VALUE: a slab of a partitioned box that
                                does not touch the domain still joins every collective of the solve          */
@@ -387,10 +393,22 @@ int phx_precond_dist_info(const phx_system *s, int64_t *out4);
  * every rank before the first iteration: Jacobi everywhere, same vectors exchanged, same check cadence. */
 int phx_krylov_precond_disable(phx_system *s);
 /* After a solve: out[8] = {preconditioner (0: Jacobi, 1: lattice solve, 2: vertex-block Jacobi of the
- * elasticity system), transform lengths L0, L1, L2, lattice points of
+ * elasticity system, 3: 2 with the coarse correction, 4: 1 with the P2 coarse correction), transform lengths L0, L1, L2, lattice points of
  * the box, sampled average seconds of one y-pass launch of the sine transforms (PHX_OPT_PROFILE_SPMV),
  * launches sampled, bytes per lattice value (4: f32 transforms, 8: f64)}. */
 int phx_precond_info(phx_system *s, double *out);
+/* After a solve, the coarse-space correction of the system (P2: PHX_OPT_P2_COARSE; elasticity: PHX_OPT_EL_COARSE):
+ * out[6] = {ratio H / h, coarse DoFs of the first field (P2: u; elasticity: all), coarse DoFs of the second field (P2: p;
+ * elasticity: 0), build seconds, operator products of the probing, bytes the dense apply streams (nc^2 * 8)}.  No
+ * correction: out[1] = out[2] = 0, and out[0] = -reason when one was asked for and could not be built (1: not a single-rank
+ * generated box with the lattice preconditioner, 2: box smaller than 2 H, 3: more coarse DoFs than the dense inverse takes
+ * (20000), 4: singular coarse matrix, 5: the check |Ac Ac^-1 v - v| failed, 6: automatic choice: the correction does not pay at
+ * this box size). */
+int phx_coarse_info(phx_system *s, double *out);
+/* Test aid: node_of[nc] = field * M + node of each compact coarse DoF (M = m0 m1 m2 coarse nodes per field, node =
+ * i + m0 (j + m1 k), node (i, j, k) at the lattice point (i, j, k) * H) and ainv[nc * nc] = Ac^-1, row-major.  Either
+ * pointer may be null.  PHX_ERR_VALUE when the system has no coarse correction. */
+int phx_coarse_export(phx_system *s, int32_t *node_of, double *ainv);
 /* After phx_solve: *on = 1 when the solve ran the identity loop (structured P1 system with the f64 lattice
  * preconditioner: SpMVs over the stored rows only, A K_box^-1 = I on the stencil rows), 0 for the standard loop.
  * PHX_KR_IDENTITY=0 in the environment forces the standard loop. */

@@ -28,7 +28,8 @@ CELL_TYPES = {"triangle": TRIANGLE, "quadrilateral": QUADRILATERAL, "tetrahedron
 CELL_NAMES = {v: k for k, v in CELL_TYPES.items()}
 PHI_NODAL_P1, PHI_POINTS, PHI_QUADRIC = 0, 1, 2
 (OPT_PROFILE_SPMV, OPT_HAS_EXTERIOR, OPT_SPMV_XCD_GROUP, OPT_SPMV_VALUE_INDEX, OPT_PRECOND, OPT_ALLOW_EMPTY,
- OPT_EXPORT_CSR, OPT_STRUCTURED, OPT_DETERMINISTIC, OPT_EL_COARSE, OPT_STENCIL_PLANE_ROWS) = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11)
+ OPT_EXPORT_CSR, OPT_STRUCTURED, OPT_DETERMINISTIC, OPT_EL_COARSE, OPT_STENCIL_PLANE_ROWS, OPT_P2_COARSE) = (
+    1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12)
 (ARR_COORDS, ARR_CELLS, ARR_C2F, ARR_F2C, ARR_CELL_TAGS, ARR_FACET_TAGS, ARR_BFACETS, ARR_C2E,
  ARR_EDGES) = range(9)
 
@@ -72,6 +73,8 @@ SIGNATURES = {
     "phx_krylov_precond_active": ([_vp, _pi], _i),
     "phx_krylov_precond_disable": ([_vp], _i),
     "phx_precond_info": ([_vp, _pd], _i),
+    "phx_coarse_info": ([_vp, _pd], _i),
+    "phx_coarse_export": ([_vp, _vp, _vp], _i),
     "phx_precond_local_bbox": ([_vp, _pi64], _i),
     "phx_precond_setup_global": ([_vp, _pi64, _i, _i, _pi64, _pi64], _i),
     "phx_precond_set_carry_buffers": ([_vp, _vp, _vp], _i),

@@ -18,6 +18,7 @@
 // Partitioned boxes (native RCCL loop, phx_dist.inc.hip): the coarse lattice is the one of the GLOBAL box; every rank
 // restricts its owned rows, the coarse right-hand side is all-reduced (a few thousand doubles per application), every
 // rank holds Ac^-1 (its own rows' share of Ac summed over the ranks once per system) and prolongs onto its owned rows.
+#include <chrono>
 #include <functional>
 
 struct phx_coarse {
@@ -35,12 +36,24 @@ struct phx_coarse {
   double *Ainv = nullptr;      // [nc * nc] row-major Ac^-1
   double *X1 = nullptr, *X2 = nullptr, *X3 = nullptr;   // line-restricted arrays ([blk][k][j][ci], [blk][k][cj][ci], [blk][ck][cj][ci])
   double *gc = nullptr, *zc = nullptr;                  // [nc]
+  int ratio_h = 0;             // H / h (elasticity: = ratio; P2: ratio counts h/2-lattice steps, = 2 ratio_h)
+  int nc_blk[2] = {0, 0};      // compact coarse DoFs of block 0 and of the other blocks (P2: u, p)
+  double build_s = 0.0;        // seconds of the build (probing, inverse, check)
+  int64_t probes = 0;          // operator products (or probing passes over the CSR copy) of the build
+  // P2 weak Dirichlet (PHX_OPT_P2_COARSE): the fine points are the h/2 lattice (F = 2 n + 1 per axis), the blocks are
+  // the fields u and p, and the active rows are kept per lattice LINE (field, K, J) instead of a position per lattice
+  // point (2 x 1.08e9 points at 512^3): entries lptr[line] .. lptr[line + 1] - 1, x index ascending
+  bool p2 = false;
+  int64_t *lptr = nullptr;     // [2 F1 F2 + 1]
+  uint16_t *lx = nullptr;      // [n] lattice x index of the entry
+  int32_t *lpos = nullptr;     // [n] solver position of the entry
 };
 
 static void coarse_free(phx_coarse *c) {
   if (!c) return;
   (void)phx_free(c->cpos); (void)phx_free(c->dpos); (void)phx_free(c->cmap); (void)phx_free(c->node_of); (void)phx_free(c->Ainv);
   (void)phx_free(c->X1); (void)phx_free(c->X2); (void)phx_free(c->X3); (void)phx_free(c->gc); (void)phx_free(c->zc);
+  (void)phx_free(c->lptr); (void)phx_free(c->lx); (void)phx_free(c->lpos);
   delete c;
 }
 void phx_coarse_destroy(phx_coarse *c) { coarse_free(c); }
@@ -353,6 +366,208 @@ __global__ void __launch_bounds__(256) k_cc_gemv(int nc, const double *__restric
   if (lane == 0) y[row] = acc;
 }
 
+// ---- P2 weak Dirichlet (PHX_OPT_P2_COARSE): the same passes over the h/2 lattice ---------------------------------
+// Fine index space: the active rows of the two fields, each at its point of the h/2 lattice (p2_lattice_point), kept
+// per lattice line (field, K, J) -- see phx_coarse::lptr.  The coarse lattice counts lattice steps: g.ratio = 2 H / h,
+// so node c sits at the lattice point c g.ratio and the hat weights are t = i / g.ratio as for the vertex lattice.
+struct P2cGeo {
+  int64_t nent, nv, n0, n1;   // entities per field, vertices, vertices per x / y line of the box
+  int64_t F1, F2;             // lattice points per y / z axis
+  const int32_t *edges;
+};
+__device__ __forceinline__ void p2c_line_of(int64_t full, const P2cGeo &q, int64_t *line, int *I) {
+  const int64_t f = full / q.nent;
+  int p[3];
+  p2_lattice_point(full - f * q.nent, q.nv, q.n0, q.n1, q.edges, p);
+  *line = (f * q.F2 + p[2]) * q.F1 + p[1];
+  *I = p[0];
+}
+__global__ void k_p2c_count(int64_t n, P2cGeo q, const int64_t *__restrict__ full, int32_t *__restrict__ cnt) {
+  const int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  int64_t line;
+  int I;
+  p2c_line_of(full[r], q, &line, &I);
+  atomicAdd(&cnt[line], 1);
+}
+// entries of a line in arrival order (k_p2c_sort puts them in x order: the lists do not depend on the atomics)
+__global__ void k_p2c_fill(int64_t n, P2cGeo q, const int64_t *__restrict__ full, const int32_t *__restrict__ iperm,
+                           const int64_t *__restrict__ lptr, int32_t *__restrict__ cur, uint16_t *__restrict__ lx,
+                           int32_t *__restrict__ lpos) {
+  const int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  int64_t line;
+  int I;
+  p2c_line_of(full[r], q, &line, &I);
+  const int64_t at = lptr[line] + atomicAdd(&cur[line], 1);
+  lx[at] = (uint16_t)I;
+  lpos[at] = iperm[r];
+}
+// one wavefront per line: the entries through a dense LDS row of the line, then compacted in x order with ballots
+__global__ void __launch_bounds__(256)
+k_p2c_sort(int64_t nlines, int F0, const int64_t *__restrict__ lptr, uint16_t *__restrict__ lx, int32_t *__restrict__ lpos) {
+  extern __shared__ int32_t p2c_row[];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t line = blockIdx.x * (int64_t)(blockDim.x >> 6) + w;
+  if (line >= nlines) return;
+  const int64_t b = lptr[line], e = lptr[line + 1];
+  if (e == b) return;
+  int32_t *t = p2c_row + (int64_t)w * F0;
+  for (int i = lane; i < F0; i += 64) t[i] = -1;
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  for (int64_t k = b + lane; k < e; k += 64) t[lx[k]] = lpos[k];
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  int64_t o = b;
+  for (int i0 = 0; i0 < F0; i0 += 64) {
+    const int i = i0 + lane;
+    const int32_t p = i < F0 ? t[i] : -1;
+    const unsigned long long mk = __ballot(p >= 0);
+    if (p >= 0) {
+      const int64_t at = o + __popcll(mk & ((1ull << lane) - 1ull));
+      lx[at] = (uint16_t)i;
+      lpos[at] = p;
+    }
+    o += __popcll(mk);
+  }
+}
+// column scaling of the operator the Krylov loop iterates on, by solver position: x = y / dpos
+__global__ void k_p2c_dpos(int64_t n, int64_t nu, bool u_unscaled, const int32_t *__restrict__ perm,
+                           const double *__restrict__ diag, double *__restrict__ dpos) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t r = perm[i];
+  dpos[i] = u_unscaled && r < nu ? 1.0 : diag[r];
+}
+__device__ __forceinline__ void p2c_line_ijk(int64_t line, const CcDims &g, int *blk, int *J, int *K) {
+  *J = (int)(line % g.nf[1]);
+  *K = (int)((line / g.nf[1]) % g.nf[2]);
+  *blk = (int)(line / (g.nf[1] * g.nf[2]));
+}
+// one wavefront per line
+__global__ void __launch_bounds__(256)
+k_p2c_used(int64_t nlines, CcDims g, const int64_t *__restrict__ lptr, const uint16_t *__restrict__ lx, uint8_t *__restrict__ used) {
+  const int lane = threadIdx.x & 63;
+  const int64_t line = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
+  if (line >= nlines) return;
+  int blk, J, K;
+  p2c_line_ijk(line, g, &blk, &J, &K);
+  int c[3][2];
+  double w[3][2];
+  cc_axis(J, g.ratio, g.m[1], c[1], w[1]);
+  cc_axis(K, g.ratio, g.m[2], c[2], w[2]);
+  for (int64_t k = lptr[line] + lane; k < lptr[line + 1]; k += 64) {
+    cc_axis(lx[k], g.ratio, g.m[0], c[0], w[0]);
+    for (int q = 0; q < 8; ++q) {
+      const double ww = w[0][q & 1] * w[1][(q >> 1) & 1] * w[2][q >> 2];
+      if (ww > 0.0) used[blk * g.M + c[0][q & 1] + (int64_t)g.m[0] * (c[1][(q >> 1) & 1] + (int64_t)g.m[1] * c[2][q >> 2])] = 1;
+    }
+  }
+}
+// probing vector of (field, colour) on the lines [line0, line0 + nlines): D R e, as k_cc_probe
+__global__ void __launch_bounds__(256)
+k_p2c_probe(int64_t nlines, int64_t line0, int col3, CcDims g, const int64_t *__restrict__ lptr, const uint16_t *__restrict__ lx,
+            const int32_t *__restrict__ lpos, const double *__restrict__ dpos, double *__restrict__ wvec) {
+  const int lane = threadIdx.x & 63;
+  const int64_t line = line0 + ((blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6);
+  if (line >= line0 + nlines) return;
+  int blk, ijk[3];
+  p2c_line_ijk(line, g, &blk, &ijk[1], &ijk[2]);
+  const int cc[3] = {col3 % 3, (col3 / 3) % 3, col3 / 9};
+  double s[3];
+  for (int a = 1; a < 3; ++a) {
+    int c[2];
+    double w[2];
+    cc_axis(ijk[a], g.ratio, g.m[a], c, w);
+    s[a] = (c[0] % 3 == cc[a] ? w[0] : 0.0) + ((c[1] != c[0] && c[1] % 3 == cc[a]) ? w[1] : 0.0);
+  }
+  if (s[1] * s[2] == 0.0) return;   // wvec is zero there already
+  for (int64_t k = lptr[line] + lane; k < lptr[line + 1]; k += 64) {
+    int c[2];
+    double w[2];
+    cc_axis(lx[k], g.ratio, g.m[0], c, w);
+    const double s0 = (c[0] % 3 == cc[0] ? w[0] : 0.0) + ((c[1] != c[0] && c[1] % 3 == cc[0]) ? w[1] : 0.0);
+    const int32_t pos = lpos[k];
+    wvec[pos] = dpos[pos] * s0 * s[1] * s[2];
+  }
+}
+// first pass of R^T, as k_cc_restrict_x: the line's values go to a dense LDS row (zeros where no row is active)
+template <bool SPLIT>
+__global__ void __launch_bounds__(256)
+k_p2c_restrict_x(int64_t nlines, CcDims g, int colour, const int64_t *__restrict__ lptr, const uint16_t *__restrict__ lx,
+                 const int32_t *__restrict__ lpos, const double *__restrict__ vin, double *__restrict__ X1) {
+  extern __shared__ double cc_xs[];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t line = blockIdx.x * (int64_t)(blockDim.x >> 6) + w;
+  if (line >= nlines) return;
+  const int nf0 = (int)g.nf[0];
+  const int64_t b = lptr[line], e = lptr[line + 1];
+  if (b == e) {
+    for (int ci = lane; ci < g.m[0]; ci += 64) {
+      if (SPLIT) { X1[2 * (line * g.m[0] + ci)] = 0.0; X1[2 * (line * g.m[0] + ci) + 1] = 0.0; }
+      else X1[line * g.m[0] + ci] = 0.0;
+    }
+    return;
+  }
+  double *xs = cc_xs + (int64_t)w * nf0;
+  for (int i = lane; i < nf0; i += 64) xs[i] = 0.0;
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  for (int64_t k = b + lane; k < e; k += 64) xs[lx[k]] = vin[lpos[k]];
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  const double inv_h = 1.0 / (double)g.ratio;
+  for (int ci = lane; ci < g.m[0]; ci += 64) {
+    const int centre = ci * g.ratio;
+    const int lo = centre - g.ratio + 1 > 0 ? centre - g.ratio + 1 : 0;
+    const int hi = centre + g.ratio - 1 < nf0 - 1 ? centre + g.ratio - 1 : nf0 - 1;
+    double acc[2] = {0.0, 0.0};
+    for (int i = lo; i <= hi; ++i) {
+      const double wt = 1.0 - fabs((double)(i - centre)) * inv_h;
+      acc[SPLIT ? cc_part(i, ci, colour, g.ratio) : 0] += wt * xs[i];
+    }
+    if (SPLIT) { X1[2 * (line * g.m[0] + ci)] = acc[0]; X1[2 * (line * g.m[0] + ci) + 1] = acc[1]; }
+    else X1[line * g.m[0] + ci] = acc[0];
+  }
+}
+// last pass of R, fused with the scaling and the sum: vout[pos] += D[pos] * sum_{two ci} w X1[line][ci]; one wavefront per line
+__global__ void __launch_bounds__(256)
+k_p2c_prolong_x_add(int64_t nlines, CcDims g, const int64_t *__restrict__ lptr, const uint16_t *__restrict__ lx,
+                    const int32_t *__restrict__ lpos, const double *__restrict__ dpos, const double *__restrict__ X1,
+                    double *__restrict__ vout) {
+  const int lane = threadIdx.x & 63;
+  const int64_t line = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
+  if (line >= nlines) return;
+  const double *x1 = X1 + line * g.m[0];
+  for (int64_t k = lptr[line] + lane; k < lptr[line + 1]; k += 64) {
+    int c[2];
+    double w[2];
+    cc_axis(lx[k], g.ratio, g.m[0], c, w);
+    const int32_t p = lpos[k];
+    vout[p] += dpos[p] * (w[0] * x1[c[0]] + w[1] * x1[c[1]]);
+  }
+}
+
+// zc = Ainv gc for the P2 correction: one wavefront per row, four independent partial sums per lane (four loads in
+// flight instead of one dependent chain), combined in a fixed order
+__global__ void __launch_bounds__(256) k_p2c_gemv(int nc, const double *__restrict__ Ainv, const double *__restrict__ x, double *__restrict__ y) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (row >= nc) return;
+  const double *a = Ainv + (int64_t)row * nc;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  int j = lane;
+  for (; j + 192 < nc; j += 256) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[u] = __builtin_fma(__builtin_nontemporal_load(a + j + 64 * u), x[j + 64 * u], acc[u]);
+  }
+  for (int u = 0; j < nc; j += 64, ++u) acc[u] = __builtin_fma(a[j], x[j], acc[u]);
+  double t = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+  if (lane == 0) y[row] = t;
+}
+
 static inline dim3 cc_grid(int64_t n) { return dim3((unsigned)phx_div_up(std::max<int64_t>(n, 1), 256)); }
 
 // gc = R^T vin (compact coarse vector)
@@ -362,7 +577,8 @@ static int coarse_restrict(phx_system *s, phx_coarse *c, const double *vin) {
   const CcDims g{{c->nf[0], c->nf[1], c->nf[2]}, {c->m[0], c->m[1], c->m[2]}, c->ratio, c->M, {c->off[0], c->off[1], c->off[2]}};
   const int64_t nb = c->nblk_u;
   const int64_t nl = nb * c->nf[2] * c->nf[1];
-  k_cc_restrict_x<false, false><<<dim3((unsigned)phx_div_up(nl, 4)), dim3(256), sizeof(double) * 4 * (size_t)c->nf[0], st>>>(nl, g, 0, c->cpos, vin, c->X1);
+  if (c->p2) k_p2c_restrict_x<false><<<dim3((unsigned)phx_div_up(nl, 4)), dim3(256), sizeof(double) * 4 * (size_t)c->nf[0], st>>>(nl, g, 0, c->lptr, c->lx, c->lpos, vin, c->X1);
+  else k_cc_restrict_x<false, false><<<dim3((unsigned)phx_div_up(nl, 4)), dim3(256), sizeof(double) * 4 * (size_t)c->nf[0], st>>>(nl, g, 0, c->cpos, vin, c->X1);
   const int64_t t2 = nb * c->nf[2] * c->m[1] * c->m[0];
   k_cc_restrict_axis<<<cc_grid(t2), dim3(256), 0, st>>>(t2, c->m[0], c->nf[1], c->m[1], c->ratio, c->off[1], c->X1, c->X2);
   const int64_t t3 = nb * c->M;
@@ -379,7 +595,8 @@ static int coarse_restrict_split(phx_system *s, phx_coarse *c, int col3, const d
   const CcDims g{{c->nf[0], c->nf[1], c->nf[2]}, {c->m[0], c->m[1], c->m[2]}, c->ratio, c->M, {c->off[0], c->off[1], c->off[2]}};
   const int64_t nb = c->nblk_u;
   const int64_t nl = nb * c->nf[2] * c->nf[1];
-  if (direct) k_cc_restrict_x<true, true><<<dim3((unsigned)phx_div_up(nl, 4)), dim3(256), sizeof(double) * 4 * (size_t)c->nf[0], st>>>(nl, g, col3 % 3, c->cpos, vin, X1s);
+  if (c->p2) k_p2c_restrict_x<true><<<dim3((unsigned)phx_div_up(nl, 4)), dim3(256), sizeof(double) * 4 * (size_t)c->nf[0], st>>>(nl, g, col3 % 3, c->lptr, c->lx, c->lpos, vin, X1s);
+  else if (direct) k_cc_restrict_x<true, true><<<dim3((unsigned)phx_div_up(nl, 4)), dim3(256), sizeof(double) * 4 * (size_t)c->nf[0], st>>>(nl, g, col3 % 3, c->cpos, vin, X1s);
   else k_cc_restrict_x<true, false><<<dim3((unsigned)phx_div_up(nl, 4)), dim3(256), sizeof(double) * 4 * (size_t)c->nf[0], st>>>(nl, g, col3 % 3, c->cpos, vin, X1s);
   const int64_t t2 = nb * c->nf[2] * c->m[1] * c->m[0] * 2;
   k_cc_restrict_axis_split<<<cc_grid(t2), dim3(256), 0, st>>>(t2, (int64_t)c->m[0] * 2, c->nf[1], c->m[1], c->ratio, c->off[1], (col3 / 3) % 3, X1s, X2s);
@@ -389,12 +606,9 @@ static int coarse_restrict_split(phx_system *s, phx_coarse *c, int col3, const d
   return PHX_OK;
 }
 
-// vout += D R zc,  zc = Ac^-1 gc  (gc: the restricted vector, all-reduced by the driver on a partitioned box)
-static int coarse_apply_end(phx_system *s, phx_coarse *c, double *vout) {
-  if (!c || c->nc == 0) return PHX_OK;
+// vout += D R zc
+static int coarse_prolong_add(phx_system *s, phx_coarse *c, double *vout) {
   hipStream_t st = s->mesh->stream;
-  if (s->n == 0) return PHX_OK;   // a slab outside the domain: nothing to prolong onto
-  k_cc_gemv<<<dim3((unsigned)phx_div_up(c->nc, 4)), dim3(256), 0, st>>>(c->nc, c->Ainv, c->gc, c->zc);
   const CcDims g{{c->nf[0], c->nf[1], c->nf[2]}, {c->m[0], c->m[1], c->m[2]}, c->ratio, c->M, {c->off[0], c->off[1], c->off[2]}};
   const int64_t nb = c->nblk_u;
   const int64_t t3 = nb * c->M;
@@ -403,10 +617,24 @@ static int coarse_apply_end(phx_system *s, phx_coarse *c, double *vout) {
   k_cc_prolong_axis<<<cc_grid(t2), dim3(256), 0, st>>>(t2, (int64_t)c->m[0] * c->m[1], c->nf[2], c->m[2], c->ratio, c->off[2], c->X3, c->X2);
   const int64_t t1 = nb * c->nf[2] * c->nf[1] * c->m[0];
   k_cc_prolong_axis<<<cc_grid(t1), dim3(256), 0, st>>>(t1, c->m[0], c->nf[1], c->m[1], c->ratio, c->off[1], c->X2, c->X1);
-  const int64_t tf = nb * s->mesh->nv;
-  k_cc_prolong_x_add<<<cc_grid(tf), dim3(256), 0, st>>>(tf, g, c->cpos, c->dpos, c->X1, vout);
+  if (c->p2) {
+    const int64_t nl = nb * c->nf[2] * c->nf[1];
+    k_p2c_prolong_x_add<<<dim3((unsigned)phx_div_up(nl, 4)), dim3(256), 0, st>>>(nl, g, c->lptr, c->lx, c->lpos, c->dpos, c->X1, vout);
+  } else {
+    const int64_t tf = nb * s->mesh->nv;
+    k_cc_prolong_x_add<<<cc_grid(tf), dim3(256), 0, st>>>(tf, g, c->cpos, c->dpos, c->X1, vout);
+  }
   PHX_HIP(hipGetLastError());
   return PHX_OK;
+}
+// vout += D R zc,  zc = Ac^-1 gc  (gc: the restricted vector, all-reduced by the driver on a partitioned box)
+static int coarse_apply_end(phx_system *s, phx_coarse *c, double *vout) {
+  if (!c || c->nc == 0) return PHX_OK;
+  hipStream_t st = s->mesh->stream;
+  if (s->n == 0) return PHX_OK;   // a slab outside the domain: nothing to prolong onto
+  if (c->p2) k_p2c_gemv<<<dim3((unsigned)phx_div_up(c->nc, 4)), dim3(256), 0, st>>>(c->nc, c->Ainv, c->gc, c->zc);
+  else k_cc_gemv<<<dim3((unsigned)phx_div_up(c->nc, 4)), dim3(256), 0, st>>>(c->nc, c->Ainv, c->gc, c->zc);
+  return coarse_prolong_add(s, c, vout);
 }
 // vout += D R Ac^-1 R^T vin on one rank
 static int coarse_apply_add(phx_system *s, phx_coarse *c, const double *vin, double *vout) {
@@ -451,7 +679,7 @@ static int coarse_build(phx_system *s, int nblk, phx_coarse **out, const CcReduc
   bool veto = false;
   phx_coarse *c = new phx_coarse();
   auto fail = [&](int code) { coarse_free(c); return code; };
-  c->d = d; c->nblk_u = 2 * d; c->ratio = ratio; c->dist = reduce != nullptr;
+  c->d = d; c->nblk_u = 2 * d; c->ratio = ratio; c->ratio_h = ratio; c->dist = reduce != nullptr;
   c->M = 1;
   for (int a = 0; a < 3; ++a) {
     c->nf[a] = a < d ? m->box_n[a] + 1 : 1;
@@ -490,6 +718,7 @@ static int coarse_build(phx_system *s, int nblk, phx_coarse **out, const CcReduc
   static const int nc_max = getenv("PHX_EL_COARSE_MAX") ? atoi(getenv("PHX_EL_COARSE_MAX")) : 24000;
   if (c->nc == 0 || c->nc > nc_max) { coarse_free(c); return PHX_OK; }   // the same numbers on every rank
   const int nc = c->nc;
+  c->nc_blk[0] = nc;
   const int64_t t1 = nb * c->nf[2] * c->nf[1] * c->m[0], t2 = nb * c->nf[2] * c->m[1] * c->m[0], t3 = nb * c->M;
   double *wv = nullptr, *tv = nullptr, *X1s = nullptr, *X2s = nullptr, *X3s = nullptr, *T = nullptr, *vflag = nullptr;
   int32_t *f32 = nullptr;
@@ -543,6 +772,7 @@ static int coarse_build(phx_system *s, int nblk, phx_coarse **out, const CcReduc
     for (int bj = 0; bj < c->nblk_u && rc == PHX_OK; ++bj) {
       for (int cz = 0; cz < 3 && cz < c->m[2] && rc == PHX_OK; ++cz) {
         k_cc_probe_rows<<<cc_grid(n * 16), dim3(256), 0, st>>>(n, nv, bj, c->nblk_u, g, cz, s->rowptr, s->col, s->val, f32, c->cpos, T, tf);
+        ++c->probes;
         for (int cxy = 0; cxy < 9 && rc == PHX_OK; ++cxy) {
           if (cxy % 3 >= c->m[0] || cxy / 3 >= c->m[1]) continue;   // a colour no node of the lattice carries
           const int col = cxy + 9 * cz;
@@ -562,6 +792,7 @@ static int coarse_build(phx_system *s, int nblk, phx_coarse **out, const CcReduc
       if (hipMemsetAsync(wv, 0, sizeof(double) * (size_t)n, st) != hipSuccess) { rc = PHX_ERR_HIP; break; }
       k_cc_probe<<<cc_grid(nv), dim3(256), 0, st>>>(nv, bj, col, g, c->cpos, c->dpos, wv);
       rc = launch_spmv(s, s->sell_val, wv, tv, 0, nullptr, nullptr, nullptr, 0);
+      ++c->probes;
       if (rc == PHX_OK && lumped) {
         rc = coarse_restrict(s, c, tv);
         if (rc == PHX_OK) k_cc_store_column<<<cc_grid(nc), dim3(256), 0, st>>>(nc, bj, col, g, c->node_of, c->cmap, c->gc, c->Ainv);
@@ -587,6 +818,198 @@ static int coarse_build(phx_system *s, int nblk, phx_coarse **out, const CcReduc
     coarse_free(c);
     return PHX_OK;
   }
+  *out = c;
+  return PHX_OK;
+}
+
+// ---- P2 weak Dirichlet on a generated Kuhn box (PHX_OPT_P2_COARSE), one rank ------------------------------------------
+// M^-1 = (h/2-lattice sine transform on u (+) Jacobi on p) + D R Ac^-1 R^T, Ac = R^T A R (additive, as the CPU prototype
+// tools/experiments/p2_band_precond.py).  R: multilinear hats of spacing H = ratio h, one set per field, on the active
+// rows of that field.
+//   * Probing colours.  A couples two P2 DoFs when they share a cell or two cells share a ghost-penalty facet: at most
+//     2 h = 4 lattice steps apart per axis.  With H = 2 r steps, the hat of node c covers |i - 2 r c| <= 2 r - 1 and its
+//     image under A |i - 2 r c| <= 2 r + 3.  Same-colour nodes are 6 r apart: the images are disjoint for r >= 4, and the
+//     split of cc_part (half a coarse cell, r steps, beyond the node) separates them when 2 r c + 3 < 2 r c + r and
+//     2 r (c + 1) - 3 >= 2 r c + r, i.e. r >= 4.  The option takes r >= 5.
+//   * Column scaling.  The loop iterates on A C (C = 1 on the u columns of a structured system, D^-1 elsewhere: the
+//     u_unscaled convention); the probes are C^-1 R e, so that A C (C^-1 R e) = A R e, and the prolongation is C^-1 R.
+enum { PHX_CC_NOT_BOX = 1, PHX_CC_SMALL_BOX = 2, PHX_CC_TOO_MANY = 3, PHX_CC_SINGULAR = 4, PHX_CC_CHECK = 5,
+       PHX_CC_AUTO_OFF = 6 };
+#define PHX_P2C_NC_MAX 20000      // phx_dense_inverse
+// automatic choice: on for PHX_P2C_AUTO_MIN_N <= n < PHX_P2C_AUTO_MAX_N cubes per axis only.  Measured on MI355X
+// ("P2 coarse space"): the correction saves seconds at 96^3 (0.57 -> 0.46 s), breaks even at 64^3 and
+// 128^3, and costs at 256^3 (3.37 -> 4.35 s: 764 -> 714 iterations do not pay for the dearer iteration)
+#define PHX_P2C_AUTO_MIN_N 80
+#define PHX_P2C_AUTO_MAX_N 128
+
+// compact coarse DoFs for the ratio set in c (c->m, c->M, c->ratio): hmap / hnode as coarse_build, *nc_u of field u
+static int p2c_count_used(phx_system *s, phx_coarse *c, uint8_t *used, std::vector<int32_t> &hmap,
+                          std::vector<int32_t> &hnode, int *nc_u) {
+  hipStream_t st = s->mesh->stream;
+  const CcDims g{{c->nf[0], c->nf[1], c->nf[2]}, {c->m[0], c->m[1], c->m[2]}, c->ratio, c->M, {0, 0, 0}};
+  const int64_t nl = 2 * c->nf[1] * c->nf[2], tot = 2 * c->M;
+  PHX_HIP(hipMemsetAsync(used, 0, (size_t)tot, st));
+  k_p2c_used<<<dim3((unsigned)phx_div_up(nl * 64, 256)), dim3(256), 0, st>>>(nl, g, c->lptr, c->lx, used);
+  PHX_HIP(hipGetLastError());
+  std::vector<uint8_t> hu((size_t)tot);
+  PHX_HIP(hipMemcpyAsync(hu.data(), used, (size_t)tot, hipMemcpyDeviceToHost, st));
+  PHX_HIP(hipStreamSynchronize(st));
+  hmap.assign((size_t)tot, -1);
+  hnode.clear();
+  *nc_u = 0;
+  for (int64_t q = 0; q < tot; ++q)
+    if (hu[(size_t)q]) {
+      hmap[(size_t)q] = (int32_t)hnode.size();
+      hnode.push_back((int32_t)q);
+      if (q < c->M) ++*nc_u;
+    }
+  return PHX_OK;
+}
+
+// Builds the correction of the P2 system `s` on its first solve (*out = nullptr and s->cc_reason set when it cannot).
+static int p2_coarse_build(phx_system *s, phx_coarse **out) {
+  *out = nullptr;
+  s->cc_reason = 0;
+  phx_mesh *m = s->mesh;
+  hipStream_t st = m->stream;
+  const int req = m->p2_coarse;
+  if (req == 0) return PHX_OK;
+  const auto t0 = std::chrono::steady_clock::now();
+  if (!m->is_box || m->is_submesh || !m->edges || s->own || s->kr_work || s->precond_state != 1 || !s->precond ||
+      s->precond->dist || s->n == 0 || !s->u_p2_block) {
+    s->cc_reason = PHX_CC_NOT_BOX;
+    return PHX_OK;
+  }
+  const int d = m->gdim;
+  int64_t nmax = 0;
+  for (int a = 0; a < d; ++a) nmax = std::max<int64_t>(nmax, m->box_n[a]);
+  if (req < 0 && (nmax < PHX_P2C_AUTO_MIN_N || nmax >= PHX_P2C_AUTO_MAX_N)) { s->cc_reason = PHX_CC_AUTO_OFF; return PHX_OK; }
+  const int rmin = req > 0 ? req : 5;
+  if (nmax < 2 * rmin) { s->cc_reason = PHX_CC_SMALL_BOX; return PHX_OK; }
+  PHX_REQUIRE(2 * m->box_n[0] + 1 <= 65535, PHX_ERR_VALUE, "P2 coarse space: more than 32767 cubes along x");
+  const int64_t n = s->n;
+  phx_coarse *c = new phx_coarse();
+  uint8_t *used = nullptr;
+  int32_t *cnt = nullptr;
+  double *wv = nullptr, *tv = nullptr, *X1s = nullptr, *X2s = nullptr, *X3s = nullptr;
+  auto drop = [&]() {
+    (void)phx_free(used); (void)phx_free(cnt); (void)phx_free(wv); (void)phx_free(tv);
+    (void)phx_free(X1s); (void)phx_free(X2s); (void)phx_free(X3s);
+  };
+  auto fail = [&](int code) { drop(); coarse_free(c); return code; };
+  auto give_up = [&](int reason) { drop(); coarse_free(c); s->cc_reason = reason; return PHX_OK; };
+  c->p2 = true; c->d = d; c->nblk_u = 2;
+  for (int a = 0; a < 3; ++a) c->nf[a] = a < d ? 2 * m->box_n[a] + 1 : 1;
+  const int64_t nl = 2 * c->nf[1] * c->nf[2];
+  // ---- the per-line lists of the active rows
+  const P2cGeo q{s->nent, m->nv, m->box_n[0] + 1, m->box_n[1] + 1, c->nf[1], c->nf[2], m->edges};
+  if (phx_malloc(&c->lptr, sizeof(int64_t) * (size_t)(nl + 1)) != hipSuccess || phx_malloc(&c->lx, sizeof(uint16_t) * (size_t)n) != hipSuccess ||
+      phx_malloc(&c->lpos, sizeof(int32_t) * (size_t)n) != hipSuccess || phx_malloc(&cnt, sizeof(int32_t) * (size_t)nl) != hipSuccess ||
+      phx_malloc(&c->dpos, sizeof(double) * (size_t)n) != hipSuccess)
+    return fail(PHX_ERR_HIP);
+  if (hipMemsetAsync(cnt, 0, sizeof(int32_t) * (size_t)nl, st) != hipSuccess) return fail(PHX_ERR_HIP);
+  k_p2c_count<<<cc_grid(n), dim3(256), 0, st>>>(n, q, s->full_of_active, cnt);
+  std::vector<int32_t> hcnt((size_t)nl);
+  std::vector<int64_t> hptr((size_t)nl + 1);
+  if (hipMemcpyAsync(hcnt.data(), cnt, sizeof(int32_t) * (size_t)nl, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return fail(PHX_ERR_HIP);
+  hptr[0] = 0;
+  for (int64_t l = 0; l < nl; ++l) hptr[(size_t)l + 1] = hptr[(size_t)l] + hcnt[(size_t)l];
+  if (hptr[(size_t)nl] != n) { phx_set_error("P2 coarse space: %lld rows on the lattice lines, %lld active", (long long)hptr[(size_t)nl], (long long)n); return fail(PHX_ERR_VALUE); }
+  if (hipMemcpyAsync(c->lptr, hptr.data(), sizeof(int64_t) * hptr.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemsetAsync(cnt, 0, sizeof(int32_t) * (size_t)nl, st) != hipSuccess)
+    return fail(PHX_ERR_HIP);
+  k_p2c_fill<<<cc_grid(n), dim3(256), 0, st>>>(n, q, s->full_of_active, s->iperm, c->lptr, cnt, c->lx, c->lpos);
+  k_p2c_sort<<<dim3((unsigned)phx_div_up(nl, 4)), dim3(256), sizeof(int32_t) * 4 * (size_t)c->nf[0], st>>>(nl, (int)c->nf[0], c->lptr, c->lx, c->lpos);
+  k_p2c_dpos<<<cc_grid(n), dim3(256), 0, st>>>(n, s->nu, s->u_unscaled, s->perm, s->diag, c->dpos);
+  if (hipGetLastError() != hipSuccess) return fail(PHX_ERR_HIP);
+  // ---- the ratio: the one asked for, or (automatic) the smallest >= 5 whose compact coarse space fits the dense inverse
+  // and whose dense apply streams at most a quarter of the bytes of one SpMV (its value streams, x read, y written)
+  const double spmv_bytes = (double)s->sell_stream_bytes + 16.0 * (double)n;
+  std::vector<int32_t> hmap, hnode;
+  int nc_u = 0;
+  for (int r = rmin;; ++r) {
+    if (nmax < 2 * r) return give_up(req > 0 ? PHX_CC_SMALL_BOX : PHX_CC_TOO_MANY);
+    c->ratio_h = r;
+    c->ratio = 2 * r;
+    c->M = 1;
+    for (int a = 0; a < 3; ++a) {
+      c->m[a] = a < d ? (int)phx_div_up(m->box_n[a], r) + 1 : 1;
+      c->M *= c->m[a];
+    }
+    (void)phx_free(used);
+    used = nullptr;
+    if (phx_malloc(&used, (size_t)(2 * c->M)) != hipSuccess) return fail(PHX_ERR_HIP);
+    const int rcu = p2c_count_used(s, c, used, hmap, hnode, &nc_u);
+    if (rcu != PHX_OK) return fail(rcu);
+    const double nc2 = (double)hnode.size() * (double)hnode.size();
+    if (hnode.size() <= PHX_P2C_NC_MAX && (req > 0 || 8.0 * nc2 <= 0.25 * spmv_bytes)) break;
+    if (req > 0) return give_up(PHX_CC_TOO_MANY);
+  }
+  c->nc = (int)hnode.size();
+  c->nc_blk[0] = nc_u;
+  c->nc_blk[1] = c->nc - nc_u;
+  if (c->nc == 0) return give_up(PHX_CC_TOO_MANY);
+  const int nc = c->nc;
+  const CcDims g{{c->nf[0], c->nf[1], c->nf[2]}, {c->m[0], c->m[1], c->m[2]}, c->ratio, c->M, {0, 0, 0}};
+  const int64_t t1 = 2 * c->nf[2] * c->nf[1] * c->m[0], t2 = 2 * c->nf[2] * c->m[1] * c->m[0], t3 = 2 * c->M;
+  if (phx_malloc(&c->cmap, sizeof(int32_t) * (size_t)t3) != hipSuccess || phx_malloc(&c->node_of, sizeof(int32_t) * (size_t)nc) != hipSuccess ||
+      phx_malloc(&c->Ainv, sizeof(double) * (size_t)nc * nc) != hipSuccess || phx_malloc(&c->X1, sizeof(double) * (size_t)t1) != hipSuccess ||
+      phx_malloc(&c->X2, sizeof(double) * (size_t)t2) != hipSuccess || phx_malloc(&c->X3, sizeof(double) * (size_t)t3) != hipSuccess ||
+      phx_malloc(&c->gc, sizeof(double) * (size_t)nc) != hipSuccess || phx_malloc(&c->zc, sizeof(double) * (size_t)nc) != hipSuccess ||
+      phx_malloc(&X1s, sizeof(double) * (size_t)t1 * 2) != hipSuccess || phx_malloc(&X2s, sizeof(double) * (size_t)t2 * 4) != hipSuccess ||
+      phx_malloc(&X3s, sizeof(double) * (size_t)t3 * 8) != hipSuccess || phx_malloc(&wv, sizeof(double) * (size_t)n) != hipSuccess ||
+      phx_malloc(&tv, sizeof(double) * (size_t)n) != hipSuccess)
+    return fail(PHX_ERR_HIP);
+  if (hipMemcpyAsync(c->cmap, hmap.data(), sizeof(int32_t) * hmap.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(c->node_of, hnode.data(), sizeof(int32_t) * hnode.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemsetAsync(c->Ainv, 0, sizeof(double) * (size_t)nc * nc, st) != hipSuccess)
+    return fail(PHX_ERR_HIP);
+  // ---- Ac by probing through the solver's own operator: one product per (field, colour)
+  const int64_t lpf = c->nf[1] * c->nf[2];   // lines per field
+  for (int bj = 0; bj < 2; ++bj) {
+    for (int col = 0; col < (d == 3 ? 27 : 9); ++col) {
+      const int cc3[3] = {col % 3, (col / 3) % 3, col / 9};
+      if (cc3[0] >= c->m[0] || cc3[1] >= c->m[1] || cc3[2] >= c->m[2]) continue;   // a colour no node carries
+      if (hipMemsetAsync(wv, 0, sizeof(double) * (size_t)n, st) != hipSuccess) return fail(PHX_ERR_HIP);
+      k_p2c_probe<<<dim3((unsigned)phx_div_up(lpf * 64, 256)), dim3(256), 0, st>>>(lpf, bj * lpf, col, g, c->lptr, c->lx, c->lpos, c->dpos, wv);
+      int rc = launch_spmv(s, s->sell_val, wv, tv, 0, nullptr, nullptr, nullptr, 0);
+      if (rc == PHX_OK) rc = coarse_restrict_split(s, c, col, tv, false, X1s, X2s, X3s);
+      if (rc != PHX_OK) return fail(rc);
+      k_cc_store_parts<<<cc_grid(nc), dim3(256), 0, st>>>(nc, bj, col, g, c->node_of, c->cmap, X3s, c->Ainv);
+      ++c->probes;
+    }
+  }
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(PHX_ERR_HIP);
+  // ---- dense inverse, then the check |Ac Ac^-1 v - v| / |v| with Ac v' = R^T A C (C^-1 R v') through the operator: the
+  // elimination flags a singular pivot only when it is exactly zero
+  int singular = 0;
+  const int rci = dense_inverse_inplace(c->Ainv, nc, st, &singular);
+  if (rci != PHX_OK) return fail(rci);
+  if (singular) return give_up(PHX_CC_SINGULAR);
+  std::vector<double> hv((size_t)nc), hg((size_t)nc);
+  for (int i = 0; i < nc; ++i) hv[(size_t)i] = 1.0 + (double)((i * 7) % 13) / 13.0;
+  if (hipMemcpyAsync(c->gc, hv.data(), sizeof(double) * (size_t)nc, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemsetAsync(wv, 0, sizeof(double) * (size_t)n, st) != hipSuccess)
+    return fail(PHX_ERR_HIP);
+  k_p2c_gemv<<<dim3((unsigned)phx_div_up(nc, 4)), dim3(256), 0, st>>>(nc, c->Ainv, c->gc, c->zc);
+  int rc = coarse_prolong_add(s, c, wv);
+  if (rc == PHX_OK) rc = launch_spmv(s, s->sell_val, wv, tv, 0, nullptr, nullptr, nullptr, 0);
+  if (rc == PHX_OK) rc = coarse_restrict(s, c, tv);
+  if (rc != PHX_OK) return fail(rc);
+  ++c->probes;
+  if (hipMemcpyAsync(hg.data(), c->gc, sizeof(double) * (size_t)nc, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    return fail(PHX_ERR_HIP);
+  double e2 = 0.0, v2 = 0.0;
+  for (int i = 0; i < nc; ++i) {
+    e2 += (hg[(size_t)i] - hv[(size_t)i]) * (hg[(size_t)i] - hv[(size_t)i]);
+    v2 += hv[(size_t)i] * hv[(size_t)i];
+  }
+  if (!(e2 <= 1e-12 * v2)) return give_up(PHX_CC_CHECK);   // NaN included
+  drop();
+  c->build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   *out = c;
   return PHX_OK;
 }

@@ -153,6 +153,7 @@ struct phx_mesh {
   int structured = 1;              // PHX_OPT_STRUCTURED: stencil-coded interior rows on Kuhn boxes (P1 weak Dirichlet)
   int allow_empty = 0;             // PHX_OPT_ALLOW_EMPTY: assembly returns an EMPTY system when no cell is tagged 1 / 2
   int el_coarse = -1;              // PHX_OPT_EL_COARSE
+  int p2_coarse = 0;               // PHX_OPT_P2_COARSE: 0 off, -1 automatic, >= 5 the ratio H / h
   int deterministic = 0;           // PHX_OPT_DETERMINISTIC: bit-reproducible P2 / elasticity assembly and Krylov dot products
   // A caller-supplied mesh that IS a Kuhn box in some vertex / cell order (what dolfinx's create_box / create_rectangle
   // hand over, demo/weak-dirichlet/flower/main.py:45-46): `inner` is the generated box with the same lattice, the maps
@@ -292,6 +293,7 @@ struct phx_system {
   bool bj_tried = false;
   struct phx_coarse *cc = nullptr; // coarse correction on top of the vertex blocks (phx_coarse.inc.hip)
   bool cc_tried = false;
+  int cc_reason = 0;               // P2 coarse correction asked for but not built: PHX_CC_* reason (phx_coarse.inc.hip)
   // PHX_OPT_DETERMINISTIC: every block of a dot-product kernel leaves its partial sum in its own entry of `dpart`
   // ([4][dpart_cap]) instead of adding it to a slot atomically; k_fold_partials sums them in a fixed order
   double *dpart = nullptr;

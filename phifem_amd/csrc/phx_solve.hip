@@ -2044,7 +2044,17 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
       s->bj_tried = true;
       PHX_CHECK(blockjac_build(s, s->el_nblk, &s->bj));   // nullptr when a vertex block is singular: scalar Jacobi then
       // coarse correction on top of the vertex blocks (one rank; a partitioned box keeps the blocks alone)
-      if (s->bj && !s->own && !s->kr_work && !s->cc_tried) { s->cc_tried = true; PHX_CHECK(coarse_build(s, s->el_nblk, &s->cc)); }
+      if (s->bj && !s->own && !s->kr_work && !s->cc_tried) {
+        s->cc_tried = true;
+        const auto t0 = std::chrono::steady_clock::now();
+        PHX_CHECK(coarse_build(s, s->el_nblk, &s->cc));
+        if (s->cc) s->cc->build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      }
+    }
+    // P2 weak Dirichlet: coarse correction on top of the lattice preconditioner (PHX_OPT_P2_COARSE), once per system
+    if (s->u_p2_block && m->p2_coarse != 0 && !s->cc_tried) {
+      s->cc_tried = true;
+      PHX_CHECK(p2_coarse_build(s, &s->cc));
     }
     if ((s->precond_state == 1 || s->u_unscaled || s->bj) && n > 0 && !s->kr_work) {
       // phat / shat: rows the preconditioner never writes (u rows another rank owns) stay zero
@@ -2106,13 +2116,17 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
       k_update_p<<<vec_grid(n), block, 0, st>>>(n, par, s->own, V.r, V.v, V.p, V.rhat, S, kr_drop2(s), rop);
       break;
     case KR_PRECOND_P:
-      if (s->precond_state == 1) PHX_CHECK(box_precond_apply(s, V.p, V.phat, s->precond->dist ? 1 : 0));
-      else if (s->bj) { PHX_CHECK(blockjac_apply(s, s->bj, V.p, V.phat)); PHX_CHECK(coarse_apply_add(s, s->cc, V.p, V.phat)); }
+      if (s->precond_state == 1) {
+        PHX_CHECK(box_precond_apply(s, V.p, V.phat, s->precond->dist ? 1 : 0));
+        if (s->cc && s->cc->p2) PHX_CHECK(coarse_apply_add(s, s->cc, V.p, V.phat));
+      } else if (s->bj) { PHX_CHECK(blockjac_apply(s, s->bj, V.p, V.phat)); PHX_CHECK(coarse_apply_add(s, s->cc, V.p, V.phat)); }
       else if (s->u_unscaled && n > 0) k_jacobi_u<<<vec_grid(n), block, 0, st>>>(n, s->nu, s->perm, s->diag, V.p, V.phat);
       break;
     case KR_PRECOND_S:
-      if (s->precond_state == 1) PHX_CHECK(box_precond_apply(s, V.sv, V.shat, s->precond->dist ? 1 : 0));
-      else if (s->bj) { PHX_CHECK(blockjac_apply(s, s->bj, V.sv, V.shat)); PHX_CHECK(coarse_apply_add(s, s->cc, V.sv, V.shat)); }
+      if (s->precond_state == 1) {
+        PHX_CHECK(box_precond_apply(s, V.sv, V.shat, s->precond->dist ? 1 : 0));
+        if (s->cc && s->cc->p2) PHX_CHECK(coarse_apply_add(s, s->cc, V.sv, V.shat));
+      } else if (s->bj) { PHX_CHECK(blockjac_apply(s, s->bj, V.sv, V.shat)); PHX_CHECK(coarse_apply_add(s, s->cc, V.sv, V.shat)); }
       else if (s->u_unscaled && n > 0) k_jacobi_u<<<vec_grid(n), block, 0, st>>>(n, s->nu, s->perm, s->diag, V.sv, V.shat);
       break;
     case KR_CC_RESTRICT_P: if (s->cc) PHX_CHECK(coarse_restrict(s, s->cc, V.p)); break;
@@ -2305,7 +2319,7 @@ extern "C" int phx_precond_info(phx_system *s, double *out) {
   if (s->cc) { out[1] = (double)s->cc->ratio; out[4] = (double)s->cc->nc; }
   if (s->precond_state != 1) return PHX_OK;
   const BoxGrid &g = s->precond->g;
-  out[0] = 1.0;
+  out[0] = s->cc && s->cc->p2 ? 4.0 : 1.0;   // 4: with the P2 coarse correction
   for (int a = 0; a < 3; ++a) out[1 + a] = (double)g.L[a];
   out[4] = (double)g.m[0] * (double)g.m[1] * (double)g.m[2];
   double avg = 0.0;
@@ -2314,6 +2328,31 @@ extern "C" int phx_precond_info(phx_system *s, double *out) {
   out[5] = avg;
   out[6] = (double)cnt;
   out[7] = s->precond->f32 ? 4.0 : 8.0;
+  return PHX_OK;
+}
+
+extern "C" int phx_coarse_info(phx_system *s, double *out) {
+  for (int i = 0; i < 6; ++i) out[i] = 0.0;
+  const phx_coarse *c = s->cc;
+  if (!c) {
+    out[0] = -(double)s->cc_reason;
+    return PHX_OK;
+  }
+  out[0] = (double)c->ratio_h;
+  out[1] = (double)c->nc_blk[0];
+  out[2] = (double)c->nc_blk[1];
+  out[3] = c->build_s;
+  out[4] = (double)c->probes;
+  out[5] = 8.0 * (double)c->nc * (double)c->nc;
+  return PHX_OK;
+}
+
+extern "C" int phx_coarse_export(phx_system *s, int32_t *node_of, double *ainv) {
+  PHX_REQUIRE(s->cc && s->cc->nc > 0, PHX_ERR_VALUE, "the system has no coarse correction (solve it first, with the option set)");
+  PHX_HIP(hipSetDevice(s->mesh->device));
+  const phx_coarse *c = s->cc;
+  if (node_of) PHX_HIP(hipMemcpy(node_of, c->node_of, sizeof(int32_t) * (size_t)c->nc, hipMemcpyDeviceToHost));
+  if (ainv) PHX_HIP(hipMemcpy(ainv, c->Ainv, sizeof(double) * (size_t)c->nc * c->nc, hipMemcpyDeviceToHost));
   return PHX_OK;
 }
 

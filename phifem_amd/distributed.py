@@ -266,8 +266,10 @@ class P2Problem(SlabProblem):
     are applied from eight translation-invariant stencils and never assembled or stored, which is what lets the
     512^3 box of the config (1.08e9 P2 entities per field, 1.7e8 active rows) fit one GPU."""
 
-    def __init__(self, n, device=0, rtol=1e-8, max_iter=100000):
+    def __init__(self, n, device=0, rtol=1e-8, max_iter=100000, coarse_space=None):
+        """coarse_space: PhiFEMSolver's two-level option (None: off, "auto", or H / h >= 5)."""
         self.n, self.device, self.rtol, self.max_iter = n, device, rtol, max_iter
+        self.coarse_space = coarse_space
         self.world, self.rank = 1, 0
 
     def setup(self):
@@ -278,7 +280,8 @@ class P2Problem(SlabProblem):
         L.check(L.lib.phx_mesh_get_array(self.mesh._h, L.ARR_COORDS, C.c_void_p(x.data_ptr()), L.DEVICE))
         self.phi1 = (x ** 2).sum(dim=1) - 1.0            # P1 nodal values drive the tagging
         # bit-reproducible assembly and dot products (the iteration count moved between 694 and 892 without)
-        self.solver = PhiFEMSolver(self.mesh, degree=2, levelset_degree=2, deterministic=True)
+        self.solver = PhiFEMSolver(self.mesh, degree=2, levelset_degree=2, deterministic=True,
+                                   coarse_space=self.coarse_space)
         ne = self.mesh.ne                                 # builds the edge numbering
         e = torch.empty((ne, 2), dtype=torch.int32, device=dev)
         L.check(L.lib.phx_mesh_get_array(self.mesh._h, L.ARR_EDGES, C.c_void_p(e.data_ptr()), L.DEVICE))

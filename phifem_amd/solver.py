@@ -30,9 +30,39 @@ def check_converged(stats, rtol, strict=False):
     warnings.warn(msg, ConvergenceWarning, stacklevel=3)
 
 
+_COARSE_REASONS = {
+    1: "not a single-rank P2 system on a generated box with the lattice preconditioner",
+    2: "the box is smaller than 2 H",
+    3: "too many coarse DoFs for the dense inverse (20000)",
+    4: "the Galerkin coarse matrix is singular",
+    5: "the check |Ac Ac^-1 v - v| of the inverse failed",
+    6: "automatic choice: the correction does not pay at this box size",
+}
+
+
+def _p2_coarse_option(coarse_space):
+    """PHX_OPT_P2_COARSE value of the `coarse_space` argument."""
+    if coarse_space is None:
+        return 0
+    if isinstance(coarse_space, str):
+        if coarse_space == "auto":
+            return -1
+        raise ValueError(f"coarse_space={coarse_space!r}: None, 'auto' or an int >= 5")
+    if isinstance(coarse_space, bool) or int(coarse_space) != coarse_space or int(coarse_space) < 5:
+        raise ValueError(f"coarse_space={coarse_space!r}: None, 'auto' or an int >= 5 (H / h)")
+    return int(coarse_space)
+
+
 class PhiFEMSolver:
-    def __init__(self, mesh, pen_coef=1.0, stab_coef=1.0, degree=1, levelset_degree=1, deterministic=False):
-        """deterministic=True (PHX_OPT_DETERMINISTIC): bit-reproducible assembly (degree 2: the element kernels run
+    def __init__(self, mesh, pen_coef=1.0, stab_coef=1.0, degree=1, levelset_degree=1, deterministic=False,
+                 coarse_space=None):
+        """coarse_space (PHX_OPT_P2_COARSE, degree 2 on a generated Kuhn box, one rank): two-level preconditioner, the
+        additive Galerkin correction R Ac^-1 R^T on multilinear functions of spacing H on top of the lattice sine
+        transform.  None (default): off; "auto": the library picks H (and leaves it off where it does not pay);
+        an int >= 5: H / h.  Built on the first solve; a correction that was asked for and could not be built is
+        reported by a RuntimeWarning and `stats["coarse_reason"]`.
+
+        deterministic=True (PHX_OPT_DETERMINISTIC): bit-reproducible assembly (degree 2: the element kernels run
         twice and accumulate exactly) and Krylov dot products -- the same matrix bits, iteration count and solution
         on every run; costs one more pass of the element kernels.
 
@@ -52,9 +82,17 @@ class PhiFEMSolver:
         self._sys = None
         self.stats = {}
         self.deterministic = bool(deterministic)
+        self.coarse_space = coarse_space
+        self._p2_coarse = _p2_coarse_option(coarse_space)
+        if self._p2_coarse != 0:
+            if degree != 2:
+                raise NotImplementedError("coarse_space is implemented for degree = 2")
+            if getattr(mesh, "parent", None) is not None:
+                raise NotImplementedError("coarse_space needs the box mesh (box_mode=True), not a sub-mesh")
 
     def _apply_options(self):
         L.check(L.lib.phx_set_option(self.mesh._h, L.OPT_DETERMINISTIC, int(getattr(self, "deterministic", False))))
+        L.check(L.lib.phx_set_option(self.mesh._h, L.OPT_P2_COARSE, int(getattr(self, "_p2_coarse", 0))))
         if hasattr(self, "coarse"):
             L.check(L.lib.phx_set_option(self.mesh._h, L.OPT_EL_COARSE, self.coarse))
 
@@ -206,6 +244,12 @@ class PhiFEMSolver:
         L.check(L.lib.phx_krylov_identity_loop(self._sys, C.byref(ident)))
         self.stats["identity_loop"] = bool(ident.value)
         self.stats.update(self.precond_info())
+        if getattr(self, "_p2_coarse", 0) != 0:
+            self.stats.update(self.coarse_info())
+            reason = self.stats["coarse_reason"]
+            if reason:
+                warnings.warn(f"coarse_space={self.coarse_space!r}: no coarse correction was built ({reason}); the solve "
+                              f"used the plain preconditioner", RuntimeWarning, stacklevel=2)
         check_converged(self.stats, rtol, strict)
         return out
 
@@ -218,9 +262,31 @@ class PhiFEMSolver:
         """State of the fictitious-domain preconditioner after a solve (phx_precond_info)."""
         o = (C.c_double * 8)()
         L.check(L.lib.phx_precond_info(self._sys, o))
-        return {"precond": {1: "box-dst", 2: "vertex-block-jacobi", 3: "vertex-block-jacobi+coarse"}.get(int(o[0]), "jacobi"), "precond_L": [int(o[1]), int(o[2]), int(o[3])],
+        return {"precond": {1: "box-dst", 2: "vertex-block-jacobi", 3: "vertex-block-jacobi+coarse",
+                            4: "box-dst+coarse"}.get(int(o[0]), "jacobi"), "precond_L": [int(o[1]), int(o[2]), int(o[3])],
                 "precond_points": int(o[4]), "dst_avg_s": o[5], "dst_timed": int(o[6]),
                 "precond_value_bytes": int(o[7])}
+
+    def coarse_info(self):
+        """The coarse-space correction after a solve (phx_coarse_info): ratio H / h, coarse DoFs of u and p, build
+        seconds, operator products of the probing, bytes of the dense apply; `coarse_reason` names why a requested
+        correction was not built (None when it was, or when none was asked for)."""
+        o = (C.c_double * 6)()
+        L.check(L.lib.phx_coarse_info(self._sys, o))
+        built = o[1] + o[2] > 0
+        return {"coarse_ratio": int(o[0]) if built else 0, "coarse_dofs": int(o[1] + o[2]),
+                "coarse_dofs_u": int(o[1]), "coarse_dofs_p": int(o[2]), "coarse_build_s": o[3],
+                "coarse_probes": int(o[4]), "coarse_apply_bytes": int(o[5]),
+                "coarse_reason": None if built else _COARSE_REASONS.get(int(-o[0]))}
+
+    def coarse_export(self):
+        """(node_of, Ac^-1) of the coarse correction (phx_coarse_export): node_of[i] = field * M + node of compact
+        coarse DoF i, node = i + m0 (j + m1 k) at the lattice point (i, j, k) * H."""
+        nc = self.coarse_info()["coarse_dofs"]
+        node_of = np.empty(nc, dtype=np.int32)
+        ainv = np.empty((nc, nc), dtype=np.float64)
+        L.check(L.lib.phx_coarse_export(self._sys, node_of.ctypes.data_as(C.c_void_p), ainv.ctypes.data_as(C.c_void_p)))
+        return node_of, ainv
 
     def spmv(self, x):
         y = np.empty_like(x)
