@@ -413,6 +413,10 @@ int phx_coarse_export(phx_system *s, int32_t *node_of, double *ainv);
  * preconditioner: SpMVs over the stored rows only, A K_box^-1 = I on the stencil rows), 0 for the standard loop.
  * PHX_KR_IDENTITY=0 in the environment forces the standard loop. */
 int phx_krylov_identity_loop(const phx_system *s, int *on);
+/* After phx_solve: *on = 1 when the identity loop ran on compact vectors over the stored rows (started from
+ * x0 = M^-1 E_C b_C, so that every Krylov vector vanishes on the stencil rows).  PHX_KR_REDUCED=0 in the environment
+ * keeps the full-length identity loop. */
+int phx_krylov_reduced_loop(const phx_system *s, int *on);
 /* Phases (the KrPhase names of phx_solve.hip): 0 KR_BEGIN, 1 KR_BEGIN2, 2 KR_SPMV_P v = A phat, 3 KR_UPDATE_S
  * s-update, 4 KR_SPMV_S t = A shat, 5 KR_UPDATE_XR x/r-update, 6 KR_UPDATE_P p-update + roll, 7 KR_PRECOND_P phat = P p,
  * 8 KR_PRECOND_S shat = P s (no-ops without a preconditioner); with the slab-exact preconditioner

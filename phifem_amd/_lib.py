@@ -111,6 +111,7 @@ SIGNATURES = {
     "phx_system_export": ([_vp, _vp, _vp, _vp, _vp, _vp], _i),
     "phx_solve": ([_vp, _i, _d, _i64, _vp, _i, _pd], _i),
     "phx_krylov_identity_loop": ([_vp, C.POINTER(C.c_int)], _i),
+    "phx_krylov_reduced_loop": ([_vp, C.POINTER(C.c_int)], _i),
     "phx_spmv": ([_vp, _vp, _vp, _i], _i),
     "phx_spmv_bench": ([_vp, _i, _pd], _i),
     "phx_last_timings": ([_vp, _pd], _i),

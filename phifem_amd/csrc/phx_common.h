@@ -303,6 +303,9 @@ struct phx_system {
   int kr_ident_coef = -1;          // -1 not checked; 1: the stencil row equals the lattice row of the preconditioner
   bool kr_ident_used = false;      // the last phx_solve ran the identity loop
   uint32_t *kr_cmask = nullptr;    // [ceil(n / 32)] bit q: solver position q is applied by the stencil blocks
+  // reduced loop (kr_reduced): the identity loop on compact stored-row vectors
+  bool kr_red_used = false;        // the last phx_solve ran it
+  double *kr_red = nullptr;        // [7 * nslices * 16 + n] r, rhat, p, v, s, t, u_B (compact), u (solver order)
   // system assembled on the `inner` box of a caller-supplied mesh: vertex of s->mesh -> vertex of the caller's mesh
   // (applied where full DoF indices leave the library: the solution vector, phx_system_export's dof map)
   const int32_t *out_vertex = nullptr;

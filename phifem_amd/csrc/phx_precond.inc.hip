@@ -711,6 +711,13 @@ struct phx_box_precond {
   bool ztri = true;          // z direction: tridiagonal solve (default) or forward / inverse sine transform in LDS
   bool rowskip = false;      // an APPLICATION is running (gathering / scattering x passes around the middle passes): rows of
                              // x lines without a mapped point are neither written by the forward passes nor read back
+  const int2 *line_iv_out = nullptr;   // set while the backward passes scatter through another map than the forward ones gather
+  // reduced loop (phx_solve.hip, kr_reduced): the input is a compact vector over the stored rows, the output is needed at
+  // the columns those rows read.  red_map[0]: lattice point -> compact stored-row index, red_map[1]: lattice point ->
+  // solver position for points in cols(stored rows); -1 none.  Line flags and row intervals of each, as line_any / line_iv.
+  int32_t *red_map[2] = {nullptr, nullptr};
+  uint8_t *red_any[2] = {nullptr, nullptr};
+  int2 *red_iv[2] = {nullptr, nullptr};
 };
 
 static void box_precond_free(phx_box_precond *bp) {
@@ -718,6 +725,7 @@ static void box_precond_free(phx_box_precond *bp) {
   (void)phx_free(bp->G); (void)phx_free(bp->gmap); (void)phx_free(bp->dscale); (void)phx_free(bp->iscale); (void)phx_free(bp->line_any); (void)phx_free(bp->line_iv);
   if (!bp->carry_borrowed) { (void)phx_free(bp->carry_send); (void)phx_free(bp->carry_recv); }
   (void)phx_free(bp->tri_in);
+  for (int k = 0; k < 2; ++k) { (void)phx_free(bp->red_map[k]); (void)phx_free(bp->red_any[k]); (void)phx_free(bp->red_iv[k]); }
   for (int a = 0; a < 3; ++a) if (bp->lam[a]) (void)hipFree(bp->lam[a]);   // only tables the cache did not take
   delete bp;
 }
@@ -846,7 +854,7 @@ template <typename T>
 static int box_pass_y_t(phx_box_precond *bp, hipStream_t st, phx_system *prof, int dir = 0) {
   const BoxGrid &g = bp->g;
   if (g.m[2] <= 0) return PHX_OK;
-  const int2 *ra = dir != 0 ? bp->line_iv : nullptr;
+  const int2 *ra = dir == 0 ? nullptr : dir == 2 && bp->line_iv_out ? bp->line_iv_out : bp->line_iv;
   const DstPlan &py = bp->plan[1];
   T *G = static_cast<T *>(bp->G);
   const size_t el = sizeof(T) * 2;
@@ -1424,6 +1432,84 @@ static int box_precond_apply(phx_system *s, const double *vin, double *vout, int
   if (part != 1) PHX_CHECK(box_pass_x<2>(bp, st, nullptr, vout));
   bp->rowskip = false;
   return PHX_OK;
+}
+
+// ---- maps of the reduced loop (phx_solve.hip, kr_reduced), built once per system
+// bidx[rows[k]] = k: compact index of a stored row
+__global__ void k_red_bidx(int64_t ns, const int32_t *__restrict__ rows, int32_t *__restrict__ bidx) {
+  const int64_t k = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (k < ns) bidx[rows[k]] = (int32_t)k;
+}
+// cols[c] = 1 for every column a stored row reads (SELL padding marks a few more: their values are then formed too)
+__global__ void k_red_cols(int64_t nnz, int64_t n, const int32_t *__restrict__ scol, uint8_t *__restrict__ cols) {
+  GRID_STRIDE(e, nnz) {
+    const int32_t c = scol[e];
+    if (c >= 0 && c < n) cols[c] = 1;
+  }
+}
+__global__ void k_red_maps(int64_t tot, const int32_t *__restrict__ gmap, const int32_t *__restrict__ bidx,
+                           const uint8_t *__restrict__ cols, int32_t *__restrict__ fwd, int32_t *__restrict__ bwd) {
+  GRID_STRIDE(e, tot) {
+    const int32_t q = gmap[e];
+    fwd[e] = q >= 0 ? bidx[q] : -1;
+    bwd[e] = q >= 0 && cols[q] ? q : -1;
+  }
+}
+
+static int box_red_maps(phx_system *s) {
+  phx_box_precond *bp = s->precond;
+  if (bp->red_map[0]) return PHX_OK;
+  hipStream_t st = s->mesh->stream;
+  const int64_t n = s->n, tot = bp->g.plane * bp->g.m[2], nlines = (int64_t)bp->g.m[1] * bp->g.m[2];
+  PHX_REQUIRE(tot > 0 && bp->line_iv, PHX_ERR_VALUE, "reduced loop: empty lattice");
+  int32_t *bidx = nullptr;
+  uint8_t *cols = nullptr;
+  PHX_HIP(phx_malloc(&bidx, sizeof(int32_t) * (size_t)n));
+  PHX_HIP(phx_malloc(&cols, (size_t)n));
+  for (int k = 0; k < 2; ++k) {
+    PHX_HIP(phx_malloc(&bp->red_map[k], sizeof(int32_t) * (size_t)tot));
+    PHX_HIP(phx_malloc(&bp->red_any[k], (size_t)nlines));
+    PHX_HIP(phx_malloc(&bp->red_iv[k], sizeof(int2) * (size_t)bp->g.m[2]));
+  }
+  PHX_HIP(hipMemsetAsync(bidx, 0xff, sizeof(int32_t) * (size_t)n, st));
+  PHX_HIP(hipMemsetAsync(cols, 0, (size_t)n, st));
+  const dim3 block(256);
+  k_red_bidx<<<dim3((unsigned)phx_div_up(s->n_sell_rows, 256)), block, 0, st>>>(s->n_sell_rows, s->sell_rows, bidx);
+  k_red_cols<<<dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(phx_div_up(s->sell_nnz, 256), 4096))), block, 0, st>>>(
+      s->sell_nnz, n, s->sell_col, cols);
+  k_red_maps<<<dim3((unsigned)std::min<int64_t>(phx_div_up(tot, 256), 8192)), block, 0, st>>>(tot, bp->gmap, bidx, cols,
+                                                                                             bp->red_map[0], bp->red_map[1]);
+  for (int k = 0; k < 2; ++k) {
+    k_line_any<<<dim3((unsigned)phx_div_up(nlines * 64, 256)), block, 0, st>>>(bp->g, bp->red_map[k], bp->red_any[k]);
+    k_line_intervals<<<dim3((unsigned)bp->g.m[2]), dim3(64), 0, st>>>(bp->g.m[1], bp->g.m[2], bp->red_any[k], bp->red_iv[k]);
+  }
+  PHX_HIP(hipGetLastError());
+  PHX_HIP(hipStreamSynchronize(st));   // the temporaries are freed behind their last kernel
+  PHX_HIP(phx_free(bidx));
+  PHX_HIP(phx_free(cols));
+  return PHX_OK;
+}
+
+// vout = K_box^-1 vin of the reduced loop: vin is the compact stored-row vector (zero on every other row), gathered through
+// red_map[0]; vout is written at the columns the stored rows read (red_map[1]) and nowhere else.  The transform passes are
+// those of box_precond_apply; only the maps, line flags and row intervals they are handed differ.
+static int box_precond_apply_red(phx_system *s, const double *vin, double *vout) {
+  phx_box_precond *bp = s->precond;
+  hipStream_t st = s->mesh->stream;
+  int32_t *gmap = bp->gmap;
+  uint8_t *any = bp->line_any;
+  int2 *iv = bp->line_iv;
+  const int64_t nvec = bp->nvec;
+  bp->rowskip = true;
+  bp->gmap = bp->red_map[0]; bp->line_any = bp->red_any[0]; bp->line_iv = bp->red_iv[0]; bp->line_iv_out = bp->red_iv[1];
+  bp->nvec = s->n_sell_rows;
+  int rc = box_pass_x<1>(bp, st, vin, nullptr);
+  if (rc == PHX_OK) rc = box_solve_middle(bp, st, s);
+  bp->gmap = bp->red_map[1]; bp->line_any = bp->red_any[1]; bp->nvec = s->n;
+  if (rc == PHX_OK) rc = box_pass_x<2>(bp, st, nullptr, vout);
+  bp->gmap = gmap; bp->line_any = any; bp->line_iv = iv; bp->line_iv_out = nullptr; bp->nvec = nvec;
+  bp->rowskip = false;
+  return rc;
 }
 
 // Test / inspection entry: solve K_box u = f on an (L0-1) x (L1-1) x (L2-1) interior lattice with spacings h

@@ -954,7 +954,9 @@ struct StencilArgs {
   const int32_t *map;     // nullable: [8][chunk][2] {first slice, slices} per block (planes beyond the L2 window)
 };
 
-template <int DOTS>
+// CY (stored rows of a structured system only): y and the dot-product operands are compact vectors indexed by the SELL
+// slot (slice * 16 + row of the slice) instead of the solver position (reduced loop)
+template <int DOTS, bool CY = false>
 __global__ void __launch_bounds__(256)
 k_spmv_sell(int64_t n, int64_t nslices, const int64_t *__restrict__ slice_ptr,
             const int32_t *__restrict__ scol, const double *__restrict__ sval,
@@ -1091,11 +1093,13 @@ k_spmv_sell(int64_t n, int64_t nslices, const int64_t *__restrict__ slice_ptr,
       for (; j < trips; ++j) acc = __builtin_fma(NT_LOAD(&v[j * 64]), x[NT_LOAD(&c[j * 64])], acc);
       acc += __shfl_xor(acc, 16);
       acc += __shfl_xor(acc, 32);
-      const int32_t rr = rows[s * 16 + (lane & 15)];
+      const int64_t ci = s * 16 + (lane & 15);
+      const int32_t rr = rows[ci];
       if (lane < 16 && rr >= 0 && !(bnd && bnd[rr])) {
         if (own && !own[rr]) acc = 0.0;
-        y[rr] = acc;
-        PHX_DOT_ACC(acc, rr);
+        const int64_t yo = CY ? ci : (int64_t)rr;
+        y[yo] = acc;
+        PHX_DOT_ACC(acc, yo);
       }
     }
   } else if (s < nslices) {
@@ -1925,6 +1929,134 @@ k_ident_xrp(int64_t n, int par, const uint32_t *__restrict__ cmask, const double
   block_atomic_sum(apc, slot_base(S, par ^ 1, I_RV), part.p1);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Reduced loop (kr_reduced; on by default wherever the identity loop is, PHX_KR_REDUCED=0: the full-length identity loop).
+// B = A M^-1 has B[C,:] = I[C,:].  Starting from u0 = E_C b_C, x0 = M^-1 u0, gives r0_C = 0, hence rhat_C = 0 and
+// p, v, s, t vanish on C in every later iteration: BiCGStab on the full system from x0 lives on the stored rows alone.  So
+// r, rhat, p, v, s, t and the solution in u-space, u_B, are compact vectors in SELL stored-row order (index k, solver
+// position rows[k]) and x = M^-1 u is formed only where the loop hands out a solution (the true-residual check).  The
+// producers of p and s write their non-u entries (the identity part of M^-1) into phat / shat, as RestOut does.
+
+// b = rhs in solver order; u = b on the C rows, 0 elsewhere; (b, b) -> R_RHO of slot set 0
+__global__ void __launch_bounds__(256)
+k_red_begin(int64_t n, const int32_t *__restrict__ perm, const double *__restrict__ rhs, const uint32_t *__restrict__ cmask,
+            double *__restrict__ b, double *__restrict__ u, double *__restrict__ S, DotPart part) {
+  double acc = 0.0;
+  GRID_STRIDE(i, n) {
+    const double bi = rhs[perm[i]];
+    b[i] = bi;
+    u[i] = cmask_bit(cmask, i) ? bi : 0.0;
+    acc += bi * bi;
+  }
+  block_atomic_sum(acc, slot_base(S, 0, R_RHO), part.p0);
+}
+
+// r = rhat = p = src[rows[k]] - (sub ? sub[k] : 0) (begin: b - A x0; restart: the true residual); u_B = 0 when ub is
+// given; phat at non-u rows = p; (r, r) -> R_RR of slot set 0
+__global__ void __launch_bounds__(256)
+k_red_from(int64_t nb, const int32_t *__restrict__ rows, int64_t nu, const double *__restrict__ src,
+           const double *__restrict__ sub, double *__restrict__ r, double *__restrict__ rhat, double *__restrict__ p,
+           double *__restrict__ ub, double *__restrict__ phat, double *__restrict__ S, DotPart part) {
+  double acc = 0.0;
+  GRID_STRIDE(k, nb) {
+    const int32_t q = rows[k];
+    const double rk = sub ? src[q] - sub[k] : src[q];
+    r[k] = rk; rhat[k] = rk; p[k] = rk;
+    if (ub) ub[k] = 0.0;
+    if (q >= nu) phat[q] = rk;
+    acc += rk * rk;
+  }
+  block_atomic_sum(acc, slot_base(S, 0, R_RR), part.p0);
+}
+
+// recurrences (re)started from r: rho = (r, r) = R[R_RR]
+__global__ void k_red_rho(double *S, int restart) {
+  const double rr = S[R_OFF + R_RR];
+  S[S_RHO] = rr; S[S_RHO_NEXT] = rr; S[S_RR] = rr; S[S_RR0] = rr; S[S_RR0 + 1] = rr;
+  S[S_ALPHA] = 1.0; S[S_OMEGA] = 1.0;
+  if (restart) S[S_RESTARTS] += 1.0;
+}
+
+// u_C += r_C (B is the identity on C: a restart from the true residual r moves u there by r)
+__global__ void __launch_bounds__(256)
+k_red_add_c(int64_t n, const uint32_t *__restrict__ cmask, const double *__restrict__ r, double *__restrict__ u) {
+  GRID_STRIDE(i, n) if (cmask_bit(cmask, i)) u[i] += r[i];
+}
+
+// u[rows[k]] = u_B[k]
+__global__ void __launch_bounds__(256)
+k_red_put_u(int64_t nb, const int32_t *__restrict__ rows, const double *__restrict__ ub, double *__restrict__ u) {
+  GRID_STRIDE(k, nb) u[rows[k]] = ub[k];
+}
+
+// s = r - alpha v; (rhat, s), (s, s).  Block 0 clears the other slot set (read for the last time by the previous iteration)
+__global__ void __launch_bounds__(256)
+k_red_s(int64_t nb, int par, const int32_t *__restrict__ rows, int64_t nu, const double *__restrict__ r,
+        const double *__restrict__ v, const double *__restrict__ rhat, double *__restrict__ sv, double *__restrict__ shat,
+        double *__restrict__ S, DotPart part) {
+  const double rho = S[S_RHO_NEXT];
+  const double alpha = rho / dotv(S, par, I_RV);
+  double rs = 0.0, ss = 0.0;
+  GRID_STRIDE(k, nb) {
+    const double sk = r[k] - alpha * v[k];
+    sv[k] = sk;
+    const int32_t q = rows[k];
+    if (q >= nu) shat[q] = sk;
+    rs += rhat[k] * sk;
+    ss += sk * sk;
+  }
+  if (blockIdx.x == 0) {
+    double *nxt = slot_base(S, par ^ 1, 0);
+    for (int k = threadIdx.x; k < 8 * NSLOT * SLOT_STRIDE; k += blockDim.x) nxt[k] = 0.0;
+    if (threadIdx.x == 0) { S[S_ALPHA] = alpha; S[S_RHO] = rho; }
+  }
+  block_atomic_sum(rs, slot_base(S, par, I_RS), part.p0);
+  block_atomic_sum(ss, slot_base(S, par, I_SS), part.p1);
+}
+
+// omega = (t, s) / (t, t), rho_new = (rhat, s) - omega (rhat, t), (r, r) = (s, s) - 2 omega (t, s) + omega^2 (t, t), beta and
+// the restart rule as k_ident_xrp.  Per stored row:
+//   u_B += alpha p + omega s,  r = s - omega t,  p = r + beta (p - omega v)   (restart: p = rhat = r)
+// accumulating (r, r) for the host check
+__global__ void __launch_bounds__(256)
+k_red_xrp(int64_t nb, int par, const int32_t *__restrict__ rows, int64_t nu, const double *__restrict__ sv,
+          const double *__restrict__ t, const double *__restrict__ v, double *__restrict__ rhat, double *__restrict__ ub,
+          double *__restrict__ r, double *__restrict__ p, double *__restrict__ phat, double *__restrict__ S, DotPart part) {
+  const double alpha = S[S_ALPHA];
+  const double ts = dotv(S, par, I_TS_B), tt = dotv(S, par, I_TT_B);
+  const double omega = ts / tt;
+  const double rho_new = dotv(S, par, I_RS) - omega * dotv(S, par, I_RT_B);
+  const double rr = fmax(0.0, dotv(S, par, I_SS) - 2.0 * omega * ts + omega * omega * tt);
+  const double beta = (rho_new / S[S_RHO]) * (alpha / omega);
+  const bool restart = !(fabs(beta) <= 1.0e300) || !(fabs(rho_new) > 1.0e-14 * rr);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    S[S_OMEGA] = omega;
+    S[S_RHO_NEXT] = restart ? rr : rho_new;
+    S[S_RR] = rr;
+    if (restart) S[S_RESTARTS] += 1.0;
+    S[S_RR0 + (par ^ 1)] = restart ? rr : S[S_RR0 + par];
+  }
+  double arr = 0.0;
+  GRID_STRIDE(k, nb) {
+    const double sk = sv[k], po = p[k];
+    ub[k] += alpha * po + omega * sk;
+    const double rk = sk - omega * t[k];
+    r[k] = rk;
+    arr += rk * rk;
+    double pk;
+    if (restart) {
+      pk = rk;
+      rhat[k] = rk;
+    } else {
+      pk = rk + beta * (po - omega * v[k]);
+    }
+    p[k] = pk;
+    const int32_t q = rows[k];
+    if (q >= nu) phat[q] = pk;
+  }
+  block_atomic_sum(arr, slot_base(S, par, I_RR), part.p0);
+}
+
 struct KrVecs {
   double *r, *rhat, *p, *v, *sv, *t, *y, *b, *phat, *shat;
 };
@@ -1940,6 +2072,16 @@ static inline KrVecs kr_vecs(phx_system *s) {
   return V;
 }
 static inline double *kr_scal(phx_system *s) { return s->kr_scal ? s->kr_scal : s->scal; }
+
+// reduced loop: compact stored-row vectors (nslices * 16 entries each) and u in solver order (n)
+struct KrRed {
+  double *r, *rhat, *p, *v, *sv, *t, *ub, *u;
+};
+static inline KrRed kr_red_vecs(phx_system *s) {
+  double *w = s->kr_red;
+  const int64_t m = s->nslices * SELL_S;
+  return KrRed{w, w + m, w + 2 * m, w + 3 * m, w + 4 * m, w + 5 * m, w + 6 * m, w + 7 * m};
+}
 
 // Identity loop in force for this solve?  Native single-rank loop only (PHX_KR_IDENTITY=0 forces the standard one):
 // structured P1 system, unscaled u columns, the f64 lattice preconditioner of one rank, stencil rows present, and
@@ -1972,11 +2114,27 @@ static int kr_identity(phx_system *s, bool *on) {
   return PHX_OK;
 }
 
+// Reduced loop in force for this solve (the identity loop is; PHX_KR_REDUCED=0 keeps the full-length identity loop, read once
+// per process)?  Needs stored rows and an unscaled application (no dscale / iscale).  Workspace and preconditioner maps are
+// built on the first solve of the system.
+static int kr_reduced(phx_system *s, bool *on) {
+  *on = false;
+  static const int env = getenv("PHX_KR_REDUCED") ? atoi(getenv("PHX_KR_REDUCED")) : 1;
+  const phx_box_precond *bp = s->precond;
+  if (!env || s->n_sell_rows <= 0 || bp->dscale || bp->iscale || !bp->line_iv) return PHX_OK;
+  if (!s->kr_red) PHX_HIP(phx_malloc(&s->kr_red, sizeof(double) * (size_t)(7 * s->nslices * SELL_S + s->n)));
+  PHX_CHECK(box_red_maps(s));
+  *on = true;
+  return PHX_OK;
+}
+
 // SpMV of the identity loop: the SELL-16 blocks of the stored rows alone (the rows of the stencil blocks are left
 // unwritten).  dots 1: o0 += (y, d0);  dots 3: o0 += (y, d0), o1 += (y, y), o2 += (y, d1).  PHX_OPT_DETERMINISTIC:
-// the partial sums are ADDED to slot 0 (R_RV already holds the C-row share there).
-static int launch_spmv_stored(phx_system *s, const double *x, double *y, int dots, const double *d0, const double *d1,
-                              double *o0, double *o1, double *o2) {
+// the partial sums are ADDED to slot 0 (R_RV already holds the C-row share there).  compact (reduced loop): y, d0 and d1
+// are compact stored-row vectors (k_spmv_sell<DOTS, true>); dots 0: no dot product.
+template <bool CY>
+static int launch_spmv_stored_t(phx_system *s, const double *x, double *y, int dots, const double *d0, const double *d1,
+                                double *o0, double *o1, double *o2) {
   hipStream_t st = s->mesh->stream;
   const int64_t nb = (phx_div_up(s->nslices, 4) + 7) & ~(int64_t)7;   // a multiple of 8, as launch_spmv
   if (nb == 0) return PHX_OK;
@@ -1984,16 +2142,26 @@ static int launch_spmv_stored(phx_system *s, const double *x, double *y, int dot
   const int xg = xg_env >= 0 ? xg_env : s->mesh->spmv_xcd_group;
   const StencilArgs sa{0, nullptr, 0, nullptr, nullptr, 0, nullptr};
   DotPart dp{nullptr, nullptr};
-  PHX_CHECK(det_part(s, nb, &dp));
-  if (dots == 1)
-    k_spmv_sell<1><<<dim3((unsigned)nb), dim3(256), 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, s->sell_val, x, y, nullptr,
-                                                             d0, o0, nullptr, xg, s->sell_kind, s->sell_rows, nb, sa, nullptr, dp,
-                                                             nullptr, nullptr);
+  if (dots > 0) PHX_CHECK(det_part(s, nb, &dp));
+  if (dots == 0)
+    k_spmv_sell<0, CY><<<dim3((unsigned)nb), dim3(256), 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, s->sell_val, x, y, nullptr,
+                                                                 nullptr, nullptr, nullptr, xg, s->sell_kind, s->sell_rows, nb, sa, nullptr,
+                                                                 dp, nullptr, nullptr);
+  else if (dots == 1)
+    k_spmv_sell<1, CY><<<dim3((unsigned)nb), dim3(256), 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, s->sell_val, x, y, nullptr,
+                                                                 d0, o0, nullptr, xg, s->sell_kind, s->sell_rows, nb, sa, nullptr, dp,
+                                                                 nullptr, nullptr);
   else
-    k_spmv_sell<3><<<dim3((unsigned)nb), dim3(256), 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, s->sell_val, x, y, nullptr,
-                                                             d0, o0, o1, xg, s->sell_kind, s->sell_rows, nb, sa, nullptr, dp, d1, o2);
+    k_spmv_sell<3, CY><<<dim3((unsigned)nb), dim3(256), 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, s->sell_val, x, y, nullptr,
+                                                                 d0, o0, o1, xg, s->sell_kind, s->sell_rows, nb, sa, nullptr, dp, d1, o2);
   PHX_HIP(hipGetLastError());
+  if (dots == 0) return PHX_OK;
   return det_fold(s, o0, dots == 3 ? o1 : nullptr, dots == 3 ? o2 : nullptr, nullptr, 1);
+}
+static int launch_spmv_stored(phx_system *s, const double *x, double *y, int dots, const double *d0, const double *d1,
+                              double *o0, double *o1, double *o2, bool compact = false) {
+  return compact ? launch_spmv_stored_t<true>(s, x, y, dots, d0, d1, o0, o1, o2)
+                 : launch_spmv_stored_t<false>(s, x, y, dots, d0, d1, o0, o1, o2);
 }
 
 // Phases of kr_phase.  The numbers are ABI (phx_krylov_phase; dist_solver.py names them alike).
@@ -2024,6 +2192,14 @@ enum KrPhase {
   KR_ID_UPDATE_S = 53,     // s pass
   KR_ID_SPMV_S = 54,       // t = A shat on the stored rows
   KR_ID_UPDATE_XRP = 55,   // x / r / p pass (replaces 5 and 6)
+  KR_RED_PRECOND_P = 56,   // reduced loop (kr_reduced; native loop only): phat = M^-1 p_B at cols(B)
+  KR_RED_SPMV_P = 57,      // v_B = (A phat)_B
+  KR_RED_UPDATE_S = 58,    // s_B pass
+  KR_RED_PRECOND_S = 59,   // shat = M^-1 s_B at cols(B)
+  KR_RED_SPMV_S = 60,      // t_B = (A shat)_B
+  KR_RED_UPDATE_XRP = 61,  // u_B / r_B / p_B pass
+  KR_RED_FORM_X = 62,      // y = M^-1 u (u_C as held, u_B scattered)
+  KR_RED_RESTART = 63,     // after KR_TRUE_RESIDUAL: u_C += r_C, recurrences restarted from r_B
 };
 
 // mode 1 (phase API, multi-GPU): every dot product is folded into R right after its producer so
@@ -2061,9 +2237,11 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
       if (!s->pvec) PHX_HIP(phx_malloc(&s->pvec, sizeof(double) * (size_t)n * 2));
       PHX_HIP(hipMemsetAsync(s->pvec, 0, sizeof(double) * (size_t)n * 2, st));
     }
-    bool ident = false;
+    bool ident = false, red = false;
     if (mode == 0) PHX_CHECK(kr_identity(s, &ident));
+    if (ident) PHX_CHECK(kr_reduced(s, &red));
     s->kr_ident_used = ident;
+    s->kr_red_used = red;
   }
   const KrVecs V = kr_vecs(s);
   double *S = kr_scal(s);
@@ -2072,14 +2250,19 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
   const bool rest_out = s->precond_state == 1 && V.phat != V.p;
   const int32_t *rperm = s->structured ? nullptr : s->perm;
   const RestOut rop{rest_out ? V.phat : nullptr, rperm, s->nu}, ros{rest_out ? V.shat : nullptr, rperm, s->nu};
+  const KrRed R = s->kr_red_used ? kr_red_vecs(s) : KrRed{};
+  const int64_t nb = s->n_sell_rows;
   switch (phase) {
     case KR_BEGIN:
       PHX_HIP(hipMemsetAsync(S, 0, sizeof(double) * PHX_SCAL_DOUBLES, st));
       {
         DotPart dp{nullptr, nullptr};
         PHX_CHECK(det_part(s, vec_grid(n).x, &dp));
-        const uint32_t *cm = s->kr_ident_used ? s->kr_cmask : nullptr;
-        k_kr_begin<<<vec_grid(n), block, 0, st>>>(n, s->perm, s->rhs, s->own, V.b, V.r, V.rhat, V.p, V.y, S, rop, dp, cm);
+        const uint32_t *cm = s->kr_ident_used && !s->kr_red_used ? s->kr_cmask : nullptr;
+        if (s->kr_red_used)
+          k_red_begin<<<vec_grid(n), block, 0, st>>>(n, s->perm, s->rhs, s->kr_cmask, V.b, R.u, S, dp);
+        else
+          k_kr_begin<<<vec_grid(n), block, 0, st>>>(n, s->perm, s->rhs, s->own, V.b, V.r, V.rhat, V.p, V.y, S, rop, dp, cm);
         PHX_CHECK(det_fold(s, slot_base(S, 0, R_RHO), cm ? slot_base(S, 0, R_RV) : nullptr));
       }
       k_reduce_slots<<<1, 64, 0, st>>>(S, 0, R_RHO, 1, 1);
@@ -2087,6 +2270,18 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
       break;
     case KR_BEGIN2:
       k_kr_begin2<<<1, 1, 0, st>>>(S, mode);
+      if (s->kr_red_used) {
+        // x0 = M^-1 u0 (u0 = E_C b_C), r0_B = b_B - (A x0)_B; S_BB keeps (b, b) over all rows
+        PHX_CHECK(box_precond_apply(s, R.u, V.y));
+        if (n > s->nu) PHX_HIP(hipMemcpyAsync(V.y + s->nu, R.u + s->nu, sizeof(double) * (size_t)(n - s->nu), hipMemcpyDeviceToDevice, st));
+        PHX_CHECK(launch_spmv_stored(s, V.y, R.t, 0, nullptr, nullptr, nullptr, nullptr, nullptr, true));
+        DotPart dp{nullptr, nullptr};
+        PHX_CHECK(det_part(s, vec_grid(nb).x, &dp));
+        k_red_from<<<vec_grid(nb), block, 0, st>>>(nb, s->sell_rows, s->nu, V.b, R.t, R.r, R.rhat, R.p, R.ub, V.phat, S, dp);
+        PHX_CHECK(det_fold(s, slot_base(S, 0, R_RR), nullptr));
+        k_reduce_slots<<<1, 64, 0, st>>>(S, 0, R_RR, 1, 1);
+        k_red_rho<<<1, 1, 0, st>>>(S, 0);
+      }
       break;
     case KR_SPMV_P:
       PHX_CHECK(prof_begin(s));
@@ -2203,6 +2398,57 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
         PHX_CHECK(det_fold(s, slot_base(S, par, I_RR), slot_base(S, par ^ 1, I_RV), nullptr, nullptr, 1));
       }
       break;
+    // --- reduced loop (kr_reduced; native loop only)
+    case KR_RED_PRECOND_P:
+      PHX_CHECK(box_precond_apply_red(s, R.p, V.phat));
+      break;
+    case KR_RED_SPMV_P:
+      PHX_CHECK(prof_begin(s));
+      PHX_CHECK(launch_spmv_stored(s, V.phat, R.v, 1, R.rhat, nullptr, slot_base(S, par, I_RV), nullptr, nullptr, true));
+      PHX_CHECK(prof_end(s));
+      break;
+    case KR_RED_UPDATE_S:
+      {
+        DotPart dp{nullptr, nullptr};
+        PHX_CHECK(det_part(s, vec_grid(nb).x, &dp));
+        k_red_s<<<vec_grid(nb), block, 0, st>>>(nb, par, s->sell_rows, s->nu, R.r, R.v, R.rhat, R.sv, V.shat, S, dp);
+        PHX_CHECK(det_fold(s, slot_base(S, par, I_RS), slot_base(S, par, I_SS)));
+      }
+      break;
+    case KR_RED_PRECOND_S:
+      PHX_CHECK(box_precond_apply_red(s, R.sv, V.shat));
+      break;
+    case KR_RED_SPMV_S:
+      PHX_CHECK(prof_begin(s));
+      PHX_CHECK(launch_spmv_stored(s, V.shat, R.t, 3, R.sv, R.rhat, slot_base(S, par, I_TS_B), slot_base(S, par, I_TT_B),
+                                   slot_base(S, par, I_RT_B), true));
+      PHX_CHECK(prof_end(s));
+      break;
+    case KR_RED_UPDATE_XRP:
+      {
+        DotPart dp{nullptr, nullptr};
+        PHX_CHECK(det_part(s, vec_grid(nb).x, &dp));
+        k_red_xrp<<<vec_grid(nb), block, 0, st>>>(nb, par, s->sell_rows, s->nu, R.sv, R.t, R.v, R.rhat, R.ub, R.r, R.p, V.phat,
+                                                  S, dp);
+        PHX_CHECK(det_fold(s, slot_base(S, par, I_RR), nullptr));
+      }
+      break;
+    case KR_RED_FORM_X:
+      k_red_put_u<<<vec_grid(nb), block, 0, st>>>(nb, s->sell_rows, R.ub, R.u);
+      PHX_CHECK(box_precond_apply(s, R.u, V.y));
+      if (n > s->nu) PHX_HIP(hipMemcpyAsync(V.y + s->nu, R.u + s->nu, sizeof(double) * (size_t)(n - s->nu), hipMemcpyDeviceToDevice, st));
+      break;
+    case KR_RED_RESTART:
+      k_red_add_c<<<vec_grid(n), block, 0, st>>>(n, s->kr_cmask, V.r, R.u);
+      {
+        DotPart dp{nullptr, nullptr};
+        PHX_CHECK(det_part(s, vec_grid(nb).x, &dp));
+        k_red_from<<<vec_grid(nb), block, 0, st>>>(nb, s->sell_rows, s->nu, V.r, nullptr, R.r, R.rhat, R.p, nullptr, V.phat, S, dp);
+        PHX_CHECK(det_fold(s, slot_base(S, 0, R_RR), nullptr));
+      }
+      k_reduce_slots<<<1, 64, 0, st>>>(S, 0, R_RR, 1, 1);
+      k_red_rho<<<1, 1, 0, st>>>(S, 1);
+      break;
     case KR_EXACT_P:
       if (s->precond_state == 1 && s->precond->dist) PHX_CHECK(box_precond_apply(s, V.p, V.phat, 2));
       break;
@@ -2256,6 +2502,12 @@ extern "C" int phx_krylov_precond_active(const phx_system *s, int *active) {
 // 1 when the last phx_solve of `s` ran the identity loop (kr_identity), 0 for the standard loop
 extern "C" int phx_krylov_identity_loop(const phx_system *s, int *on) {
   *on = s->kr_ident_used ? 1 : 0;
+  return PHX_OK;
+}
+
+// 1 when the last phx_solve of `s` ran the identity loop on compact stored-row vectors (kr_reduced)
+extern "C" int phx_krylov_reduced_loop(const phx_system *s, int *on) {
+  *on = s->kr_red_used ? 1 : 0;
   return PHX_OK;
 }
 
@@ -2382,6 +2634,7 @@ static int kr_drive(phx_system *s, const KrDist *d, double rtol, int64_t max_ite
   double *S = kr_scal(s);
   const KrVecs V = kr_vecs(s);
   const bool ident = s->kr_ident_used;   // decided by phase 0 (kr_identity; never in mode 1)
+  const bool red = s->kr_red_used;       // kr_reduced (only with ident)
   const bool pc = d ? d->pc_all : s->precond_state == 1;
   const double bb = s->scal_h[S_BB];
   auto read_head = [&](const char *what) -> int {
@@ -2417,18 +2670,30 @@ static int kr_drive(phx_system *s, const KrDist *d, double rtol, int64_t max_ite
   double relres = bb == 0.0 ? 0.0 : 1.0, last_relres = 1.0;
   int rc = PHX_OK;
   int verifications = 0;
+  // reduced loop: r0_B = 0 (read with the head after phase 1) means that x0 solves the system: straight to the check
+  bool skip = red && bb != 0.0 && s->scal_h[S_RR] == 0.0;
+  if (skip) relres = 0.0;
   for (;;) {
-    while (bb != 0.0 && it < max_iter) {
+    while (bb != 0.0 && it < max_iter && !skip) {
       const int par = d ? 0 : (int)(it & 1);
-      PHX_CHECK(precond(KR_PRECOND_P, KR_EXACT_P, KR_CC_RESTRICT_P, KR_CC_ADD_P));
-      PHX_CHECK(spmv(ident ? KR_ID_SPMV_P : KR_SPMV_P, KR_SPMV_P_INNER, KR_SPMV_P_HALO, V.phat, par));
-      PHX_CHECK(allreduce(R_RV, R_RV + 1));
-      PHX_CHECK(kr_phase(s, ident ? KR_ID_UPDATE_S : KR_UPDATE_S, mode, par));
-      PHX_CHECK(precond(KR_PRECOND_S, KR_EXACT_S, KR_CC_RESTRICT_S, KR_CC_ADD_S));
-      PHX_CHECK(spmv(ident ? KR_ID_SPMV_S : KR_SPMV_S, KR_SPMV_S_INNER, KR_SPMV_S_HALO, V.shat, par));
-      PHX_CHECK(allreduce(R_TS, R_TT + 1));
-      PHX_CHECK(kr_phase(s, ident ? KR_ID_UPDATE_XRP : KR_UPDATE_XR, mode, par));
-      PHX_CHECK(allreduce(R_RHO, R_RR + 1));
+      if (red) {
+        PHX_CHECK(kr_phase(s, KR_RED_PRECOND_P, mode, par));
+        PHX_CHECK(kr_phase(s, KR_RED_SPMV_P, mode, par));
+        PHX_CHECK(kr_phase(s, KR_RED_UPDATE_S, mode, par));
+        PHX_CHECK(kr_phase(s, KR_RED_PRECOND_S, mode, par));
+        PHX_CHECK(kr_phase(s, KR_RED_SPMV_S, mode, par));
+        PHX_CHECK(kr_phase(s, KR_RED_UPDATE_XRP, mode, par));
+      } else {
+        PHX_CHECK(precond(KR_PRECOND_P, KR_EXACT_P, KR_CC_RESTRICT_P, KR_CC_ADD_P));
+        PHX_CHECK(spmv(ident ? KR_ID_SPMV_P : KR_SPMV_P, KR_SPMV_P_INNER, KR_SPMV_P_HALO, V.phat, par));
+        PHX_CHECK(allreduce(R_RV, R_RV + 1));
+        PHX_CHECK(kr_phase(s, ident ? KR_ID_UPDATE_S : KR_UPDATE_S, mode, par));
+        PHX_CHECK(precond(KR_PRECOND_S, KR_EXACT_S, KR_CC_RESTRICT_S, KR_CC_ADD_S));
+        PHX_CHECK(spmv(ident ? KR_ID_SPMV_S : KR_SPMV_S, KR_SPMV_S_INNER, KR_SPMV_S_HALO, V.shat, par));
+        PHX_CHECK(allreduce(R_TS, R_TT + 1));
+        PHX_CHECK(kr_phase(s, ident ? KR_ID_UPDATE_XRP : KR_UPDATE_XR, mode, par));
+        PHX_CHECK(allreduce(R_RHO, R_RR + 1));
+      }
       spmvs += 2;
       ++it;
       if (it >= next_check || it == max_iter) {
@@ -2458,6 +2723,7 @@ static int kr_drive(phx_system *s, const KrDist *d, double rtol, int64_t max_ite
       }
       if (!ident) PHX_CHECK(kr_phase(s, KR_UPDATE_P, mode, par));
     }
+    if (red && rc == PHX_OK && bb != 0.0) PHX_CHECK(kr_phase(s, KR_RED_FORM_X, mode, 0));   // y = M^-1 u
     if (rc != PHX_OK || bb == 0.0 || !(relres <= rtol)) break;
     // verify (mode 1: after one more halo exchange, with one more all-reduce)
     if (d) PHX_CHECK(halo_exchange(s, d->c, *d->H, V.y));
@@ -2471,7 +2737,8 @@ static int kr_drive(phx_system *s, const KrDist *d, double rtol, int64_t max_ite
     if (!(rr_true == rr_true)) { phx_set_error("non-finite true residual"); rc = PHX_ERR_BREAKDOWN; break; }
     relres = sqrt(rr_true / bb);
     if (relres <= rtol || ++verifications > 8 || it >= max_iter) break;
-    PHX_CHECK(kr_phase(s, KR_RESTART, mode, d ? 0 : (int)(it & 1)));
+    PHX_CHECK(kr_phase(s, red ? KR_RED_RESTART : KR_RESTART, mode, d ? 0 : (int)(it & 1)));
+    skip = false;
     last_relres = relres;
     last_check = it;
     next_check = it + 2;   // (every slot is clear now: the parity the loop derives from `it` needs no care)

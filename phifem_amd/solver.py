@@ -243,6 +243,8 @@ class PhiFEMSolver:
         ident = C.c_int(0)
         L.check(L.lib.phx_krylov_identity_loop(self._sys, C.byref(ident)))
         self.stats["identity_loop"] = bool(ident.value)
+        L.check(L.lib.phx_krylov_reduced_loop(self._sys, C.byref(ident)))
+        self.stats["reduced_loop"] = bool(ident.value)
         self.stats.update(self.precond_info())
         if getattr(self, "_p2_coarse", 0) != 0:
             self.stats.update(self.coarse_info())
