@@ -4,11 +4,13 @@ path: the counterpart of the reference's demo/interface-elasticity/main.py with 
 (E_in = 1, E_out = 1e-3, nu = 0.3, phi = 1 - r^2, all degrees 1, box [-1.5,1.5]^2, h-refinement
 loop with relative error slopes).
 
-    python main.py [--iterations 4] [--mesh-size 0.2]
+    python main.py [--iterations 4] [--mesh-size 0.2] [--cell-type {triangle,quadrilateral}]
 
 The reference refines with dolfinx.mesh.refine; the structured background mesh is simply
 regenerated with twice the cells.  Errors as in the reference: u_h and the exact solution in the
-degree-3 Lagrange space, cell-wise H10 / L2 integrals (`phifem_amd.postprocess.cell_errors`).
+degree-3 Lagrange space (Q3 on quadrilaterals), cell-wise H10 / L2 integrals
+(`phifem_amd.postprocess.cell_errors`).  --cell-type is the reference's `cell_type` parameter
+(main.py:93,99-108): triangles (default) or quadrilaterals, with Q1 spaces on the latter.
 """
 import argparse
 import os
@@ -61,12 +63,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iterations", type=int, default=4)
     ap.add_argument("--mesh-size", type=float, default=0.2)
+    ap.add_argument("--cell-type", choices=["triangle", "quadrilateral"], default="triangle")
     args = ap.parse_args()
     f = source()
     n = int(round(3.0 / args.mesh_size))
     dofs, h10s, l2s = [], [], []
     for it in range(args.iterations):
-        mesh = P.create_rectangle([[-1.5, -1.5], [1.5, 1.5]], [n, n])
+        mesh = P.create_rectangle([[-1.5, -1.5], [1.5, 1.5]], [n, n], cell_type=args.cell_type)
         x = mesh.x
         phi = 1.0 - (x ** 2).sum(axis=1)
         with warnings.catch_warnings():

@@ -23,6 +23,7 @@ struct ElArgs {
   int32_t nv;
   double *rhs;
   Slots slots;
+  int *bad;                // quadrilaterals: set when a cell is not an axis-parallel rectangle
 };
 
 template <int D>
@@ -68,14 +69,14 @@ __device__ __forceinline__ void el_rhs(const ElArgs &A, int32_t row_full, double
   slot_rhs_add(A.slots, A.rhs, A.dofmap[row_full], v);
 }
 
-template <int D>
+template <int D, int NV = D + 1>   // NV: vertices per cell (4 on quadrilaterals)
 __global__ void k_el_mark_active(int64_t nc, ElArgs A, uint8_t *__restrict__ flags) {
   using B = ElB<D>;
   const int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (c >= nc) return;
   const int t = A.ctags[c] & PHX_TAG_MASK;
-  for (int i = 0; i < B::N; ++i) {
-    const int64_t v = A.cells[c * B::N + i];
+  for (int i = 0; i < NV; ++i) {
+    const int64_t v = A.cells[c * NV + i];
     for (int blk = 0; blk < B::C; ++blk) {
       int kind, a, b;
       B::decode(blk, kind, a, b);
@@ -466,10 +467,15 @@ struct SelFacetTagInterior {
   __host__ __device__ bool operator()(const int32_t &f) const { return ft[f] == tag && f2c[2 * (int64_t)f + 1] >= 0; }
 };
 
+// the Q1 element kernels on rectangles (phx_assemble_el_quad.inc.hip)
+static int el_quad_launch(phx_mesh *m, const ElArgs &A, int64_t n_cut, const int32_t *l_cut, int64_t n_f3,
+                          const int32_t *l_f3, int64_t n_f4, const int32_t *l_f4);
+
 static int assemble_el_with_capacity(phx_mesh *m, const double *params, const double *dphi,
                                      const double *df, const double *dud, const int32_t *dbcv,
                                      int64_t nbc, int W, phx_system **out) {
   const int D = m->gdim;
+  const bool quad = m->cell_type == PHX_QUADRILATERAL;
   const int C = 2 * D + 2 * D * D + D;
   const int64_t nent = (int64_t)C * m->nv;
   PHX_REQUIRE(nent < INT32_MAX, PHX_ERR_VALUE, "too many DoFs for 32-bit column keys");
@@ -499,7 +505,8 @@ static int assemble_el_with_capacity(phx_mesh *m, const double *params, const do
   PHX_HIP(hipMemsetAsync(bc, 0, (size_t)m->nv, m->stream));
   A.bc = bc;
   const dim3 gcells((unsigned)phx_div_up(m->nc, 256));
-  if (D == 2) k_el_mark_active<2><<<gcells, block, 0, m->stream>>>(m->nc, A, flags);
+  if (quad) k_el_mark_active<2, 4><<<gcells, block, 0, m->stream>>>(m->nc, A, flags);
+  else if (D == 2) k_el_mark_active<2><<<gcells, block, 0, m->stream>>>(m->nc, A, flags);
   else k_el_mark_active<3><<<gcells, block, 0, m->stream>>>(m->nc, A, flags);
   if (nbc > 0) k_el_mark_bc<<<dim3((unsigned)phx_div_up(nbc, 256)), block, 0, m->stream>>>(nbc, D, m->nv, dbcv, flags, bc);
   int32_t n = 0;
@@ -527,7 +534,7 @@ static int assemble_el_with_capacity(phx_mesh *m, const double *params, const do
     PHX_HIP(hipMemsetAsync(cutv, 0, (size_t)m->nv, m->stream));
     if (n_cut > 0) {
       const dim3 g((unsigned)phx_div_up(n_cut, 256));
-      if (D == 2) k_mark_cells<3><<<g, block, 0, m->stream>>>(n_cut, l_cut, m->cells, cutv);
+      if (D == 2 && !quad) k_mark_cells<3><<<g, block, 0, m->stream>>>(n_cut, l_cut, m->cells, cutv);
       else k_mark_cells<4><<<g, block, 0, m->stream>>>(n_cut, l_cut, m->cells, cutv);
     }
     int wbig = 0;
@@ -573,11 +580,17 @@ static int assemble_el_with_capacity(phx_mesh *m, const double *params, const do
           k_mark_entity_cells<NN><<<dim3((unsigned)phx_div_up(m->ent_count[sd], 256)), gb, 0, m->stream>>>(       \
               m->ent_count[sd], m->ent_buf[sd], m->cells, touched);                                               \
     } while (0)
-    if (D == 2) PHX_MARK(3); else PHX_MARK(4);
+    if (D == 2 && !quad) PHX_MARK(3); else PHX_MARK(4);
 #undef PHX_MARK
   }
   if (!m->is_box) PHX_REQUIRE_GRID(m->nc * 256, "elasticity bulk assembly");
   PHX_REQUIRE_GRID(n_cut * 256, "elasticity cut-cell assembly");
+  int *bad = nullptr;
+  if (quad) {
+    PHX_HIP(phx_malloc(&bad, sizeof(int)));
+    PHX_HIP(hipMemsetAsync(bad, 0, sizeof(int), m->stream));
+    A.bad = bad;
+  }
   // PHX_OPT_DETERMINISTIC: every kernel that adds into the slots or the right-hand side runs twice (Slots)
   bool det = false;
   PHX_CHECK(det_alloc(m, sl, total_slots, n, &det));
@@ -591,7 +604,9 @@ static int assemble_el_with_capacity(phx_mesh *m, const double *params, const do
       if (D == 2) k_el_bulk_box<2><<<g, block, 0, m->stream>>>(nthreads, bd, touched, A);
       else k_el_bulk_box<3><<<g, block, 0, m->stream>>>(nthreads, bd, touched, A);
     }
-    if (D == 2) {
+    if (quad) {
+      PHX_CHECK(el_quad_launch(m, A, n_cut, l_cut, n_f3, l_f3, n_f4, l_f4));
+    } else if (D == 2) {
       if (!m->is_box) k_el_bulk<2><<<dim3((unsigned)m->nc), block, 0, m->stream>>>(m->nc, A);
       if (n_cut) k_el_cut<2><<<dim3((unsigned)n_cut), block, 0, m->stream>>>(n_cut, l_cut, A);
       for (int sd = 0; sd < 2; ++sd)
@@ -614,6 +629,17 @@ static int assemble_el_with_capacity(phx_mesh *m, const double *params, const do
   PHX_HIP(hipStreamSynchronize(m->stream));
   PHX_HIP(phx_free(l_cut)); PHX_HIP(phx_free(l_f3)); PHX_HIP(phx_free(l_f4)); PHX_HIP(phx_free(bc));
   PHX_HIP(phx_free(touched));
+  if (quad) {
+    int hbad = 0;
+    PHX_HIP(hipMemcpy(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost));
+    PHX_HIP(phx_free(bad));
+    if (hbad) {
+      PHX_CHECK(free_slots(sl));
+      phx_system_destroy(s);
+      phx_set_error("quadrilateral elasticity assembly covers axis-parallel rectangles only");
+      return PHX_ERR_NOT_IMPLEMENTED;
+    }
+  }
   const int rc = phx_finish_system(s, sl, (int32_t)nent);
   if (rc != PHX_OK) { phx_system_destroy(s); return rc; }
   *out = s;
@@ -625,8 +651,9 @@ extern "C" int phx_assemble_elasticity_if(phx_mesh *m, const double *params, con
                                           const int32_t *bc_vertices, int64_t nbc, int loc,
                                           phx_system **out) {
   PHX_HIP(hipSetDevice(m->device));
-  PHX_REQUIRE(m->cell_type == PHX_TRIANGLE || m->cell_type == PHX_TETRAHEDRON,
-              PHX_ERR_NOT_IMPLEMENTED, "assembly supports simplices (triangle, tetrahedron) only");
+  PHX_REQUIRE(m->cell_type == PHX_TRIANGLE || m->cell_type == PHX_TETRAHEDRON ||
+              (m->cell_type == PHX_QUADRILATERAL && m->gdim == 2),
+              PHX_ERR_NOT_IMPLEMENTED, "assembly supports triangles, tetrahedra and quadrilaterals only");
   PHX_REQUIRE(m->have_cell_tags && m->have_facet_tags, PHX_ERR_VALUE,
               "cell and facet tags must be computed before assembly");
   PHX_REQUIRE(!m->is_submesh, PHX_ERR_NOT_IMPLEMENTED, "interface elasticity runs in box mode");

@@ -5,6 +5,9 @@
 // give one number per cell; the norms of I(u_ex) (:339-345, :363-367) normalise the global errors.
 // The reference space is basix's default Lagrange variant (GLL-warped [3P]): on an edge the two interior
 // nodes of degree 3 sit at (1 -+ 1/sqrt 5)/2, the face node at the centroid.  I(u_h) = u_h (P1, P2 in P3).
+// Quadrilaterals (axis-parallel rectangles, u_h of degree 1): Q3 on the tensor product of the 1-D GLL-warped nodes
+// t = 0, (1 - 1/sqrt 5)/2, (1 + 1/sqrt 5)/2, 1 (local node iy * 4 + ix at (t[ix], t[iy])), I(u_h) = u_h (Q1 in Q3),
+// and a 4 x 4 Gauss rule, exact for the integrands of degree <= 6 per variable.
 
 #define PHX_ERR_MAXNB 20  // P3 on a tetrahedron
 
@@ -189,6 +192,127 @@ __global__ void __launch_bounds__(256) k_sum_partials(int64_t nblocks, const dou
   }
 }
 
+// --- quadrilaterals ----------------------------------------------------------------------------------------------
+struct ErrTabQ {
+  double t[4];        // 1-D nodes
+  double w[4];        // 1-D Gauss weights on [0, 1]
+  double L[4][4];     // L[q][k]: 1-D cubic Lagrange basis k at Gauss point q
+  double dL[4][4];    // its derivative
+};
+
+__global__ void __launch_bounds__(ERR_THREADS)
+k_cell_errors_quad(int64_t ncells, const int32_t *__restrict__ list, const int32_t *__restrict__ cells,
+                   const double *__restrict__ x, int ncomp, int64_t ndh, const double *__restrict__ uh,
+                   const double *__restrict__ uref, ErrTabQ T, double *__restrict__ l2, double *__restrict__ h10,
+                   double *__restrict__ partial, int *__restrict__ bad) {
+  constexpr int NB = 16;
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  double s[4] = {0.0, 0.0, 0.0, 0.0};   // l2, h10, |I u_ex|^2, |grad I u_ex|^2 of this cell
+  if (i < ncells) {
+    const int64_t c = list ? list[i] : i;
+    int32_t v[4];
+    double X[4][2];
+    for (int k = 0; k < 4; ++k) {
+      v[k] = cells[c * 4 + k];
+      X[k][0] = x[2 * (int64_t)v[k]];
+      X[k][1] = x[2 * (int64_t)v[k] + 1];
+    }
+    const double hx = X[1][0] - X[0][0], hy = X[2][1] - X[0][1];
+    const double tx = 1e-12 * fabs(hx), ty = 1e-12 * fabs(hy);
+    if (!(hx > 0.0 && hy > 0.0 && fabs(X[1][1] - X[0][1]) <= tx && fabs(X[2][0] - X[0][0]) <= ty &&
+          fabs(X[3][0] - X[1][0]) <= tx && fabs(X[3][1] - X[2][1]) <= ty))
+      *bad = 1;
+    for (int cp = 0; cp < ncomp; ++cp) {
+      double e[NB], r[NB], un[4];
+      for (int k = 0; k < 4; ++k) un[k] = uh[(int64_t)cp * ndh + v[k]];
+      for (int j = 0; j < NB; ++j) {
+        const double a = T.t[j & 3], b = T.t[j >> 2];
+        const double uj = (1.0 - a) * (1.0 - b) * un[0] + a * (1.0 - b) * un[1] + (1.0 - a) * b * un[2] + a * b * un[3];
+        r[j] = uref[((int64_t)i * NB + j) * ncomp + cp];
+        e[j] = r[j] - uj;
+      }
+      for (int qy = 0; qy < 4; ++qy)
+        for (int qx = 0; qx < 4; ++qx) {
+          double se = 0.0, sr = 0.0, ex = 0.0, ey = 0.0, rx = 0.0, ry = 0.0;
+          for (int j = 0; j < NB; ++j) {
+            const int jx = j & 3, jy = j >> 2;
+            const double N = T.L[qx][jx] * T.L[qy][jy];
+            const double Nx = T.dL[qx][jx] * T.L[qy][jy] / hx, Ny = T.L[qx][jx] * T.dL[qy][jy] / hy;
+            se += e[j] * N; sr += r[j] * N;
+            ex += e[j] * Nx; ey += e[j] * Ny;
+            rx += r[j] * Nx; ry += r[j] * Ny;
+          }
+          const double w = T.w[qx] * T.w[qy] * hx * hy;
+          s[0] += w * se * se; s[1] += w * (ex * ex + ey * ey); s[2] += w * sr * sr; s[3] += w * (rx * rx + ry * ry);
+        }
+    }
+    l2[i] = s[0];
+    h10[i] = s[1];
+  }
+  // fixed-order block sums, as in k_cell_errors
+  __shared__ double sh[ERR_THREADS / 64][4];
+  for (int k = 0; k < 4; ++k) {
+    double t = s[k];
+    for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][k] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    double t = 0.0;
+    for (int wv = 0; wv < ERR_THREADS / 64; ++wv) t += sh[wv][threadIdx.x];
+    partial[(int64_t)blockIdx.x * 4 + threadIdx.x] = t;
+  }
+}
+
+static int cell_errors_quad(phx_mesh *m, int ncomp, const double *duh, const double *duref, int64_t ncells,
+                            const int32_t *dlist, double *dl2, double *dh10, double *norms_host) {
+  ErrTabQ T;
+  const double g1 = 0.5 * (1.0 - 1.0 / sqrt(5.0)), g2 = 0.5 * (1.0 + 1.0 / sqrt(5.0));
+  T.t[0] = 0.0; T.t[1] = g1; T.t[2] = g2; T.t[3] = 1.0;
+  // 4-point Gauss-Legendre on [0, 1]
+  const double za = sqrt(3.0 / 7.0 - 2.0 / 7.0 * sqrt(6.0 / 5.0)), zb = sqrt(3.0 / 7.0 + 2.0 / 7.0 * sqrt(6.0 / 5.0));
+  const double wa = (18.0 + sqrt(30.0)) / 36.0, wb = (18.0 - sqrt(30.0)) / 36.0;
+  const double gq[4] = {0.5 * (1.0 - zb), 0.5 * (1.0 - za), 0.5 * (1.0 + za), 0.5 * (1.0 + zb)};
+  const double gw[4] = {0.5 * wb, 0.5 * wa, 0.5 * wa, 0.5 * wb};
+  for (int q = 0; q < 4; ++q) {
+    T.w[q] = gw[q];
+    for (int k = 0; k < 4; ++k) {
+      double v = 1.0, dv = 0.0;
+      for (int l = 0; l < 4; ++l) {
+        if (l == k) continue;
+        const double den = T.t[k] - T.t[l];
+        double p = 1.0 / den;   // derivative of the product: sum over the dropped factor
+        for (int mm = 0; mm < 4; ++mm)
+          if (mm != k && mm != l) p *= (gq[q] - T.t[mm]) / (T.t[k] - T.t[mm]);
+        dv += p;
+        v *= (gq[q] - T.t[l]) / den;
+      }
+      T.L[q][k] = v;
+      T.dL[q][k] = dv;
+    }
+  }
+  hipStream_t st = m->stream;
+  double *partial = nullptr, *dsum = nullptr;
+  int *bad = nullptr;
+  const int64_t nblocks = phx_div_up(ncells, ERR_THREADS);
+  PHX_HIP(phx_malloc(&partial, sizeof(double) * (size_t)nblocks * 4));
+  PHX_HIP(phx_malloc(&dsum, sizeof(double) * 4));
+  PHX_HIP(phx_malloc(&bad, sizeof(int)));
+  PHX_HIP(hipMemsetAsync(bad, 0, sizeof(int), st));
+  PHX_REQUIRE_GRID(nblocks * ERR_THREADS, "cell errors");
+  k_cell_errors_quad<<<dim3((unsigned)nblocks), dim3(ERR_THREADS), 0, st>>>(
+      ncells, dlist, m->cells, m->x, ncomp, m->nv, duh, duref, T, dl2, dh10, partial, bad);
+  k_sum_partials<<<dim3(1), dim3(256), 0, st>>>(nblocks, partial, dsum);
+  PHX_HIP(hipGetLastError());
+  int hbad = 0;
+  PHX_HIP(hipMemcpyAsync(norms_host, dsum, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
+  PHX_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
+  PHX_HIP(hipStreamSynchronize(st));
+  PHX_HIP(phx_free(partial)); PHX_HIP(phx_free(dsum)); PHX_HIP(phx_free(bad));
+  PHX_REQUIRE(!hbad, PHX_ERR_NOT_IMPLEMENTED, "error evaluation on quadrilaterals covers axis-parallel rectangles only");
+  return PHX_OK;
+}
+
 template <int D>
 static int cell_errors_impl(phx_mesh *m, int ncomp, int degh, const double *duh, const double *duref,
                             int64_t ncells, const int32_t *dlist, double *dl2, double *dh10, double *norms_host) {
@@ -257,8 +381,10 @@ extern "C" int phx_cell_errors(phx_mesh *m, int ncomp, int degree_h, const doubl
                                int64_t ncells, const int32_t *cell_list, int loc, double *l2_local,
                                double *h10_local, double *norms) {
   PHX_HIP(hipSetDevice(m->device));
-  PHX_REQUIRE(m->cell_type == PHX_TRIANGLE || m->cell_type == PHX_TETRAHEDRON, PHX_ERR_NOT_IMPLEMENTED,
-              "error evaluation supports simplices (triangle, tetrahedron) only");
+  const bool quad = m->cell_type == PHX_QUADRILATERAL;
+  PHX_REQUIRE(m->cell_type == PHX_TRIANGLE || m->cell_type == PHX_TETRAHEDRON || (quad && m->gdim == 2),
+              PHX_ERR_NOT_IMPLEMENTED, "error evaluation supports triangles, tetrahedra and quadrilaterals only");
+  PHX_REQUIRE(!quad || degree_h == 1, PHX_ERR_NOT_IMPLEMENTED, "error evaluation on quadrilaterals takes degree_h = 1");
   PHX_REQUIRE(ncomp >= 1 && ncomp <= 3, PHX_ERR_VALUE, "ncomp must be 1, 2 or 3");
   PHX_REQUIRE(degree_h == 1 || degree_h == 2, PHX_ERR_VALUE, "degree_h must be 1 or 2");
   PHX_REQUIRE(ncells >= 0 && (cell_list != nullptr || ncells == m->nc), PHX_ERR_VALUE,
@@ -266,7 +392,7 @@ extern "C" int phx_cell_errors(phx_mesh *m, int ncomp, int degree_h, const doubl
   PHX_REQUIRE(u_h && u_ref && l2_local && h10_local && norms, PHX_ERR_VALUE, "NULL array");
   if (degree_h == 2) PHX_CHECK(phx_mesh_build_edges(m));
   if (ncells == 0) { for (int k = 0; k < 4; ++k) norms[k] = 0.0; return PHX_OK; }
-  const int D = m->gdim, NB = D == 3 ? 20 : 10;
+  const int D = m->gdim, NB = quad ? 16 : (D == 3 ? 20 : 10);
   const int64_t ndh = degree_h == 1 ? m->nv : m->nv + m->ne;
   const double *duh, *duref;
   double *o1, *o2, *dl2 = l2_local, *dh10 = h10_local;
@@ -284,8 +410,9 @@ extern "C" int phx_cell_errors(phx_mesh *m, int ncomp, int degree_h, const doubl
     }
   }
   const int32_t *lst = loc == PHX_DEVICE ? cell_list : dlist;
-  int rc = D == 2 ? cell_errors_impl<2>(m, ncomp, degree_h, duh, duref, ncells, lst, dl2, dh10, norms)
-                  : cell_errors_impl<3>(m, ncomp, degree_h, duh, duref, ncells, lst, dl2, dh10, norms);
+  int rc = quad ? cell_errors_quad(m, ncomp, duh, duref, ncells, lst, dl2, dh10, norms)
+           : D == 2 ? cell_errors_impl<2>(m, ncomp, degree_h, duh, duref, ncells, lst, dl2, dh10, norms)
+                    : cell_errors_impl<3>(m, ncomp, degree_h, duh, duref, ncells, lst, dl2, dh10, norms);
   if (rc == PHX_OK && loc != PHX_DEVICE) {
     PHX_HIP(hipMemcpy(l2_local, dl2, sizeof(double) * (size_t)ncells, hipMemcpyDeviceToHost));
     PHX_HIP(hipMemcpy(h10_local, dh10, sizeof(double) * (size_t)ncells, hipMemcpyDeviceToHost));

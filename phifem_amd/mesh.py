@@ -269,6 +269,19 @@ def create_box(lo, hi, n, device=0, offset=None, n_global=None):
     return Mesh(h, device=device)
 
 
-def create_rectangle(bbox, n, device=0):
-    """dolfinx.mesh.create_rectangle(comm, [[x0,y0],[x1,y1]], [nx,ny]) with diagonal 'right'."""
-    return create_box(bbox[0], bbox[1], n, device=device)
+def create_rectangle(bbox, n, device=0, cell_type="triangle"):
+    """dolfinx.mesh.create_rectangle(comm, [[x0,y0],[x1,y1]], [nx,ny], cell_type): triangles with diagonal
+    'right' (the generated box), or quadrilaterals in dolfinx's tensor-product vertex and cell order
+    (vertex j (nx + 1) + i at (x_i, y_j); cell vertices v0 (0,0), v1 (1,0), v2 (0,1), v3 (1,1))."""
+    if cell_type == "triangle":
+        return create_box(bbox[0], bbox[1], n, device=device)
+    if cell_type != "quadrilateral":
+        raise ValueError("cell_type can only be 'triangle' or 'quadrilateral'")
+    (x0, y0), (x1, y1) = bbox
+    nx, ny = int(n[0]), int(n[1])
+    X, Y = np.meshgrid(np.linspace(x0, x1, nx + 1), np.linspace(y0, y1, ny + 1), indexing="xy")
+    x = np.stack([X.reshape(-1), Y.reshape(-1)], axis=1)
+    i, j = np.meshgrid(np.arange(nx), np.arange(ny), indexing="xy")
+    v0 = (j * (nx + 1) + i).reshape(-1)
+    cells = np.stack([v0, v0 + 1, v0 + nx + 1, v0 + nx + 2], axis=1).astype(np.int32)
+    return Mesh.from_arrays("quadrilateral", x, cells, device=device)

@@ -23,20 +23,33 @@ def reference_nodes(gdim, degree=3):
     return out
 
 
+def quad_reference_nodes():
+    """Reference coordinates (16, 2) of the Q3 nodes of a quadrilateral in the order of `phx_cell_errors`:
+    node iy * 4 + ix at (t[ix], t[iy]), t = 0, (1 - 1/sqrt 5)/2, (1 + 1/sqrt 5)/2, 1 (basix's GLL-warped nodes)."""
+    t = np.array([0.0, 0.5 * (1.0 - 5.0 ** -0.5), 0.5 * (1.0 + 5.0 ** -0.5), 1.0])
+    return np.stack([np.tile(t, 4), np.repeat(t, 4)], axis=1)
+
+
 def cell_errors(mesh, u_h, exact_solution, degree=1, cells=None):
     """u_h: nodal values (nd,) or (nd, ncomp) of Lagrange degree `degree` (vertices, then edges at
-    degree 2); exact_solution: callable on points x of shape (gdim, npts), as the reference's
-    `exact_solution(x)`, returning (npts,) or (ncomp, npts); cells: cell indices (default: all).
+    degree 2; quadrilaterals: degree 1 on axis-parallel rectangles, reference space Q3); exact_solution:
+    callable on points x of shape (gdim, npts), as the reference's `exact_solution(x)`, returning
+    (npts,) or (ncomp, npts); cells: cell indices (default: all).
 
     Returns a dict: `l2_local`, `h10_local` (one value per listed cell, main.py:356,377),
     `l2_relative`, `h10_relative` (main.py:360,381), and the four integrals."""
     gdim = mesh.gdim
-    lam = reference_nodes(gdim)
-    nb = lam.shape[0]
     cl = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32)
     if cl is not None and cl.size and (cl.min() < 0 or cl.max() >= mesh.nc):
         raise ValueError("cell index out of range")
     cv = mesh.cells if cl is None else mesh.cells[cl]
+    if mesh.cell_type == "quadrilateral":
+        # Q3 nodes through the bilinear map of the cell (tensor-product vertex order)
+        xi, eta = quad_reference_nodes().T
+        lam = np.stack([(1 - xi) * (1 - eta), xi * (1 - eta), (1 - xi) * eta, xi * eta], axis=1)
+    else:
+        lam = reference_nodes(gdim)
+    nb = lam.shape[0]
     pts = np.einsum("jm,cmd->cjd", lam, mesh.x[cv]).reshape(-1, gdim)
     ue = np.asarray(exact_solution(pts.T), dtype=np.float64)
     ue = ue.reshape(1, -1) if ue.ndim == 1 else ue

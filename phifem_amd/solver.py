@@ -396,16 +396,21 @@ class InterfaceElasticitySolver(PhiFEMSolver):
     (u_in, u_out, y_in, y_out, p), all first-order Lagrange: the assemble -> solve sequence of
     demo/interface-elasticity/main.py:145-289 over the C ABI (`phx_assemble_elasticity_if`).
 
+    Cells: triangles, tetrahedra, or quadrilaterals that are axis-parallel rectangles in
+    tensor-product vertex order (Q1 spaces, main.py:99-108; `create_rectangle(...,
+    cell_type="quadrilateral")`); other quadrilaterals raise NotImplementedError at assembly.
     The mesh must be tagged in box mode (main.py:115-117).  Solution layout: component-major
     blocks of nv entries, see `blocks()`."""
 
     def __init__(self, mesh, E_in=1.0, nu_in=0.3, E_out=1.0e-3, nu_out=0.3,
                  penalization_coefficient=1.0, stabilization_coefficient=1.0, deterministic=False, coarse=-1):
         """coarse (PHX_OPT_EL_COARSE): spacing H / h of the coarse-space correction of the solve on generated boxes;
-        -1 automatic (on from 80 cubes per axis), 0 off."""
+        -1 automatic (on from 80 cubes per axis), 0 off.  Quadrilateral meshes have no coarse space."""
         # material parameters demo/interface-elasticity/data.py:14-22, coefficients param1.yaml:16-17
         super().__init__(mesh, deterministic=deterministic)
         self.coarse = int(coarse)
+        if self.coarse > 0 and mesh.cell_type == "quadrilateral":
+            raise NotImplementedError("the coarse-space correction is built on generated simplicial boxes only")
         self.params = np.array([E_in, nu_in, E_out, nu_out, penalization_coefficient,
                                 stabilization_coefficient], dtype=np.float64)
 
