@@ -343,6 +343,10 @@ int phx_system_info(const phx_system *s, int64_t *info);
  * dof[n_active].  Any pointer may be NULL. */
 int phx_system_export(phx_system *s, int64_t *rowptr, int32_t *col, double *val, double *rhs,
                       int64_t *dof);
+/* SELL-16 copy of the stored rows of a structured P1 system (Kuhn box), as the SpMV reads it; host buffers:
+ * slice_ptr[n_slices+1], col[sell_padded_nnz] (solver positions), val[sell_padded_nnz] (entries of A),
+ * rows[16*n_slices] (solver position of each slice row, -1: padding).  Any pointer may be NULL. */
+int phx_system_export_sell(phx_system *s, int64_t *slice_ptr, int32_t *col, double *val, int32_t *rows);
 
 /* ------------------------------------------------------------------ solve ------------ */
 enum phx_method { PHX_BICGSTAB_JACOBI = 0 };

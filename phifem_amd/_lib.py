@@ -109,6 +109,7 @@ SIGNATURES = {
     "phx_system_destroy": ([_vp], _i),
     "phx_system_info": ([_vp, _pi64], _i),
     "phx_system_export": ([_vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "phx_system_export_sell": ([_vp, _vp, _vp, _vp, _vp], _i),
     "phx_solve": ([_vp, _i, _d, _i64, _vp, _i, _pd], _i),
     "phx_krylov_identity_loop": ([_vp, C.POINTER(C.c_int)], _i),
     "phx_krylov_reduced_loop": ([_vp, C.POINTER(C.c_int)], _i),

@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <mutex>
 #include <vector>
 
 #include "phx_common.h"
@@ -110,7 +111,57 @@ struct Slots {
   int32_t *remax = nullptr;  // [rows] the same for the right-hand side
   double *rlo = nullptr;     // [rows]
   int pass = 0;
+  // box slots (structured P1 systems on a Kuhn box): every column a stored row can receive is its vertex plus one of a
+  // fixed set of lattice offsets (BoxCodes), so row r owns ncode slots at off[r] + code -- no keys, no hashing, no
+  // probes.  occ[slot] = 1 marks the slots that received a contribution (the structural pattern is dolfinx's, an exact
+  // zero included).  bn0 / bn1: vertices per lattice row / column (to recover lattice offsets from vertex indices).
+  // occ == nullptr: the hashed slots above.
+  uint8_t *occ = nullptr;
+  int ncode = 0;
+  int32_t bn0 = 0, bn1 = 0;
 };
+
+// Offset codes of the box slots, built on the host from the Kuhn simplex table (k_box_cells) for D = 2, 3.  Codes
+// [0, nucode) are u columns, [nucode, ncode) p columns, each in lattice order (dz, dy, dx): the active numbering is
+// monotone in the vertex index, so code order IS column order and the compaction needs no sort.
+//   u columns of u rows: any two vertices of one simplex (stiffness, cut cells, one-sided boundary term) or of the
+//                        two simplices of an interior facet (ghost penalty): offsets in [-2, 2]^D
+//   p columns, and every column of p rows: any two vertices of one simplex (cut cells)
+#define PHX_BOX_MAXCODE 64
+struct BoxCodes {
+  int ncode, nucode;
+  int8_t lut[2][125];              // [column field][(dz + 2) 25 + (dy + 2) 5 + dx + 2] -> code; -1: no slot
+  int8_t k27[2][27];               // the same by the star code sum (d_a + 1) 3^a of the row kernels
+  int8_t d[PHX_BOX_MAXCODE][3];    // lattice offset of each code
+};
+__constant__ BoxCodes c_box[2];    // [D - 2]
+
+// lattice position of vertex v
+__device__ __forceinline__ void box_xyz(const Slots &s, int32_t v, int *c) {
+  const uint32_t u = (uint32_t)v, q = u / (uint32_t)s.bn0;
+  c[0] = (int)(u - q * (uint32_t)s.bn0);
+  c[1] = (int)(q % (uint32_t)s.bn1);
+  c[2] = (int)(q / (uint32_t)s.bn1);
+}
+// slot code of column field f at the vertex at lattice position cb in the row of the vertex at ca; -1: no such slot
+template <int D>
+__device__ __forceinline__ int box_code(int f, const int *ca, const int *cb) {
+  const int dx = cb[0] - ca[0], dy = cb[1] - ca[1], dz = D == 3 ? cb[2] - ca[2] : 0;
+  if (dx < -2 || dx > 2 || dy < -2 || dy > 2 || dz < -2 || dz > 2) return -1;
+  return c_box[D - 2].lut[f][(dz + 2) * 25 + (dy + 2) * 5 + dx + 2];
+}
+// atomic add into slot `code` of the row whose slots start at `base` (the exact-zero skip of slot_add)
+__device__ __forceinline__ void slot_add_box(const Slots &s, int64_t base, int code, double v) {
+  if (code < 0) { atomicOr(s.overflow, 1); return; }
+  s.occ[base + code] = 1;
+  if (v != 0.0) unsafeAtomicAdd(&s.vals[base + code], v);
+}
+// plain add into a row this thread owns exclusively
+__device__ __forceinline__ void slot_add_box_owned(const Slots &s, int64_t base, int code, double v) {
+  if (code < 0) { atomicOr(s.overflow, 1); return; }
+  s.occ[base + code] = 1;
+  s.vals[base + code] += v;
+}
 
 __device__ __forceinline__ int det_expo(double v) { return (int)((__double_as_longlong(v) >> 52) & 0x7ff); }
 __device__ __forceinline__ void det_split(double v, int e, double &hi, double &lo) {
@@ -614,6 +665,19 @@ k_assemble_rows_box(int64_t nthreads, BoxDims bd, AsmArgs A, int mode, const int
     A.diag[row] = acc[SELF];
     if (!A.store_c0) return;
   }
+  if (A.slots.occ) {
+    // box slots: the first writer of the row (the slots are cleared), plain stores at the codes of the star
+    const int64_t sb = A.slots.off[row];
+#pragma unroll
+    for (int code = 0; code < NCODE; ++code) {
+      if (!seen[code]) continue;
+      const int k = c_box[D - 2].k27[0][code];
+      if (k < 0) { atomicOr(A.slots.overflow, 1); continue; }
+      A.slots.occ[sb + k] = 1;
+      A.slots.vals[sb + k] = acc[code];
+    }
+    return;
+  }
   // a row no scattering kernel will touch is stored densely and already sorted (codes ascend with the
   // vertex index, hence with the column): it skips the hash table and the sort of the compaction
   const bool clean = A.slots.clean && A.touched && !A.touched[vtx];
@@ -818,6 +882,21 @@ k_assemble_cut_rows_box(int64_t np, const int64_t *__restrict__ full_p, BoxDims 
       rp += kup * bq;
     }
   }
+  A.rhs[rowu] += ru;
+  A.rhs[rowp] += rp;
+  if (A.slots.occ) {
+    const int64_t bu = A.slots.off[rowu], bp = A.slots.off[rowp];
+#pragma unroll
+    for (int code = 0; code < NCODE; ++code) {
+      if (!((seen >> code) & 1u)) continue;
+      const int ku = c_box[D - 2].k27[0][code], kp = c_box[D - 2].k27[1][code];
+      slot_add_box_owned(A.slots, bu, ku, auu[code]);
+      slot_add_box_owned(A.slots, bu, kp, aup[code]);
+      slot_add_box_owned(A.slots, bp, ku, aup[code]);
+      slot_add_box_owned(A.slots, bp, kp, app[code]);
+    }
+    return;
+  }
   const int32_t nvi = A.nv;
 #pragma unroll
   for (int code = 0; code < NCODE; ++code) {
@@ -830,8 +909,6 @@ k_assemble_cut_rows_box(int64_t np, const int64_t *__restrict__ full_p, BoxDims 
     slot_add_owned(A.slots, rowp, (int32_t)w, aup[code]);
     slot_add_owned(A.slots, rowp, nvi + (int32_t)w, app[code]);
   }
-  A.rhs[rowu] += ru;
-  A.rhs[rowp] += rp;
 }
 
 // --- one-sided boundary term, main.py:114:  -int_F (grad u . n) v  over (cell, local facet) ---
@@ -858,6 +935,15 @@ __global__ void k_assemble_ds(int64_t nent, const int64_t *__restrict__ ent_pack
   simplex_geometry<D>(X, G);
   double k = 0.0;
   for (int d = 0; d < D; ++d) k += G.g[j][d] * G.g[lf][d];
+  if (A.slots.occ) {
+    const int32_t row = A.du[v[i]];
+    if (row < 0) return;
+    int ci[3], cj[3];
+    box_xyz(A.slots, v[i], ci);
+    box_xyz(A.slots, v[j], cj);
+    slot_add_box(A.slots, A.slots.off[row], box_code<D>(0, ci, cj), k * G.vol);
+    return;
+  }
   slot_add(A.slots, A.du[v[i]], v[j], k * G.vol);
 }
 
@@ -935,6 +1021,19 @@ __global__ void __launch_bounds__(256) k_assemble_facets(int64_t nlist, const in
   int32_t rows[M];
 #pragma unroll
   for (int a = 0; a < M; ++a) rows[a] = A.du[vd[a]];
+  if (A.slots.occ) {
+    int cx[M][3];
+#pragma unroll
+    for (int a = 0; a < M; ++a) box_xyz(A.slots, vd[a], cx[a]);
+#pragma unroll
+    for (int a = 0; a < M; ++a) {
+      if (rows[a] < 0) continue;
+      const int64_t base = A.slots.off[rows[a]];
+#pragma unroll
+      for (int b = 0; b < M; ++b) slot_add_box(A.slots, base, box_code<D>(0, cx[a], cx[b]), w * Jd[a] * Jd[b]);
+    }
+    return;
+  }
 #pragma unroll
   for (int a = 0; a < M; ++a)
 #pragma unroll
@@ -1294,10 +1393,90 @@ extern "C" int phx_system_destroy(phx_system *s) {
   return PHX_OK;
 }
 
+// BoxCodes of dimension D from the Kuhn simplices of the cubes around the origin
+static void box_codes_build(int D, BoxCodes &t) {
+  const int P[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};   // k_box_cells
+  const int P2[2][3] = {{0, 1, 0}, {1, 0, 0}};
+  const int N = D + 1, NPERM = D == 3 ? 6 : 2;
+  struct Simp { int v[4][3]; };
+  std::vector<Simp> cube0, around;   // simplices of the cube at the origin / of the 3^D cubes around it
+  for (int oz = (D == 3 ? -1 : 0); oz <= (D == 3 ? 1 : 0); ++oz)
+    for (int oy = -1; oy <= 1; ++oy)
+      for (int ox = -1; ox <= 1; ++ox)
+        for (int p = 0; p < NPERM; ++p) {
+          Simp s{};
+          int c[3] = {ox, oy, oz};
+          for (int q = 0; q < N; ++q) {
+            for (int a = 0; a < 3; ++a) s.v[q][a] = c[a];
+            if (q < D) c[D == 3 ? P[p][q] : P2[p][q]] += 1;
+          }
+          around.push_back(s);
+          if (ox == 0 && oy == 0 && oz == 0) cube0.push_back(s);
+        }
+  bool in[2][125] = {};   // [column field][offset]
+  auto mark = [&](int f, const int *a, const int *b) {
+    in[f][(b[2] - a[2] + 2) * 25 + (b[1] - a[1] + 2) * 5 + (b[0] - a[0] + 2)] = true;
+  };
+  for (const Simp &s : cube0)   // stiffness, cut cells (u and p), one-sided boundary term
+    for (int i = 0; i < N; ++i)
+      for (int j = 0; j < N; ++j) { mark(0, s.v[i], s.v[j]); mark(1, s.v[i], s.v[j]); }
+  for (const Simp &s : cube0)   // ghost penalty: the macro-element of two simplices sharing a facet (u columns)
+    for (const Simp &r : around) {
+      int shared = 0, opp = -1;
+      for (int j = 0; j < N; ++j) {
+        bool hit = false;
+        for (int i = 0; i < N; ++i) hit = hit || (s.v[i][0] == r.v[j][0] && s.v[i][1] == r.v[j][1] && s.v[i][2] == r.v[j][2]);
+        if (hit) ++shared; else opp = j;
+      }
+      if (shared != D) continue;
+      int mv[5][3];
+      for (int i = 0; i < N; ++i) for (int a = 0; a < 3; ++a) mv[i][a] = s.v[i][a];
+      for (int a = 0; a < 3; ++a) mv[N][a] = r.v[opp][a];
+      for (int i = 0; i <= N; ++i)
+        for (int j = 0; j <= N; ++j) mark(0, mv[i], mv[j]);
+    }
+  memset(&t, 0, sizeof(t));
+  memset(t.lut, -1, sizeof(t.lut));
+  memset(t.k27, -1, sizeof(t.k27));
+  int nc = 0;
+  for (int f = 0; f < 2; ++f) {
+    for (int o = 0; o < 125; ++o) {   // ascending o = lattice order (dz, dy, dx)
+      if (!in[f][o]) continue;
+      t.lut[f][o] = (int8_t)nc;
+      t.d[nc][0] = (int8_t)(o % 5 - 2); t.d[nc][1] = (int8_t)((o / 5) % 5 - 2); t.d[nc][2] = (int8_t)(o / 25 - 2);
+      ++nc;
+    }
+    if (f == 0) t.nucode = nc;
+  }
+  t.ncode = nc;
+  for (int f = 0; f < 2; ++f)
+    for (int c = 0; c < (D == 3 ? 27 : 9); ++c) {   // the 2-D star code has no z digit
+      const int dx = c % 3 - 1, dy = (c / 3) % 3 - 1, dz = D == 3 ? c / 9 - 1 : 0;
+      t.k27[f][c] = t.lut[f][(dz + 2) * 25 + (dy + 2) * 5 + dx + 2];
+    }
+}
+
+// the tables of D = 2 and 3, in the constant memory of the device once (host copy for the compaction's view)
+static const BoxCodes *box_codes(int device, int D) {
+  static BoxCodes host[2];
+  static bool built = false;
+  static bool uploaded[64] = {};
+  static std::mutex mu;
+  std::lock_guard<std::mutex> lk(mu);
+  if (!built) { box_codes_build(2, host[0]); box_codes_build(3, host[1]); built = true; }
+  if (device >= 0 && device < 64 && !uploaded[device]) {
+    if (hipMemcpyToSymbol(HIP_SYMBOL(c_box), host, sizeof(host), 0, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+    uploaded[device] = true;
+  }
+  return &host[D - 2];
+}
+
 static int free_slots(Slots &sl) {
+  PHX_HIP(phx_free(sl.occ));
   PHX_HIP(phx_free(sl.cols)); PHX_HIP(phx_free(sl.vals)); PHX_HIP(phx_free(sl.overflow)); PHX_HIP(phx_free(sl.clean));
   PHX_HIP(phx_free((void *)sl.off)); PHX_HIP(phx_free((void *)sl.wlog));
   sl.cols = nullptr; sl.vals = nullptr; sl.overflow = nullptr; sl.clean = nullptr; sl.off = nullptr; sl.wlog = nullptr;
+  sl.occ = nullptr;
   return PHX_OK;
 }
 
@@ -1307,8 +1486,9 @@ static int check_overflow(phx_mesh *m, Slots &sl) {
   PHX_HIP(hipStreamSynchronize(m->stream));
   if (overflow) {
     PHX_CHECK(free_slots(sl));
-    phx_set_error("row-slot capacity %d exceeded", sl.W);
-    return PHX_ERR_CAPACITY;
+    if (sl.ncode) phx_set_error("box slots: a contribution at a lattice offset outside the code table");
+    else phx_set_error("row-slot capacity %d exceeded", sl.W);
+    return sl.ncode ? PHX_ERR_VALUE : PHX_ERR_CAPACITY;
   }
   return PHX_OK;
 }
@@ -1328,7 +1508,19 @@ int phx_finish_system(phx_system *s, Slots &sl, int32_t nent) {
 static int finish_structured(phx_system *s, Slots &sl, int32_t nent, bool with_csr) {
   PHX_CHECK(check_overflow(s->mesh, sl));
   if (with_csr) PHX_CHECK(csr_from_slots(s, sl, nent));
-  const phx_slot_view sv{sl.cols, sl.vals, sl.W, sl.clean, sl.off, sl.wlog};
+  phx_slot_view sv{sl.cols, sl.vals, sl.W, sl.clean, sl.off, sl.wlog};
+  if (sl.occ) {
+    const phx_mesh *m = s->mesh;
+    const BoxCodes *t = box_codes(-1, m->gdim);
+    const int64_t n0 = m->box_n[0] + 1, n01 = n0 * (m->box_n[1] + 1);
+    sv.occ = sl.occ;
+    sv.W = sl.ncode;
+    sv.ncode = t->ncode;
+    sv.nucode = t->nucode;
+    sv.uself = t->lut[0][62];   // offset (0, 0, 0)
+    sv.pself = t->lut[1][62];
+    for (int k = 0; k < t->ncode; ++k) sv.coff[k] = (int32_t)(t->d[k][0] + t->d[k][1] * n0 + t->d[k][2] * n01);
+  }
   const int rc = phx_system_build_structured(s, sv, nent);
   PHX_CHECK(free_slots(sl));
   return rc;
@@ -1488,14 +1680,28 @@ static int assemble_with_capacity(phx_mesh *m, double pen_coef, double stab_coef
   int32_t *stored_rows = nullptr;   // structured systems without a CSR copy: active indices of the rows that are stored
   int64_t n_stored_rows = 0;
   const bool structured = m->is_box && !m->is_submesh && m->structured != 0;
+  static const bool cut_scatter = getenv("PHX_CUT_SCATTER") && atoi(getenv("PHX_CUT_SCATTER")) != 0;   // A/B aid
+  // box slots (BoxCodes) for the stored rows of structured systems; PHX_BOX_SLOTS=0: the hashed slots (A/B aid)
+  const char *bs_env = getenv("PHX_BOX_SLOTS");
+  const bool box_slots = structured && !m->export_csr && !m->deterministic && !cut_scatter && !(bs_env && atoi(bs_env) == 0);
+  const BoxCodes *codes = nullptr;
+  if (box_slots) {
+    codes = box_codes(m->device, D);
+    PHX_REQUIRE(codes != nullptr && codes->ncode <= PHX_BOX_MAXCODE, PHX_ERR_HIP, "box slot code table");
+    sl.ncode = codes->ncode;
+    sl.bn0 = (int32_t)(m->box_n[0] + 1);
+    sl.bn1 = D == 3 ? (int32_t)(m->box_n[1] + 1) : 0x7fffffff;
+  }
   int64_t slot_rows = s->n;
   if (m->is_box && !m->is_submesh) {
     // rows of vertices no scattering kernel reaches are written dense and sorted by the gather kernel
     PHX_CHECK(phx_collect_entities(m));
     PHX_HIP(phx_malloc(&touched, (size_t)m->nv));
-    PHX_HIP(phx_malloc(&sl.clean, (size_t)s->n));
     PHX_HIP(hipMemsetAsync(touched, 0, (size_t)m->nv, m->stream));
-    PHX_HIP(hipMemsetAsync(sl.clean, 0, (size_t)s->n, m->stream));
+    if (!box_slots) {   // box slots place every entry at its code: no clean rows
+      PHX_HIP(phx_malloc(&sl.clean, (size_t)s->n));
+      PHX_HIP(hipMemsetAsync(sl.clean, 0, (size_t)s->n, m->stream));
+    }
     constexpr int TB = 256;
     if (n_cut > 0) {
       const dim3 g((unsigned)phx_div_up(n_cut, TB));
@@ -1549,7 +1755,8 @@ static int assemble_with_capacity(phx_mesh *m, double pen_coef, double stab_coef
       PHX_HIP(phx_malloc(&wl, (size_t)s->n));
       int lg = 0;
       while ((1 << lg) < W) ++lg;
-      k_slot_offsets<<<dim3((unsigned)phx_div_up(s->n, 256)), block, 0, m->stream>>>(s->n, W, lg, s->c0, rank, off, wl);
+      k_slot_offsets<<<dim3((unsigned)phx_div_up(s->n, 256)), block, 0, m->stream>>>(s->n, box_slots ? sl.ncode : W, lg,
+                                                                                   s->c0, rank, off, wl);
       sl.off = off; sl.wlog = wl;
       if (nstored > 0) {   // the stored rows as a list: work list of the row kernel (mode 2)
         PHX_HIP(phx_malloc(&stored_rows, sizeof(int32_t) * (size_t)nstored));
@@ -1561,11 +1768,16 @@ static int assemble_with_capacity(phx_mesh *m, double pen_coef, double stab_coef
   }
   // ---- slots (of the stored rows)
   {
-    const size_t ns = (size_t)std::max<int64_t>(slot_rows, 1) * W;
-    PHX_HIP(phx_malloc(&sl.cols, sizeof(int32_t) * ns));
+    const size_t ns = (size_t)std::max<int64_t>(slot_rows, 1) * (box_slots ? sl.ncode : W);
     PHX_HIP(phx_malloc(&sl.vals, sizeof(double) * ns));
     PHX_HIP(phx_malloc(&sl.overflow, sizeof(int)));
-    PHX_HIP(hipMemsetAsync(sl.cols, 0xff, sizeof(int32_t) * ns, m->stream));
+    if (box_slots) {   // occupancy and values only: no keys
+      PHX_HIP(phx_malloc(&sl.occ, ns));
+      PHX_HIP(hipMemsetAsync(sl.occ, 0, ns, m->stream));
+    } else {
+      PHX_HIP(phx_malloc(&sl.cols, sizeof(int32_t) * ns));
+      PHX_HIP(hipMemsetAsync(sl.cols, 0xff, sizeof(int32_t) * ns, m->stream));
+    }
     PHX_HIP(hipMemsetAsync(sl.vals, 0, sizeof(double) * ns, m->stream));
     PHX_HIP(hipMemsetAsync(sl.overflow, 0, sizeof(int), m->stream));
   }
@@ -1588,7 +1800,6 @@ static int assemble_with_capacity(phx_mesh *m, double pen_coef, double stab_coef
       else k_assemble_rows<3><<<g, b, 0, m->stream>>>(m->nv, m->v2c_ptr, m->v2c_idx, A);
     }
   }
-  static const bool cut_scatter = getenv("PHX_CUT_SCATTER") && atoi(getenv("PHX_CUT_SCATTER")) != 0;   // A/B aid
   if (n_cut > 0 && m->is_box && !cut_scatter) {
     // Kuhn box: the cut-cell terms as row gathers (no atomics)
     const BoxDims bd{{m->box_n[0], m->box_n[1], m->box_n[2]}, {m->box_h[0], m->box_h[1], m->box_h[2]}};

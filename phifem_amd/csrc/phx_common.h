@@ -338,6 +338,12 @@ struct phx_slot_view {
   const int64_t *off;     // per-row slot offsets (nullptr: row * W)
   const uint8_t *wlog;
   bool pneg = false;      // column key of a p DoF e: -2 - e (structured P2) instead of nent + e
+  // box slots (structured P1 on a Kuhn box, phx_assemble.hip: BoxCodes): no column keys -- row r owns ncode slots at
+  // off[r] + code, occ[slot] = 1 once anything was added there.  Code k is the column at lattice offset coff[k] of the
+  // row's vertex, u for k < nucode, p beyond; codes ascend with the column.  occ == nullptr: hashed slots above.
+  const uint8_t *occ = nullptr;
+  int ncode = 0, nucode = 0, uself = 0, pself = 0;
+  int32_t coff[64] = {};
 };
 int phx_system_build_structured(phx_system *s, const phx_slot_view &sv, int32_t nent);  // phx_solve.hip
 // structured P2: lattice flags of the C0 rows / of the rows the stencils apply (uint8 [F0 F1 F2]), s->c0 = the latter

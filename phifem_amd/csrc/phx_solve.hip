@@ -331,6 +331,32 @@ k_slot_row_meta(int64_t ns, const int32_t *__restrict__ list, phx_slot_view sv, 
   if (lane == 0) { len[i] = keep; nstruct[i] = st; }
 }
 
+// the same over box slots (sv.occ): lane k holds code k of the row
+__global__ void __launch_bounds__(256)
+k_slot_row_meta_box(int64_t ns, const int32_t *__restrict__ list, phx_slot_view sv, const uint8_t *__restrict__ c0,
+                    int64_t nu, int gdim, int32_t *__restrict__ len, int32_t *__restrict__ nstruct,
+                    double *__restrict__ diag) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
+  if (i >= ns) return;
+  const int32_t row = list[i];
+  if (c0 && c0[row]) {
+    if (lane == 0) { len[i] = gdim == 3 ? 7 : 5; nstruct[i] = gdim == 3 ? 15 : 7; }
+    return;
+  }
+  const int64_t base = sv.off[row];
+  const int self = row < nu ? sv.uself : sv.pself;
+  bool st = false, keep = false;
+  if (lane < sv.ncode && sv.occ[base + lane]) {
+    const double v = sv.vals[base + lane];
+    st = true;
+    if (lane == self) { diag[row] = v; keep = true; }
+    else keep = v != 0.0;
+  }
+  const unsigned long long bst = __ballot(st), bkeep = __ballot(keep);
+  if (lane == 0) { len[i] = __popcll(bkeep); nstruct[i] = __popcll(bst); }
+}
+
 // totals[0] += sum a, totals[1] += sum b (one atomic pair per block; per-row atomics on a few addresses cost
 // 2.7 ms for 6e5 rows)
 __global__ void __launch_bounds__(256)
@@ -511,6 +537,71 @@ k_sell_fill_slots(int64_t ns, const int32_t *__restrict__ rows, phx_slot_view sv
     } else {
       scol[o] = iperm[row]; sraw[o] = 0.0; sval[o] = 0.0;
     }
+  }
+}
+
+// k_sell_fill_slots over box slots (sv.occ): lane k holds code k of the row, and the codes ascend with the column, so
+// a kept entry goes to the position of its rank among the kept lanes -- no sort.  A stored C0 row is written from the
+// stencil coefficients at the ranks of its lattice neighbours in column order (-z, -y, -x, self, +x, +y, +z).
+__global__ void __launch_bounds__(256)
+k_sell_fill_slots_box(int64_t ns, const int32_t *__restrict__ rows, phx_slot_view sv, const uint8_t *__restrict__ c0,
+                      int32_t nent, const int32_t *__restrict__ du, const int32_t *__restrict__ dp, int64_t nu, int gdim,
+                      const double *__restrict__ stencil, const double *__restrict__ diag,
+                      const int32_t *__restrict__ iperm, const int64_t *__restrict__ slice_ptr,
+                      int32_t *__restrict__ scol, double *__restrict__ sval, double *__restrict__ sraw,
+                      const int64_t *__restrict__ full, int64_t n0, int64_t n01) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
+  if (i >= ns) return;
+  const int32_t row = rows[i];
+  const int64_t sl = i / SELL_S, li = i % SELL_S;
+  const int64_t sb = slice_ptr[sl];
+  const int width = (int)((slice_ptr[sl + 1] - sb) / SELL_S);
+  bool keep = false;
+  int pos = 0;
+  int32_t c = 0;
+  double v = 0.0;
+  int cnt;
+  if (c0[row]) {
+    // lattice Laplacian row: lanes 0..6 = self, -x, +x, -y, +y, -z, +z (k_sell_fill_slots)
+    const int64_t vtx = full[row];
+    cnt = gdim == 3 ? 7 : 5;
+    if (lane < cnt) {
+      const int64_t off = lane == 0 ? 0 : (lane <= 2 ? 1 : (lane <= 4 ? n0 : n01));
+      const int64_t w = (lane & 1) ? vtx - off : vtx + off;
+      c = du[w];
+      v = stencil[lane == 0 ? 0 : (lane + 1) / 2];
+      keep = true;
+      // rank in column order: lane 0 sits behind the minus sides, a plus side behind self
+      const int half = cnt >> 1;
+      pos = lane == 0 ? half : ((lane & 1) ? half - (lane + 1) / 2 : half + lane / 2);
+    }
+  } else {
+    const int64_t base = sv.off[row];
+    const int self = row < nu ? sv.uself : sv.pself;
+    if (lane < sv.ncode && sv.occ[base + lane]) {
+      v = sv.vals[base + lane];
+      keep = v != 0.0 || lane == self;
+    }
+    const unsigned long long bk = __ballot(keep);
+    cnt = __popcll(bk);
+    pos = __popcll(bk & ((1ull << lane) - 1ull));
+    if (keep) {
+      int64_t vtx = full[row];
+      if (vtx >= nent) vtx -= nent;
+      const int64_t w = vtx + sv.coff[lane];
+      c = lane < sv.nucode ? du[w] : dp[w];
+    }
+  }
+  if (keep && pos < width) {
+    const int64_t o = sb + (int64_t)pos * SELL_S + li;
+    scol[o] = iperm[c];
+    sraw[o] = v;
+    sval[o] = c < nu ? v : v / diag[c];   // u columns unscaled, p columns A D^-1
+  }
+  if (lane >= cnt && lane < width) {
+    const int64_t o = sb + (int64_t)lane * SELL_S + li;
+    scol[o] = iperm[row]; sraw[o] = 0.0; sval[o] = 0.0;
   }
 }
 
@@ -766,8 +857,12 @@ int phx_system_build_structured(phx_system *s, const phx_slot_view &sv, int32_t 
   PHX_HIP(hipMemsetAsync(dtot, 0, sizeof(htot), st));
   if (ns > 0) {
     PHX_REQUIRE_GRID(ns * 64, "stored-row scan");
-    k_slot_row_meta<<<dim3((unsigned)phx_div_up(ns * 64, 256)), block, 0, st>>>(
-        ns, list, sv, s->c0, nent, s->dof_of_vertex_u, s->dof_of_vertex_p, m->gdim, len, nstruct, s->diag);
+    if (sv.occ)
+      k_slot_row_meta_box<<<dim3((unsigned)phx_div_up(ns * 64, 256)), block, 0, st>>>(
+          ns, list, sv, s->c0, nu, m->gdim, len, nstruct, s->diag);
+    else
+      k_slot_row_meta<<<dim3((unsigned)phx_div_up(ns * 64, 256)), block, 0, st>>>(
+          ns, list, sv, s->c0, nent, s->dof_of_vertex_u, s->dof_of_vertex_p, m->gdim, len, nstruct, s->diag);
     k_sum2_i32<<<dim3((unsigned)std::min<int64_t>(phx_div_up(ns, 256), 512)), block, 0, st>>>(ns, nstruct, len, dtot);
   }
   PHX_HIP(hipMemcpyAsync(htot, dtot, sizeof(htot), hipMemcpyDeviceToHost, st));
@@ -840,9 +935,14 @@ int phx_system_build_structured(phx_system *s, const phx_slot_view &sv, int32_t 
   s->sell_stream_bytes = 0;
   if (ns > 0) {
     const dim3 gf((unsigned)phx_div_up(ns * 64, 256));
-    k_sell_fill_slots<<<gf, block, 0, st>>>(ns, rows_active, sv, s->c0, nent, s->dof_of_vertex_u, s->dof_of_vertex_p, nu,
-                                            m->gdim, s->stencil, s->diag, s->iperm, s->slice_ptr, s->sell_col, s->sell_val,
-                                            s->sell_val_raw, s->full_of_active, n0, n01);
+    if (sv.occ)
+      k_sell_fill_slots_box<<<gf, block, 0, st>>>(ns, rows_active, sv, s->c0, nent, s->dof_of_vertex_u, s->dof_of_vertex_p,
+                                                  nu, m->gdim, s->stencil, s->diag, s->iperm, s->slice_ptr, s->sell_col,
+                                                  s->sell_val, s->sell_val_raw, s->full_of_active, n0, n01);
+    else
+      k_sell_fill_slots<<<gf, block, 0, st>>>(ns, rows_active, sv, s->c0, nent, s->dof_of_vertex_u, s->dof_of_vertex_p, nu,
+                                              m->gdim, s->stencil, s->diag, s->iperm, s->slice_ptr, s->sell_col, s->sell_val,
+                                              s->sell_val_raw, s->full_of_active, n0, n01);
     if (ns < s->nslices * SELL_S)
       k_sell_pad_tail<<<1, 64, 0, st>>>(ns, s->nslices, s->slice_ptr, s->sell_col, s->sell_val, s->sell_val_raw);
     PHX_HIP(hipGetLastError());
@@ -896,6 +996,17 @@ int phx_system_build_structured(phx_system *s, const phx_slot_view &sv, int32_t 
   PHX_HIP(phx_malloc(&s->work, sizeof(double) * (size_t)n * 9));
   PHX_HIP(phx_malloc(&s->scal, sizeof(double) * PHX_SCAL_DOUBLES));
   PHX_CHECK(phx_mesh_pinned_scalars(s->mesh, &s->scal_h));
+  return PHX_OK;
+}
+
+extern "C" int phx_system_export_sell(phx_system *s, int64_t *slice_ptr, int32_t *col, double *val, int32_t *rows) {
+  PHX_HIP(hipSetDevice(s->mesh->device));
+  PHX_REQUIRE(s->structured && !s->p2s, PHX_ERR_VALUE, "SELL export: structured P1 systems only");
+  const size_t nsl = (size_t)s->nslices, ne = (size_t)s->sell_nnz;
+  if (slice_ptr) PHX_HIP(hipMemcpy(slice_ptr, s->slice_ptr, sizeof(int64_t) * (nsl + 1), hipMemcpyDeviceToHost));
+  if (col && ne) PHX_HIP(hipMemcpy(col, s->sell_col, sizeof(int32_t) * ne, hipMemcpyDeviceToHost));
+  if (val && ne) PHX_HIP(hipMemcpy(val, s->sell_val_raw, sizeof(double) * ne, hipMemcpyDeviceToHost));
+  if (rows && nsl) PHX_HIP(hipMemcpy(rows, s->sell_rows, sizeof(int32_t) * nsl * SELL_S, hipMemcpyDeviceToHost));
   return PHX_OK;
 }
 
