@@ -1297,7 +1297,8 @@ static int box_precond_setup(phx_system *s) {
     // z (tridiagonal solve, no transform): exactly extent + margins planes; a 2-D lattice keeps its one real plane
     const bool free_len = a == 2 && ztri;
     if (free_len && m->gdim == 3) {
-      const int top = (m->is_box || m->on_box_lattice) ? (int)m->box_n[2] : -1;   // last vertex plane of the mesh box
+      // last vertex plane of the mesh box, in the coordinates of hbb (P2: the lattice of spacing h / 2)
+      const int top = (m->is_box || m->on_box_lattice) ? (int)m->box_n[2] * (p2 ? 2 : 1) : -1;
       int mlo = hbb[2] == 0 ? PHX_PRECOND_MARGIN_OPEN : PHX_PRECOND_MARGIN;
       int mhi = hbb[5] == top ? PHX_PRECOND_MARGIN_OPEN : PHX_PRECOND_MARGIN;
       if (extent + mlo + mhi + 1 > 1025) mlo = mhi = PHX_PRECOND_MARGIN;
