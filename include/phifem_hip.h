@@ -198,7 +198,8 @@ enum phx_option {
                                SELL storage; P2 weak-Dirichlet systems on 3-D Kuhn boxes likewise (eight class
                                stencils, interior rows never assembled).  0: every row stored (SELL)          */
   PHX_OPT_DETERMINISTIC = 9, /* 1: bit-reproducible results for the scattering assemblies (P2 weak Dirichlet,
-                               interface elasticity) and the Krylov solve: the element kernels run twice and
+                               interface elasticity, P1 weak Dirichlet on meshes that are no Kuhn boxes -- boxes keep
+                               plain atomics at P1) and the Krylov solve: the element kernels run twice and
                                accumulate exactly (per-slot exponent, two accumulators), the dot products are
                                summed in a fixed order.  Costs one more pass of the element kernels and 12 bytes
                                per row slot while assembling (skipped beyond PHX_DET_LIMIT_GB, default a fifth of the device memory).
@@ -277,6 +278,32 @@ int phx_integration_entities(phx_mesh *m, int which, int32_t *out, int64_t *n_pa
  * (pass NULL first, sizes come back in counts of *sub). */
 int phx_submesh_create(phx_mesh *m, phx_mesh **sub);
 int phx_submesh_maps(phx_mesh *sub, int32_t *c_map, int32_t *v_map);
+
+/* --- partition of an unstructured background mesh over ranks (triangles, tetrahedra) ---------
+ * No counterpart in the reference (serial, src/phifem/mesh_scripts.py:264).  Every rank holds the WHOLE mesh, calls
+ * these redundantly and obtains the same bits; tests/partition_ref.py restates the rules in numpy.
+ *
+ * Recursive coordinate bisection of the cell centroids into nparts <= 4096 parts: part[nc] (int32).  weights[nc]:
+ * non-negative int32, NULL = all ones.  Centroid = vertex coordinates summed in local-vertex order, then divided by the
+ * vertex count.  A part range [p0, p1) over its cells S splits along the first axis of largest centroid extent; S is
+ * ordered by (coordinate, cell index) and the left (p1 - p0) / 2 parts take the shortest prefix whose weight w satisfies
+ * w (p1 - p0) >= W (p1 - p0) / 2 (integer arithmetic, W = weight of S).  One pass per level on the device: segmented
+ * min / max, two stable radix sorts, one weighted scan; nothing returns to the host in between.  loc: where weights and
+ * part live. */
+int phx_partition_cells(phx_mesh *m, int nparts, const int32_t *weights, int32_t *part, int loc);
+/* Ownership and local cells of `rank` for a partition of the TAGGED mesh.  owner[nv] (int32): part of the
+ * lowest-numbered cell tagged 1 or 2 that contains the vertex, -1 for vertices of exterior cells only.  flags[nc]
+ * (uint8), the first layer that takes the cell: 1 = a cell with a vertex the rank owns; 2 = a facet neighbour of a
+ * layer-1 cell (a ghost-penalty facet couples all DoFs of its two cells, so the rows of owned vertices reach that far);
+ * 3 = a cell with a vertex of layers 1 - 2; 4 = a facet neighbour of a layer-3 cell (the solver scales every column by
+ * its diagonal entry, so the diagonal of each column an owned row refers to has to be complete as well); 0 = not local.
+ * A rank that owns nothing gets one placeholder cell (flag 2): the lowest-numbered cell not tagged 1 / 2, else cell 0.
+ * Either output may be NULL.  loc: where part, owner and flags live. */
+int phx_partition_layout(phx_mesh *m, int nparts, const int32_t *part, int rank, int32_t *owner, uint8_t *flags, int loc);
+/* Local mesh of the cells with flags[nc] != 0: cells and vertices ascending in the parent's numbering (maps through
+ * phx_submesh_maps), the parent's cell and facet tags transferred, never recomputed.  Unlike phx_submesh_create the
+ * result is a BOX-MODE mesh: the facets on its rim are cuts, not boundary -- assemble with the transferred tags. */
+int phx_submesh_create_from_flags(phx_mesh *m, const uint8_t *flags, int loc, phx_mesh **sub);
 
 /* ------------------------------------------------------------------ assembly --------- */
 /* Weak-Dirichlet phi-FEM Poisson, mixed (u,p) in P1 x P1: bilinear form
@@ -443,7 +470,7 @@ int phx_system_get_perm(phx_system *s, int32_t *perm, int32_t *dof_u, int32_t *d
 /* --- native multi-GPU solve: RCCL on the solver's stream (bound with dlopen at run time) -------
  * One communicator per process; the 128-byte id comes from rank 0 (phx_comm_unique_id) and is
  * broadcast by the host (torch.distributed).  phx_solve_distributed runs the same phase sequence
- * as phx_solve with a point-to-point halo of p and s (ncclSend/ncclRecv with <= 2 neighbours, on the communicator's
+ * as phx_solve with a point-to-point halo of p and s (ncclSend/ncclRecv with up to nranks - 1 peers, on the communicator's
  * own stream, overlapped with the rows of the SpMV that read no halo entry; PHX_DIST_OVERLAP=0: in series) and
  * three all-reduces of 1, 2, 2 doubles per iteration.  Convergence checks are scheduled as in phx_solve; relres /
  * converged refer to the TRUE residual (one more halo exchange + SpMV + all-reduce, restart when it misses rtol).

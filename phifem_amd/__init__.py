@@ -9,6 +9,8 @@ Host side (this package) mirrors the reference's interface for the path:
   * `phifem_amd.solver.StrongDirichletSolver`        <- demo/strong-dirichlet/flower/main.py:83-182
   * `phifem_amd.solver.NeumannRobinSolver`           <- demo/robin/square/main.py:98-190 (simplices) and
     demo/neumann/square/main.py:49-158 (quadrilaterals)
+  * `phifem_amd.partition_cells`, `phifem_amd.distributed.PartitionedProblem`  <- no counterpart: unstructured
+    background meshes partitioned over the ranks (the reference is serial, src/phifem/mesh_scripts.py:264)
   * `phifem_amd.io`                                  <- XDMFFile.write_mesh / write_function / read_mesh
 Everything numerical runs in `libphifem_hip.so` (hand-written HIP for gfx950) through the C ABI
 declared in `include/phifem_hip.h`.  There is no CPU fallback.
@@ -18,5 +20,7 @@ from .mesh import Mesh, MeshTags, create_box, create_rectangle  # noqa: F401
 from . import io  # noqa: F401
 from .mesh_scripts import (DeviceExpression, NodalFunction, Quadric, compute_tags_measures,  # noqa: F401
                            interpolate)
+from .partition import partition_cells, partition_layout  # noqa: F401
+from .distributed import PartitionedProblem  # noqa: F401
 from .solver import (InterfaceElasticitySolver, NeumannRobinSolver, PhiFEMSolver,  # noqa: F401
                      StrongDirichletSolver)

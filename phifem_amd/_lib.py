@@ -99,6 +99,9 @@ SIGNATURES = {
     "phx_integration_entities": ([_vp, _i, _vp, _pi64], _i),
     "phx_submesh_create": ([_vp, C.POINTER(_vp)], _i),
     "phx_submesh_maps": ([_vp, _vp, _vp], _i),
+    "phx_partition_cells": ([_vp, _i, _vp, _vp, _i], _i),
+    "phx_partition_layout": ([_vp, _i, _vp, _i, _vp, _vp, _i], _i),
+    "phx_submesh_create_from_flags": ([_vp, _vp, _i, C.POINTER(_vp)], _i),
     "phx_assemble_poisson_wd": ([_vp, _d, _d, _vp, _vp, _vp, _i, C.POINTER(_vp)], _i),
     "phx_assemble_poisson_wd_p2": ([_vp, _d, _d, _vp, _i, _vp, _vp, _i, C.POINTER(_vp)], _i),
     "phx_assemble_poisson_sd": ([_vp, _d, _i, _vp, _i, _vp, _i, C.POINTER(_vp)], _i),

@@ -407,6 +407,7 @@ k_assemble_rows(int64_t nv, const int64_t *__restrict__ v2c_ptr, const int32_t *
   for (int k = 0; k < ROW_LDS_SLOTS; ++k) lcol[k * ROW_THREADS + threadIdx.x] = -1;
   constexpr int N = D + 1;
   constexpr double c2 = D == 3 ? 1.0 / 20.0 : 1.0 / 12.0;
+  const bool det = A.slots.emax != nullptr;   // PHX_OPT_DETERMINISTIC (Slots)
   double rhs = 0.0;
   for (int64_t e = v2c_ptr[vtx]; e < v2c_ptr[vtx + 1]; ++e) {
     const int64_t c = v2c_idx[e];
@@ -423,10 +424,15 @@ k_assemble_rows(int64_t nv, const int64_t *__restrict__ v2c_ptr, const int32_t *
     for (int j = 0; j < N; ++j) {
       double k = 0.0;
       for (int d = 0; d < D; ++d) k += G.g[i][d] * G.g[j][d];
-      acc.add(v[j], k * G.vol);
+      // deterministic mode: the cells of a vertex come in the order the adjacency was filled in, which changes from run
+      // to run -- every term goes through the exact accumulation instead of the private sum
+      if (det) slot_add(A.slots, row, v[j], k * G.vol);
+      else acc.add(v[j], k * G.vol);
     }
-    rhs += G.vol * c2 * (sf + A.f[vtx]);  // int f_h N_i
+    if (det) slot_rhs_add(A.slots, A.rhs, row, G.vol * c2 * (sf + A.f[vtx]));
+    else rhs += G.vol * c2 * (sf + A.f[vtx]);  // int f_h N_i
   }
+  if (det) return;
   A.rhs[row] = rhs;
   for (int k = 0; k < ROW_LDS_SLOTS; ++k) {
     const int32_t key = lcol[k * ROW_THREADS + threadIdx.x];
@@ -782,7 +788,7 @@ __global__ void __launch_bounds__(256) k_assemble_cut(int64_t nlist, const int32
       for (int q = 0; q < N; ++q) bq += ud[q] * (i == q ? 2.0 : 1.0) * (sp + ph[i] + ph[q]);
       r = -gam * h1 * h1 * h1 * c3 * bq;                                   // :147 (q part)
     }
-    unsafeAtomicAdd(&A.rhs[row], r);
+    slot_rhs_add(A.slots, A.rhs, row, r);
   }
   // main.py:123-128,150: div(grad(.)) of a P1 function is identically zero.
 }
@@ -1781,6 +1787,14 @@ static int assemble_with_capacity(phx_mesh *m, double pen_coef, double stab_coef
     PHX_HIP(hipMemsetAsync(sl.vals, 0, sizeof(double) * ns, m->stream));
     PHX_HIP(hipMemsetAsync(sl.overflow, 0, sizeof(int), m->stream));
   }
+  // PHX_OPT_DETERMINISTIC on an unstructured mesh or a sub-mesh: the element kernels run twice (exponent pass, exact
+  // accumulation pass; Slots), so matrix and right-hand side are the same bits on every run.  (Kuhn boxes gather most of
+  // their rows in closed form and keep plain atomics for the rest.)
+  bool det = false;
+  const int64_t det_slots = (int64_t)std::max<int64_t>(slot_rows, 1) * W;
+  if (!m->is_box) PHX_CHECK(det_alloc(m, sl, det_slots, s->n, &det));
+  for (int pass = det ? 1 : 0; pass <= (det ? 2 : 0); ++pass) {
+  sl.pass = pass;
   A.slots = sl;
   {
     if (m->is_box) {
@@ -1842,6 +1856,8 @@ static int assemble_with_capacity(phx_mesh *m, double pen_coef, double stab_coef
     else k_assemble_facets<3><<<g, block, 0, m->stream>>>(n_fac, l_fac, A);
   }
   PHX_HIP(hipGetLastError());
+  }   // passes
+  PHX_CHECK(det_finish(m, sl, det_slots, s->n, s->rhs));
   PHX_HIP(hipStreamSynchronize(m->stream));
   for (void *q : later) PHX_HIP(phx_free(q));
   PHX_HIP(phx_free(l_cut)); PHX_HIP(phx_free(l_fac));

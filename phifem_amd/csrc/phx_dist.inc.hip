@@ -2,7 +2,8 @@
 // products) on the solver's HIP stream; included by phx_solve.hip.  RCCL is bound at run time with
 // dlopen (the process already holds PyTorch's librccl; a C host may hold /opt/rocm's), so the
 // library itself has no link-time dependency on it.  SURVEY 8(e): slabs talk point-to-point to at
-// most two neighbours over dedicated xGMI links; the scalar all-reduces carry 1, 2 and 2 doubles.
+// most two neighbours over dedicated xGMI links, the parts of a general partition to up to nranks - 1 peers;
+// the scalar all-reduces carry 1, 2 and 2 doubles.
 #include <dlfcn.h>
 #include <time.h>
 
@@ -157,21 +158,80 @@ __global__ void k_halo_compare(int64_t n, const int64_t *__restrict__ idx, const
   if (i < n && __double_as_longlong(v[idx[i]]) != __double_as_longlong(snap[i])) atomicAdd(bad, 1ull);
 }
 
+// Peer lists of one rank.  Up to two peers (slabs) keep one pack and one unpack launch per peer; with more (a general
+// partition) the index lists are concatenated and the buffers are slices, in peer order, of ONE
+// send and ONE receive arena, so that a single pack and a single unpack launch serve all peers (seven peers would
+// otherwise put 14 tiny kernels into every SpMV).  PHX_DIST_FUSED_PACK=0 keeps the launches per peer (A/B aid).
 struct HaloSpec {
-  int npeers;
-  int peer[2];
-  int64_t nsend[2], nrecv[2];
-  const int64_t *send_idx[2], *recv_idx[2];
-  double *sbuf[2], *rbuf[2];
+  int npeers = 0;
+  std::vector<int> peer;
+  std::vector<int64_t> nsend, nrecv;
+  std::vector<const int64_t *> send_idx, recv_idx;
+  std::vector<double *> sbuf, rbuf;
+  bool fused = false;
+  int64_t tot_send = 0, tot_recv = 0;
+  int64_t *send_cat = nullptr, *recv_cat = nullptr;     // [tot_send], [tot_recv] concatenated positions (fused)
+  double *send_arena = nullptr, *recv_arena = nullptr;  // [tot_send], [tot_recv]
 };
+
+static void halo_free(HaloSpec &H) {
+  (void)phx_free(H.send_arena); (void)phx_free(H.recv_arena);
+  (void)phx_free(H.send_cat); (void)phx_free(H.recv_cat);
+  H.send_arena = H.recv_arena = nullptr;
+  H.send_cat = H.recv_cat = nullptr;
+}
+
+// peers[npeers], counts[2 npeers] = {nsend, nrecv}, idx[2 npeers] = {send_idx, recv_idx} as phx_solve_distributed
+static int halo_setup(HaloSpec &H, const phx_comm *c, int npeers, const int *peers, const int64_t *counts,
+                      const int64_t *const *idx, hipStream_t st) {
+  // (two peers are accepted on any communicator, as before the cap was lifted: a one-rank communicator exchanging with
+  // itself is how the wiring is tested on one GPU)
+  const int cap = c->nranks - 1 > 2 ? c->nranks - 1 : 2;
+  PHX_REQUIRE(npeers >= 0 && npeers <= cap, PHX_ERR_VALUE, "%d peers: a rank of %d has at most %d", npeers, c->nranks, cap);
+  H.npeers = npeers;
+  for (int p = 0; p < npeers; ++p) {
+    PHX_REQUIRE(peers[p] >= 0 && peers[p] < c->nranks, PHX_ERR_VALUE, "peer %d is no rank of the communicator", peers[p]);
+    PHX_REQUIRE(counts[2 * p] >= 0 && counts[2 * p + 1] >= 0, PHX_ERR_VALUE, "negative halo count");
+    H.peer.push_back(peers[p]);
+    H.nsend.push_back(counts[2 * p]); H.nrecv.push_back(counts[2 * p + 1]);
+    H.send_idx.push_back(idx[2 * p]); H.recv_idx.push_back(idx[2 * p + 1]);
+    H.tot_send += counts[2 * p]; H.tot_recv += counts[2 * p + 1];
+  }
+  static const bool fused_env = !(getenv("PHX_DIST_FUSED_PACK") && atoi(getenv("PHX_DIST_FUSED_PACK")) == 0);
+  H.fused = npeers > 2 && fused_env;
+  // (+ one entry per peer: every slice has an address of its own, also an empty one)
+  PHX_HIP(phx_malloc(&H.send_arena, sizeof(double) * (size_t)(H.tot_send + npeers + 1)));
+  PHX_HIP(phx_malloc(&H.recv_arena, sizeof(double) * (size_t)(H.tot_recv + npeers + 1)));
+  if (H.fused) {
+    PHX_HIP(phx_malloc(&H.send_cat, sizeof(int64_t) * (size_t)(H.tot_send + 1)));
+    PHX_HIP(phx_malloc(&H.recv_cat, sizeof(int64_t) * (size_t)(H.tot_recv + 1)));
+  }
+  int64_t so = 0, ro = 0;
+  for (int p = 0; p < npeers; ++p) {
+    // fused: the slices follow the concatenated lists without gaps
+    H.sbuf.push_back(H.send_arena + so + (H.fused ? 0 : p));
+    H.rbuf.push_back(H.recv_arena + ro + (H.fused ? 0 : p));
+    if (H.fused) {
+      if (H.nsend[p] > 0) PHX_HIP(hipMemcpyAsync(H.send_cat + so, H.send_idx[p], sizeof(int64_t) * (size_t)H.nsend[p], hipMemcpyDeviceToDevice, st));
+      if (H.nrecv[p] > 0) PHX_HIP(hipMemcpyAsync(H.recv_cat + ro, H.recv_idx[p], sizeof(int64_t) * (size_t)H.nrecv[p], hipMemcpyDeviceToDevice, st));
+    }
+    so += H.nsend[p]; ro += H.nrecv[p];
+  }
+  return PHX_OK;
+}
 
 // pack on the solver stream `st`, send / receive on `on` (st itself, or the communicator's stream behind an event)
 static int halo_begin(phx_system *s, phx_comm *c, const HaloSpec &H, const double *vec, bool overlap) {
   hipStream_t st = s->mesh->stream;
-  for (int p = 0; p < H.npeers; ++p)
-    if (H.nsend[p] > 0)
-      k_halo_pack<<<dim3((unsigned)phx_div_up(H.nsend[p], 256)), dim3(256), 0, st>>>(
-          H.nsend[p], H.send_idx[p], vec, H.sbuf[p]);
+  if (H.fused) {
+    if (H.tot_send > 0)
+      k_halo_pack<<<dim3((unsigned)phx_div_up(H.tot_send, 256)), dim3(256), 0, st>>>(H.tot_send, H.send_cat, vec, H.send_arena);
+  } else {
+    for (int p = 0; p < H.npeers; ++p)
+      if (H.nsend[p] > 0)
+        k_halo_pack<<<dim3((unsigned)phx_div_up(H.nsend[p], 256)), dim3(256), 0, st>>>(
+            H.nsend[p], H.send_idx[p], vec, H.sbuf[p]);
+  }
   PHX_HIP(hipGetLastError());
   hipStream_t on = st;
   if (overlap) {
@@ -192,10 +252,15 @@ static int halo_begin(phx_system *s, phx_comm *c, const HaloSpec &H, const doubl
 static int halo_end(phx_system *s, phx_comm *c, const HaloSpec &H, double *vec, bool overlap) {
   hipStream_t st = s->mesh->stream;
   if (overlap) PHX_HIP(hipStreamWaitEvent(st, c->ev_recvd, 0));
-  for (int p = 0; p < H.npeers; ++p)
-    if (H.nrecv[p] > 0)
-      k_halo_unpack<<<dim3((unsigned)phx_div_up(H.nrecv[p], 256)), dim3(256), 0, st>>>(
-          H.nrecv[p], H.recv_idx[p], H.rbuf[p], vec);
+  if (H.fused) {
+    if (H.tot_recv > 0)
+      k_halo_unpack<<<dim3((unsigned)phx_div_up(H.tot_recv, 256)), dim3(256), 0, st>>>(H.tot_recv, H.recv_cat, H.recv_arena, vec);
+  } else {
+    for (int p = 0; p < H.npeers; ++p)
+      if (H.nrecv[p] > 0)
+        k_halo_unpack<<<dim3((unsigned)phx_div_up(H.nrecv[p], 256)), dim3(256), 0, st>>>(
+            H.nrecv[p], H.recv_idx[p], H.rbuf[p], vec);
+  }
   PHX_HIP(hipGetLastError());
   return PHX_OK;
 }
@@ -280,27 +345,17 @@ extern "C" int phx_solve_distributed(phx_system *s, phx_comm *c, int npeers, con
                                      int64_t max_iter, double *x_out, int loc, double *stats) {
   phx_mesh *m = s->mesh;
   PHX_HIP(hipSetDevice(m->device));
-  PHX_REQUIRE(npeers >= 0 && npeers <= 2, PHX_ERR_VALUE, "a slab has at most two neighbours");
   hipStream_t st = m->stream;
   HaloSpec H;
-  memset(&H, 0, sizeof(H));
-  H.npeers = npeers;
-  for (int p = 0; p < npeers; ++p) {
-    H.peer[p] = peers[p];
-    H.nsend[p] = counts[2 * p]; H.nrecv[p] = counts[2 * p + 1];
-    H.send_idx[p] = idx[2 * p]; H.recv_idx[p] = idx[2 * p + 1];
-    PHX_HIP(phx_malloc(&H.sbuf[p], sizeof(double) * (size_t)(H.nsend[p] > 0 ? H.nsend[p] : 1)));
-    PHX_HIP(phx_malloc(&H.rbuf[p], sizeof(double) * (size_t)(H.nrecv[p] > 0 ? H.nrecv[p] : 1)));
+  {
+    const int rc = halo_setup(H, c, npeers, peers, counts, idx, st);
+    if (rc != PHX_OK) { (void)hipStreamSynchronize(st); halo_free(H); return rc; }
   }
   static const bool overlap_env = !(getenv("PHX_DIST_OVERLAP") && atoi(getenv("PHX_DIST_OVERLAP")) == 0);
   // a local matter: sends and receives pair up whatever stream each side issues them on
   const bool overlap = overlap_env && c->overlap_ok && c->nranks > 1 && npeers > 0 && c->cs != nullptr;
   auto body = [&]() -> int {
-    if (overlap) {
-      const int64_t *rl[2] = {H.recv_idx[0], H.recv_idx[1]};
-      const int64_t rn[2] = {H.nrecv[0], H.nrecv[1]};
-      PHX_CHECK(phx_spmv_flag_rows(s, npeers, rl, rn));
-    }
+    if (overlap) PHX_CHECK(phx_spmv_flag_rows(s, npeers, H.recv_idx.data(), H.nrecv.data()));   // all receive lists
     PHX_CHECK(prof_reset(s));
     PHX_CHECK(phx_begin_timing(m));
     PHX_CHECK(kr_phase(s, KR_BEGIN, 1, 0));
@@ -327,7 +382,7 @@ extern "C" int phx_solve_distributed(phx_system *s, phx_comm *c, int npeers, con
   if (rc != PHX_ERR_TIMEOUT) {   // a wedged stream would block here for ever
     (void)hipStreamSynchronize(st);
     if (c->cs) (void)hipStreamSynchronize(c->cs);
-    for (int p = 0; p < npeers; ++p) { (void)phx_free(H.sbuf[p]); (void)phx_free(H.rbuf[p]); }
+    halo_free(H);
   }
   return rc;
 }
@@ -339,23 +394,16 @@ extern "C" int phx_halo_selftest(phx_system *s, phx_comm *c, int npeers, const i
                                  const int64_t *counts, const int64_t *const *idx, double *vec) {
   PHX_HIP(hipSetDevice(s->mesh->device));
   HaloSpec H;
-  memset(&H, 0, sizeof(H));
-  H.npeers = npeers;
-  for (int p = 0; p < npeers; ++p) {
-    H.peer[p] = peers[p];
-    H.nsend[p] = counts[2 * p]; H.nrecv[p] = counts[2 * p + 1];
-    H.send_idx[p] = idx[2 * p]; H.recv_idx[p] = idx[2 * p + 1];
-    PHX_HIP(phx_malloc(&H.sbuf[p], sizeof(double) * (size_t)(H.nsend[p] > 0 ? H.nsend[p] : 1)));
-    PHX_HIP(phx_malloc(&H.rbuf[p], sizeof(double) * (size_t)(H.nrecv[p] > 0 ? H.nrecv[p] : 1)));
-  }
-  int rc = halo_exchange(s, c, H, vec);
+  int rc = halo_setup(H, c, npeers, peers, counts, idx, s->mesh->stream);
+  if (rc != PHX_OK) { (void)hipStreamSynchronize(s->mesh->stream); halo_free(H); return rc; }
+  rc = halo_exchange(s, c, H, vec);
   if (rc == PHX_OK) rc = stream_sync_watchdog(s->mesh->stream, "halo self-test");
   // ... and once more through the OVERLAPPED path: the received entries are cleared, exchanged again on the
   // communicator's stream behind the two events, and must come back bit for bit.  Every rank makes both exchanges (they
   // pair up), each decides for itself (`overlap_ok`: a local matter, see phx_solve_distributed).
   if (rc == PHX_OK && c->nranks > 1 && npeers > 0 && c->cs != nullptr) {
     hipStream_t st = s->mesh->stream;
-    double *snap[2] = {nullptr, nullptr};
+    std::vector<double *> snap((size_t)npeers, nullptr);
     unsigned long long *bad = nullptr;
     bool ok = phx_malloc(&bad, sizeof(unsigned long long)) == hipSuccess;
     for (int p = 0; p < npeers && ok; ++p) ok = phx_malloc(&snap[p], sizeof(double) * (size_t)(H.nrecv[p] > 0 ? H.nrecv[p] : 1)) == hipSuccess;
@@ -393,6 +441,6 @@ extern "C" int phx_halo_selftest(phx_system *s, phx_comm *c, int npeers, const i
     for (int p = 0; p < npeers; ++p) (void)phx_free(snap[p]);
   }
   (void)hipStreamSynchronize(s->mesh->stream);
-  for (int p = 0; p < npeers; ++p) { (void)phx_free(H.sbuf[p]); (void)phx_free(H.rbuf[p]); }
+  halo_free(H);
   return rc;
 }

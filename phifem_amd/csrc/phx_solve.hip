@@ -1783,6 +1783,16 @@ __global__ void k_mark_positions(int64_t n, const int64_t *__restrict__ idx, uin
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i < n) isg[idx[i]] = 1;
 }
+__global__ void k_bnd_keys(int64_t n, const int32_t *__restrict__ rec, uint32_t *__restrict__ key, int32_t *__restrict__ idx) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i < n) { key[i] = (uint32_t)rec[6 * i]; idx[i] = (int32_t)i; }
+}
+__global__ void k_bnd_gather(int64_t n, const int32_t *__restrict__ idx, const int32_t *__restrict__ rec, int32_t *__restrict__ out) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t *q = rec + 6 * (int64_t)idx[i];
+  for (int k = 0; k < 6; ++k) out[6 * i + k] = q[k];
+}
 static int phx_spmv_flag_rows(phx_system *s, int nlists, const int64_t *const *idx, const int64_t *counts) {
   hipStream_t st = s->mesh->stream;
   PHX_HIP(phx_free(s->bnd)); PHX_HIP(phx_free(s->bnd_rec));
@@ -1818,6 +1828,31 @@ static int phx_spmv_flag_rows(phx_system *s, int nlists, const int64_t *const *i
       if (s->nbnd == 0) break;
       PHX_HIP(phx_malloc(&s->bnd_rec, sizeof(int32_t) * 6 * (size_t)s->nbnd));
     }
+  }
+  if (s->mesh->deterministic && s->nbnd > 1) {
+    // the records land in the order the counter was reached, which changes from run to run, and the blocks of
+    // k_spmv_bnd sum their dot-product partials over runs of records: PHX_OPT_DETERMINISTIC puts them in row order
+    const int64_t nb2 = s->nbnd;
+    uint32_t *k1 = nullptr, *k2 = nullptr;
+    int32_t *i1 = nullptr, *i2 = nullptr, *rec2 = nullptr;
+    void *tmp = nullptr;
+    size_t bytes = 0;
+    PHX_HIP(phx_malloc(&k1, sizeof(uint32_t) * (size_t)nb2));
+    PHX_HIP(phx_malloc(&k2, sizeof(uint32_t) * (size_t)nb2));
+    PHX_HIP(phx_malloc(&i1, sizeof(int32_t) * (size_t)nb2));
+    PHX_HIP(phx_malloc(&i2, sizeof(int32_t) * (size_t)nb2));
+    PHX_HIP(phx_malloc(&rec2, sizeof(int32_t) * 6 * (size_t)nb2));
+    PHX_HIP(phx_sort_pairs(nullptr, bytes, k1, k2, i1, i2, (size_t)nb2, 0, 32, st));
+    PHX_HIP(phx_malloc(&tmp, bytes ? bytes : 16));
+    const dim3 g2((unsigned)phx_div_up(nb2, 256));
+    k_bnd_keys<<<g2, dim3(256), 0, st>>>(nb2, s->bnd_rec, k1, i1);
+    PHX_HIP(phx_sort_pairs(tmp, bytes, k1, k2, i1, i2, (size_t)nb2, 0, 32, st));   // a row has one record: keys are unique
+    k_bnd_gather<<<g2, dim3(256), 0, st>>>(nb2, i2, s->bnd_rec, rec2);
+    PHX_HIP(hipGetLastError());
+    PHX_HIP(hipStreamSynchronize(st));
+    PHX_HIP(phx_free(s->bnd_rec));
+    s->bnd_rec = rec2;
+    PHX_HIP(phx_free(k1)); PHX_HIP(phx_free(k2)); PHX_HIP(phx_free(i1)); PHX_HIP(phx_free(i2)); PHX_HIP(phx_free(tmp));
   }
   PHX_HIP(hipStreamSynchronize(st));
   PHX_HIP(phx_free(isg)); PHX_HIP(phx_free(cnt));

@@ -70,24 +70,18 @@ __global__ void k_sub_compose(int64_t nvs, const int32_t *__restrict__ v_map, co
 // host -- 4.5 GB at 256^3 -- and rebuilt the topology with a host sort): cell and vertex compaction by ordered
 // selects, the facet numbering by phx_topology_build_device, the tag transfer by two gather kernels.  Only the two
 // maps the API returns (phx_submesh_maps) are copied to the host.
-extern "C" int phx_submesh_create(phx_mesh *m, phx_mesh **sub_out) {
-  PHX_HIP(hipSetDevice(m->device));
-  PHX_REQUIRE(m->have_cell_tags && m->have_facet_tags, PHX_ERR_VALUE,
-              "cell and facet tags must be computed before the sub-mesh");
+// Sub-mesh of the `ncs` parent cells listed (ascending) in the device array c_map, with the parent's cell and facet
+// tags transferred and the two maps on the host; *v_map / *renum (device, parent vertex <-> sub-mesh vertex) go to
+// the caller, c_map stays the caller's.
+static int submesh_from_cells(phx_mesh *m, const int32_t *c_map, int64_t ncs, phx_mesh **sub_out, int32_t **v_map_out,
+                              int32_t **renum_out) {
   hipStream_t st = m->stream;
   const int nvpc = m->ci.nvpc, nfpc = m->ci.nfpc;
   const dim3 block(256);
-  // mesh_scripts.py:637: omega_h_cells = unique(find(1) U find(2))
-  int32_t *c_map = nullptr, *v_map = nullptr, *renum = nullptr, *scells = nullptr, *tmp32 = nullptr;
+  int32_t *v_map = nullptr, *renum = nullptr, *scells = nullptr, *tmp32 = nullptr;
   uint8_t *touched = nullptr;
   double *sx = nullptr;
-  int64_t ncs = 0, nvs = 0;
-  PHX_CHECK(phx_select_indices(st, m->nc, SelOmegaCells{m->cell_tags}, &c_map, &ncs));
-  if (ncs == 0) {
-    PHX_HIP(phx_free(c_map));
-    phx_set_error("no cell is tagged 1 or 2: empty sub-mesh");
-    return PHX_ERR_VALUE;
-  }
+  int64_t nvs = 0;
   PHX_HIP(phx_malloc(&touched, (size_t)m->nv));
   PHX_HIP(hipMemsetAsync(touched, 0, (size_t)m->nv, st));
   k_sub_touch<<<dim3((unsigned)phx_div_up(ncs * nvpc, 256)), block, 0, st>>>(ncs, nvpc, c_map, m->cells, touched);
@@ -103,7 +97,7 @@ extern "C" int phx_submesh_create(phx_mesh *m, phx_mesh **sub_out) {
   phx_mesh *s = nullptr;
   int rc = phx_mesh_create_from(m->gdim, m->cell_type, nvs, sx, ncs, scells, PHX_DEVICE, m->device, &s);
   PHX_HIP(phx_free(scells)); PHX_HIP(phx_free(sx)); PHX_HIP(phx_free(touched));
-  if (rc != PHX_OK) { (void)phx_free(c_map); (void)phx_free(v_map); (void)phx_free(renum); return rc; }
+  if (rc != PHX_OK) { (void)phx_free(v_map); (void)phx_free(renum); return rc; }
   // tags: cells through c_map (mesh_scripts.py:238-239,265-268); facets through the first occurrence (:244-260)
   PHX_HIP(phx_malloc(&tmp32, sizeof(int32_t) * (size_t)std::max<int64_t>(ncs, s->nf)));
   k_sub_cell_tags<<<dim3((unsigned)phx_div_up(ncs, 256)), block, 0, st>>>(ncs, c_map, m->cell_tags, tmp32);
@@ -114,6 +108,34 @@ extern "C" int phx_submesh_create(phx_mesh *m, phx_mesh **sub_out) {
   PHX_HIP(hipStreamSynchronize(st));
   PHX_CHECK(phx_set_tags(s, 1, tmp32, PHX_DEVICE));
   PHX_HIP(phx_free(tmp32));
+  s->c_map_h = (int32_t *)malloc(sizeof(int32_t) * (size_t)ncs);
+  s->v_map_h = (int32_t *)malloc(sizeof(int32_t) * (size_t)nvs);
+  PHX_HIP(hipMemcpy(s->c_map_h, c_map, sizeof(int32_t) * (size_t)ncs, hipMemcpyDeviceToHost));
+  PHX_HIP(hipMemcpy(s->v_map_h, v_map, sizeof(int32_t) * (size_t)nvs, hipMemcpyDeviceToHost));
+  *sub_out = s; *v_map_out = v_map; *renum_out = renum;
+  return PHX_OK;
+}
+
+extern "C" int phx_submesh_create(phx_mesh *m, phx_mesh **sub_out) {
+  PHX_HIP(hipSetDevice(m->device));
+  PHX_REQUIRE(m->have_cell_tags && m->have_facet_tags, PHX_ERR_VALUE,
+              "cell and facet tags must be computed before the sub-mesh");
+  hipStream_t st = m->stream;
+  const dim3 block(256);
+  // mesh_scripts.py:637: omega_h_cells = unique(find(1) U find(2))
+  int32_t *c_map = nullptr, *v_map = nullptr, *renum = nullptr;
+  int64_t ncs = 0;
+  PHX_CHECK(phx_select_indices(st, m->nc, SelOmegaCells{m->cell_tags}, &c_map, &ncs));
+  if (ncs == 0) {
+    PHX_HIP(phx_free(c_map));
+    phx_set_error("no cell is tagged 1 or 2: empty sub-mesh");
+    return PHX_ERR_VALUE;
+  }
+  phx_mesh *s = nullptr;
+  const int rc = submesh_from_cells(m, c_map, ncs, &s, &v_map, &renum);
+  PHX_HIP(phx_free(c_map));
+  if (rc != PHX_OK) return rc;
+  const int64_t nvs = s->nv;
   s->is_submesh = true;
   if (m->is_box) {
     s->on_box_lattice = true;
@@ -130,19 +152,16 @@ extern "C" int phx_submesh_create(phx_mesh *m, phx_mesh **sub_out) {
     k_sub_compose<<<dim3((unsigned)phx_div_up(nvs, 256)), block, 0, st>>>(nvs, v_map, m->v2lat, s->v2lat, s->lat2v);
     PHX_HIP(hipStreamSynchronize(st));
   }
-  s->c_map_h = (int32_t *)malloc(sizeof(int32_t) * (size_t)ncs);
-  s->v_map_h = (int32_t *)malloc(sizeof(int32_t) * (size_t)nvs);
-  PHX_HIP(hipMemcpy(s->c_map_h, c_map, sizeof(int32_t) * (size_t)ncs, hipMemcpyDeviceToHost));
-  PHX_HIP(hipMemcpy(s->v_map_h, v_map, sizeof(int32_t) * (size_t)nvs, hipMemcpyDeviceToHost));
-  PHX_HIP(phx_free(c_map));
   if (!m->is_box) { PHX_HIP(phx_free(v_map)); PHX_HIP(phx_free(renum)); }
   *sub_out = s;
   return PHX_OK;
 }
 
 extern "C" int phx_submesh_maps(phx_mesh *sub, int32_t *c_map, int32_t *v_map) {
-  PHX_REQUIRE(sub->is_submesh, PHX_ERR_VALUE, "not a sub-mesh");
+  PHX_REQUIRE(sub->c_map_h != nullptr && sub->v_map_h != nullptr, PHX_ERR_VALUE, "not a sub-mesh");
   if (c_map) memcpy(c_map, sub->c_map_h, sizeof(int32_t) * (size_t)sub->nc);
   if (v_map) memcpy(v_map, sub->v_map_h, sizeof(int32_t) * (size_t)sub->nv);
   return PHX_OK;
 }
+
+#include "phx_partition.inc.hip"

@@ -162,11 +162,110 @@ def ownership_and_halos(torch, backend, plane_size, k0, P0, P1, rank, world, n_p
     return own_s, halos
 
 
-class DistributedSolver:
-    """BiCGStab (right Jacobi) on a slab-partitioned system."""
+def partition_ownership_and_halos(torch, dist, backend, owned_v, owner_v, v_map, nv_global, rank, world,
+                                  stage_cpu=False, cache=None):
+    """General counterpart of `ownership_and_halos` for a partition of an unstructured mesh:
+    instead of plane arithmetic it takes, per LOCAL vertex, the owned mask `owned_v`, the owning rank `owner_v` and
+    the global vertex `v_map` (ascending).  Backend-agnostic like the slab version.
 
-    def __init__(self, backend, dist, torch, rank, world, plane_size, k0, P0, P1, n_planes_local,
-                 rtol=1e-8, max_iter=20000, check_every=8):
+    Receive set of this rank: its locally active DoFs at vertices it does not own, grouped by owner, each group in
+    ascending global DoF id  gid = vertex * nblk + kind.  The send lists are what the peers ask for: the per-owner
+    counts of all ranks go round first (one all-gather), then every rank sends each owner the gids it wants and the
+    owner maps them to its solver positions.  Point-to-point, staged through the host where the backend cannot move
+    device tensors (gloo), as `DistributedSolver._sendrecv` does.  `cache` (a dict, filled on the first call) keeps
+    the gid lists of both directions, so that later calls of the same problem only map them to the solver positions
+    of the current system and exchange nothing."""
+    dev = backend.perm.device
+    nv, n = backend.nv, backend.n
+    nblk = len(backend.dof_blocks)
+    owned_v = torch.as_tensor(owned_v).to(dev).bool()
+    owner_v = torch.as_tensor(owner_v).to(dev).long()
+    v_map = torch.as_tensor(v_map).to(dev).long()
+    owned_a = torch.zeros(n, dtype=torch.bool, device=dev)
+    for dof in backend.dof_blocks:
+        act = dof >= 0
+        owned_a[dof[act]] = owned_v[act]
+    iperm = torch.empty(n, dtype=torch.long, device=dev)
+    iperm[backend.perm] = torch.arange(n, device=dev)
+    own_s = owned_a[backend.perm].to(torch.uint8).contiguous()
+
+    # what this rank wants: (owner, gid, position), ordered by (owner, gid)
+    q, gid, pos = [], [], []
+    for kind, dof in enumerate(backend.dof_blocks):
+        v = torch.nonzero(~owned_v & (dof >= 0)).flatten()
+        q.append(owner_v[v])
+        gid.append(v_map[v] * nblk + kind)
+        pos.append(iperm[dof[v]])
+    q, gid, pos = torch.cat(q), torch.cat(gid), torch.cat(pos)
+    if q.numel() and int(q.min()) < 0:
+        raise RuntimeError(f"rank {rank}: an active DoF sits on a vertex nobody owns")
+    o1 = torch.sort(gid, stable=True)[1]
+    o2 = torch.sort(q[o1], stable=True)[1]
+    order = o1[o2]
+    q, gid, pos = q[order], gid[order], pos[order]
+    counts = torch.bincount(q, minlength=world)[:world] if q.numel() else torch.zeros(world, dtype=torch.long, device=dev)
+    offs = [0] + torch.cumsum(counts, 0).tolist()
+    recv_gid = {r: gid[offs[r]:offs[r + 1]] for r in range(world) if offs[r + 1] > offs[r]}
+    recv_pos = {r: pos[offs[r]:offs[r + 1]] for r in recv_gid}
+    if rank in recv_gid:
+        raise RuntimeError(f"rank {rank}: a vertex it owns is marked as not owned")
+
+    if cache is not None and "send_gid" in cache:
+        if sorted(cache["recv_gid"]) != sorted(recv_gid) or not all(
+                torch.equal(cache["recv_gid"][r], recv_gid[r]) for r in recv_gid):
+            raise RuntimeError(f"rank {rank}: the receive set changed between two solves of one problem")
+        send_gid = cache["send_gid"]
+    else:
+        ctl = dev if (dist.get_backend() == "nccl" and not stage_cpu) else torch.device("cpu")
+        mine = counts.to(ctl)
+        table = [torch.empty_like(mine) for _ in range(world)]
+        dist.all_gather(table, mine)                      # sizes first: table[r][o] = entries rank r wants from rank o
+        W = torch.stack(table).cpu()
+        ops, bufs, staged = [], {}, []
+        for o in range(world):
+            if o == rank:
+                continue
+            if int(W[rank, o]) > 0:
+                t = recv_gid[o].to(ctl).contiguous()
+                staged.append(t)
+                ops.append(dist.P2POp(dist.isend, t, o))
+            if int(W[o, rank]) > 0:
+                bufs[o] = torch.empty(int(W[o, rank]), dtype=torch.long, device=ctl)
+                ops.append(dist.P2POp(dist.irecv, bufs[o], o))
+        if ops:
+            for r in dist.batch_isend_irecv(ops):
+                r.wait()
+        send_gid = {o: b.to(dev) for o, b in bufs.items()}
+        if cache is not None:
+            cache["recv_gid"], cache["send_gid"] = recv_gid, send_gid
+
+    # the owner's side: gid -> local vertex -> solver position; it must own an ACTIVE DoF there
+    g2l = torch.full((int(nv_global),), -1, dtype=torch.long, device=dev)
+    g2l[v_map] = torch.arange(nv, device=dev)
+    dofs = torch.stack(list(backend.dof_blocks)) if nv else torch.zeros((nblk, 0), dtype=torch.long, device=dev)
+    send_pos = {}
+    for o, g in send_gid.items():
+        if int(g.min()) < 0 or int(g.max()) >= nblk * int(nv_global):
+            raise RuntimeError(f"rank {rank}: rank {o} asks for a DoF id out of range")
+        vl = g2l[g // nblk]
+        d = dofs[g % nblk, vl.clamp(min=0)]
+        if bool((vl < 0).any()) or bool((d < 0).any()) or not bool(owned_v[vl].all()):
+            raise RuntimeError(f"rank {rank}: rank {o} asks for DoFs that are not active rows this rank owns")
+        send_pos[o] = iperm[d]
+    empty = torch.zeros(0, dtype=torch.long, device=dev)
+    halos = []
+    for o in sorted(set(recv_gid) | set(send_gid)):
+        halos.append({"peer": o, "send": (send_pos.get(o, empty), send_gid.get(o, empty)),
+                      "recv": (recv_pos.get(o, empty), recv_gid.get(o, empty))})
+    return own_s, halos
+
+
+class DistributedSolver:
+    """BiCGStab (right Jacobi) on a partitioned system: slabs (plane arithmetic) or, with `layout` = the
+    (ownership mask, halos) of `partition_ownership_and_halos`, a general partition with any number of peers."""
+
+    def __init__(self, backend, dist, torch, rank, world, plane_size=None, k0=0, P0=0, P1=0, n_planes_local=0,
+                 rtol=1e-8, max_iter=20000, check_every=8, layout=None):
         self.b, self.dist, self.torch = backend, dist, torch
         self.rank, self.world = rank, world
         # rehearsal mode: gloo cannot move CUDA tensors point-to-point, so stage through the host
@@ -174,8 +273,11 @@ class DistributedSolver:
                               and backend.perm.device.type == "cuda")
         self.rtol, self.max_iter, self.check_every = rtol, max_iter, check_every
         dev = backend.perm.device
-        self.own, self.halos = ownership_and_halos(torch, backend, plane_size, k0, P0, P1, rank,
-                                                   world, n_planes_local)
+        if layout is not None:
+            self.own, self.halos = layout
+        else:
+            self.own, self.halos = ownership_and_halos(torch, backend, plane_size, k0, P0, P1, rank,
+                                                       world, n_planes_local)
         n = backend.n
         self.work = torch.zeros(10 * n, dtype=torch.float64, device=dev)
         self.scal = torch.zeros(SCAL_DOUBLES, dtype=torch.float64, device=dev)
@@ -436,6 +538,7 @@ class DistributedKrylov:
         self.path = "python"
         self.library = None  # file the library's RCCL entry points are bound to (native loop)
         self.overlap = False  # halo exchanges overlapped with the SpMV (the self-test has seen that path deliver)
+        self.last_solver = None  # the DistributedSolver of the last solve (its halos say who the peers were)
 
     def agree_on_exterior(self):
         """`len(exterior_cells) == 0` (mesh_scripts.py:469) must be decided over ALL slabs."""
@@ -527,13 +630,10 @@ class DistributedKrylov:
                 ok = ok and bool(torch.equal(vec[h["recv"][0]], h["recv"][1].to(torch.float64)))
         return ok
 
-    def solve(self, out, profile_spmv=False):
-        from . import _lib as L
+    def _build_solver(self, backend):
+        """Ownership, halos and preconditioner of the slab layout."""
         prob = self.prob
         lay = prob.lay
-        backend = HipBackend(prob.solver, self.dev, blocks=getattr(prob, "n_blocks", None))
-        backend.use_current_stream()
-        L.check(L.lib.phx_set_option(prob.mesh._h, L.OPT_PROFILE_SPMV, int(profile_spmv)))
         plane = getattr(prob, "plane_vertices", None) or (prob.nxy + 1) * (prob.nxy + 1)
         ds = DistributedSolver(backend, self.dist, self.torch, prob.rank, prob.world, plane,
                                lay["k0"], lay["P0"], lay["P1"], lay["k1"] - lay["k0"] + 1,
@@ -544,6 +644,15 @@ class DistributedKrylov:
             n_per = lay["L1"] - lay["L0"]
             zb = [r * n_per for r in range(prob.world)] + [lay["nz"] + 1]
             backend.setup_exact_precond(self.dist, prob.rank, prob.world, zb, stage_cpu=ds.stage_cpu)
+        return ds
+
+    def solve(self, out, profile_spmv=False):
+        from . import _lib as L
+        prob = self.prob
+        backend = HipBackend(prob.solver, self.dev, blocks=getattr(prob, "n_blocks", None))
+        backend.use_current_stream()
+        L.check(L.lib.phx_set_option(prob.mesh._h, L.OPT_PROFILE_SPMV, int(profile_spmv)))
+        ds = self._build_solver(backend)
         if self.native is None:
             with Watchdog("RCCL communicator set-up + halo self-test", prob.rank):
                 self._init_native()
@@ -553,6 +662,7 @@ class DistributedKrylov:
                     ov = C.c_int(0)
                     if L.lib.phx_comm_overlap(self.comm, C.byref(ov)) == 0:
                         self.overlap = bool(ov.value)
+        self.last_solver = ds
         if not self.native:
             self.path = "python"
             return ds.solve(out, profile_spmv=profile_spmv)
@@ -570,3 +680,21 @@ class DistributedKrylov:
                 "n_owned": ds.n_owned, "spmv_avg_s": st[4], "spmv_timed": int(st[5]),
                 "converged": bool(st[6]), "precond_all": bool(st[7]),
                 "precond_exact": bool(st[7]) and backend.exact}
+
+
+class PartitionedKrylov(DistributedKrylov):
+    """`DistributedKrylov` for `PartitionedProblem`: the layout of a general partition (ownership by vertex, any
+    number of peers) and the Jacobi path -- no lattice preconditioner exists for an unstructured mesh."""
+
+    def __init__(self, prob):
+        super().__init__(prob)
+        self.halo_cache = {}
+
+    def _build_solver(self, backend):
+        prob = self.prob
+        stage = bool(self.dist.get_backend() == "gloo" and backend.perm.device.type == "cuda")
+        layout = partition_ownership_and_halos(self.torch, self.dist, backend, prob.owned_v, prob.owner_v, prob.v_map,
+                                               prob.bg.nv, prob.rank, prob.world, stage_cpu=stage,
+                                               cache=self.halo_cache)
+        return DistributedSolver(backend, self.dist, self.torch, prob.rank, prob.world, rtol=prob.rtol,
+                                 max_iter=prob.max_iter, layout=layout)

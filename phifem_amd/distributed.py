@@ -1,4 +1,7 @@
-"""Slab-partitioned problem driver: one process per GPU (torch.distributed over RCCL/xGMI).
+"""Partitioned problem drivers: one process per GPU (torch.distributed over RCCL/xGMI).
+
+Two layouts.  SLABS (`SlabProblem` and its subclasses) serve uniform Kuhn lattices and are described below; a GENERAL
+PARTITION (`PartitionedProblem`, at the end of this file) serves any triangle or tetrahedron mesh.
 
 The background box is cut into slabs of cube layers along the last axis; every rank generates
 its slab plus GHOST cube layers on the device (same global coordinates bit for bit), tags and
@@ -104,7 +107,10 @@ class SlabProblem:
         else:
             st = self.dk.solve(self.out, profile_spmv=profile_spmv)
             n_owned = st["n_owned"]
-        t = mesh.timings()
+        return self._step_result(mesh.timings(), info, st, n_owned)
+
+    def _step_result(self, t, info, st, n_owned):
+        """The dict `step()` returns; t = stage timings of the mesh that was tagged."""
         pc = self.solver.precond_info()
         return {
             "n_active_owned": n_owned, "iterations": st["iterations"], "relres": st["relres"],
@@ -311,3 +317,126 @@ class P2Problem(SlabProblem):
 
     def _tag_levelset(self):
         return self.phi1
+
+
+class PartitionedProblem:
+    """P1 x P1 weak-Dirichlet Poisson (box mode) on ANY triangle or tetrahedron background mesh -- graded, unstructured,
+    vertices and cells in any order -- partitioned over the ranks (the reference is serial,
+    src/phifem/mesh_scripts.py:264 "TODO ... parallel computing").
+
+    Data model: every rank is handed the WHOLE mesh (`x`, `cells`) and the nodal data `phi`, `f`, `u_D` in the caller's
+    numbering, as `ArraySlabProblem` is handed its vertex array, and tags the whole mesh itself, so no tag ever crosses
+    a rank.  THE BACKGROUND MESH THEREFORE HAS TO FIT ONE GPU.  The cells are split by recursive coordinate bisection
+    (`partition_cells`, weight 1 for cells tagged 1 / 2, 0 for the exterior); a vertex belongs to the part of the
+    lowest-numbered cell of Omega_h that contains it; a rank works on four layers of cells around its vertices
+    (`phx_partition_layout`), with the tags of the whole mesh transferred, and assembles every row it owns -- and the
+    diagonal of every column those rows refer to -- completely from them: no matrix entry crosses a rank.  The solve is Jacobi-BiCGStab with a halo exchange with up to world - 1 peers.
+    A rank that owns nothing holds an empty system and still joins every collective."""
+
+    single_layer_cut = True   # as SlabProblem: one layer of cut cells
+
+    def __init__(self, cell_type, x, cells, phi, f, u_D, rank=0, world=1, device=0, rtol=1e-8, max_iter=20000,
+                 deterministic=False, balance="domain"):
+        """balance = "domain" (default): the parts share the cells of Omega_h (weight 1 for tags 1 / 2, 0 outside);
+        "cells": they share the background cells -- parts away from the domain then own nothing."""
+        if cell_type not in ("triangle", "tetrahedron"):
+            raise NotImplementedError("PartitionedProblem serves triangle and tetrahedron meshes")
+        if balance not in ("domain", "cells"):
+            raise ValueError("balance is 'domain' or 'cells'")
+        self.balance = balance
+        self.cell_type = cell_type
+        self._x = np.ascontiguousarray(x, dtype=np.float64)
+        self._cells = np.ascontiguousarray(cells, dtype=np.int32)
+        nv = self._x.shape[0]
+        self._phi, self._f, self._uD = (np.ascontiguousarray(a, dtype=np.float64) for a in (phi, f, u_D))
+        for a, name in ((self._phi, "phi"), (self._f, "f"), (self._uD, "u_D")):
+            if a.shape != (nv,):
+                raise ValueError(f"{name} has shape {a.shape}, the mesh has {nv} vertices")
+        self.rank, self.world, self.device = int(rank), int(world), int(device)
+        self.rtol, self.max_iter, self.deterministic = rtol, max_iter, bool(deterministic)
+        self.setup_s = {}
+
+    def _tag_background(self):
+        staged = _tag_cells(self.bg, NodalFunction(self.phi_g), 1, single_layer_cut=self.single_layer_cut)
+        _tag_facets(self.bg, staged, 1)
+
+    def _extract(self):
+        """Local mesh with the tags of the background mesh, the nodal data on it and the solver."""
+        import torch
+        from .partition import local_mesh
+        dev = torch.device("cuda", self.device)
+        self.mesh, self.c_map, self.v_map = local_mesh(self.bg, self.flags)
+        take = torch.from_numpy(self.v_map.astype(np.int64)).to(dev)
+        self.phi, self.f, self.u_D = (g[take].contiguous() for g in (self.phi_g, self.f_g, self.uD_g))
+        self.owner_v = self.owner[take]
+        self.owned_v = self.owner_v == self.rank
+        self.out = torch.empty(2 * self.mesh.nv, dtype=torch.float64, device=dev)
+        pc = self.part[torch.from_numpy(self.c_map.astype(np.int64)).to(dev)]
+        self.owned_cells = int((pc == self.rank).sum().item())
+        self.ghost_cells = int(self.c_map.size) - self.owned_cells
+        # a rank that owns nothing gets an empty system and still joins every collective
+        L.check(L.lib.phx_set_option(self.mesh._h, L.OPT_ALLOW_EMPTY, 1))
+        self.solver = PhiFEMSolver(self.mesh, deterministic=self.deterministic)
+
+    def setup(self):
+        import time
+        import torch
+        import warnings
+        from .mesh import Mesh
+        from .partition import partition_cells, partition_layout
+        dev = torch.device("cuda", self.device)
+        self.bg = Mesh.from_arrays(self.cell_type, self._x, self._cells, device=self.device)
+        self.phi_g, self.f_g, self.uD_g = (torch.from_numpy(a).to(dev) for a in (self._phi, self._f, self._uD))
+        torch.cuda.synchronize(dev)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            self._tag_background()
+        self.tag_timings = self.bg.timings()
+        t0 = time.perf_counter()
+        tags = torch.empty(self.bg.nc, dtype=torch.int32, device=dev)
+        L.check(L.lib.phx_mesh_get_array(self.bg._h, L.ARR_CELL_TAGS, C.c_void_p(tags.data_ptr()), L.DEVICE))
+        weights = ((tags == 1) | (tags == 2)).to(torch.int32).contiguous()
+        self.part = partition_cells(self.bg, self.world, weights if self.balance == "domain" else None)
+        if self.balance != "domain":   # (the all-ones weights are made inside the library; the result lives on the host)
+            self.part = torch.from_numpy(self.part).to(dev)
+        t1 = time.perf_counter()
+        self.owner, self.flags = partition_layout(self.bg, self.world, self.part, self.rank)
+        self._extract()
+        torch.cuda.synchronize(dev)
+        t2 = time.perf_counter()
+        self.setup_s = {"partition": t1 - t0, "layout": t2 - t1}
+        if self.world > 1:
+            from .dist_solver import PartitionedKrylov
+            self.dk = PartitionedKrylov(self)
+
+    def step(self, profile_spmv=False):
+        """assemble -> solve on the local mesh.  The level-set is fixed at construction, so tagging, partition and local
+        mesh are the ones of `setup()` (the "tag" stage time reported is that tagging of the whole mesh)."""
+        t = dict(self.tag_timings)
+        info = self.solver.assemble(self.phi, self.f, self.u_D)
+        t["assemble"] = self.mesh.timings()["assemble"]
+        n_peers = halo_entries = 0
+        if self.world == 1:
+            self.solver.solve(rtol=self.rtol, max_iter=self.max_iter, out=self.out, profile_spmv=profile_spmv)
+            st = self.solver.stats
+            n_owned = info["n_active"]
+        else:
+            st = self.dk.solve(self.out, profile_spmv=profile_spmv)
+            n_owned = st["n_owned"]
+            halos = self.dk.last_solver.halos
+            n_peers = len(halos)
+            halo_entries = sum(int(h["recv"][0].numel()) for h in halos)
+        res = self._step_result(t, info, st, n_owned)
+        res.update({"n_peers": n_peers, "halo_entries": halo_entries, "ghost_cells": self.ghost_cells,
+                    "owned_cells": self.owned_cells,
+                    "ghost_cells_per_owned_cell": self.ghost_cells / max(self.owned_cells, 1)})
+        return res
+
+    _step_result = SlabProblem._step_result
+
+    def solution(self):
+        """(caller vertex ids, u, p) of the vertices this rank OWNS."""
+        nv = self.mesh.nv
+        w = self.out.cpu().numpy()
+        own = self.owned_v.cpu().numpy()
+        return self.v_map[own].astype(np.int64), w[:nv][own], w[nv:][own]

@@ -62,8 +62,8 @@ class PhiFEMSolver:
         an int >= 5: H / h.  Built on the first solve; a correction that was asked for and could not be built is
         reported by a RuntimeWarning and `stats["coarse_reason"]`.
 
-        deterministic=True (PHX_OPT_DETERMINISTIC): bit-reproducible assembly (degree 2: the element kernels run
-        twice and accumulate exactly) and Krylov dot products -- the same matrix bits, iteration count and solution
+        deterministic=True (PHX_OPT_DETERMINISTIC): bit-reproducible assembly (degree 2, and degree 1 on meshes that
+        are not Kuhn boxes: the element kernels run twice and accumulate exactly) and Krylov dot products -- the same matrix bits, iteration count and solution
         on every run; costs one more pass of the element kernels.
 
         mesh: a tagged `phifem_amd.Mesh` (box mode) or the sub-mesh returned by
