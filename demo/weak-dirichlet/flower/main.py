@@ -8,6 +8,8 @@ single-layer cut), same two modes --
     python main.py bg     solve on the background mesh (box mode, one-sided ds(100))
     python main.py sub    solve on the sub-mesh of the cells tagged 1/2
 
+(--cell-type quadrilateral: the same forms in Q1 x Q1 on the 200 x 200 squares themselves, degree 1)
+
 -- with phifem_amd in place of dolfinx / PETSc / MUMPS.  Writes <mode>_output/solution.npz
 (vertex coordinates, cells, u_h, p_h, cell tags) instead of XDMF.
 """
@@ -33,12 +35,13 @@ def main():
                     help="solve on the background mesh (bg) or on a submesh (sub)")
     ap.add_argument("--cells", type=int, default=200, help="background squares per direction")
     ap.add_argument("--degree", type=int, default=1, choices=[1, 2], help="primal degree")
+    ap.add_argument("--cell-type", choices=["triangle", "quadrilateral"], default="triangle")
     args = ap.parse_args()
     out_dir = os.path.join(HERE, args.mesh_type + "_output")
     os.makedirs(out_dir, exist_ok=True)
 
     pen_coef, stab_coef = 1.0, 1.0
-    bg_mesh = P.create_rectangle([[-4.5, -4.5], [4.5, 4.5]], [args.cells, args.cells])
+    bg_mesh = P.create_rectangle([[-4.5, -4.5], [4.5, 4.5]], [args.cells, args.cells], cell_type=args.cell_type)
     detection_h = NodalFunction(detection_levelset(bg_mesh.x.T))          # P1 interpolant
 
     with warnings.catch_warnings():

@@ -311,7 +311,9 @@ int phx_submesh_create_from_flags(phx_mesh *m, const uint8_t *flags, int loc, ph
  * assemble_vector :153-154, on the tags currently held by the mesh (dx((1,2)), dx(2), dS((2,3)),
  * ds = ds(100) in box mode or all exterior facets on a sub-mesh).
  * phi_h, f_h, u_D: nodal P1 arrays [nv].  Only the active DoFs (rows touched by an integral)
- * are stored. */
+ * are stored.  Quadrilateral meshes: Q1 x Q1 with Q1 nodal arrays [nv] on axis-parallel rectangles in
+ * tensor-product vertex order (same DoF layout and active set); any other quadrilateral returns
+ * PHX_ERR_NOT_IMPLEMENTED. */
 int phx_assemble_poisson_wd(phx_mesh *m, double pen_coef, double stab_coef, const double *phi_h,
                             const double *f_h, const double *u_D, int loc, phx_system **out);
 /* The same forms with primal_degree = auxiliary_degree = 2 (BASELINE configs[2]); the

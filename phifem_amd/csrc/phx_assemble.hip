@@ -1945,17 +1945,21 @@ static int assemble_poisson_wd_on_inner(phx_mesh *m, double pen_coef, double sta
   return rc;
 }
 
+static int assemble_wd_quad_with_capacity(phx_mesh *m, double pen_coef, double stab_coef, const double *dphi,
+                                          const double *df, const double *dud, int W, phx_system **out);
+
 extern "C" int phx_assemble_poisson_wd(phx_mesh *m, double pen_coef, double stab_coef,
                                        const double *phi_h, const double *f_h, const double *u_D,
                                        int loc, phx_system **out) {
   PHX_HIP(hipSetDevice(m->device));
-  PHX_REQUIRE(m->cell_type == PHX_TRIANGLE || m->cell_type == PHX_TETRAHEDRON,
-              PHX_ERR_NOT_IMPLEMENTED, "assembly supports simplices (triangle, tetrahedron) only");
+  const bool quad = m->cell_type == PHX_QUADRILATERAL;   // Q1 x Q1 on rectangles: phx_assemble_wd_quad.inc.hip
+  PHX_REQUIRE(m->cell_type == PHX_TRIANGLE || m->cell_type == PHX_TETRAHEDRON || quad, PHX_ERR_NOT_IMPLEMENTED,
+              "assembly supports triangles, tetrahedra and quadrilaterals (axis-parallel rectangles) only");
   PHX_REQUIRE(m->have_cell_tags && m->have_facet_tags, PHX_ERR_VALUE,
               "cell and facet tags must be computed before assembly");
   // a caller-supplied mesh that is a Kuhn box in disguise: assemble (and later solve) on the generated box behind it
   if (m->inner) return assemble_poisson_wd_on_inner(m, pen_coef, stab_coef, phi_h, f_h, u_D, loc, out);
-  if (!m->is_box) PHX_CHECK(build_v2c(m));  // Kuhn boxes enumerate vertex stars in closed form
+  if (!m->is_box && !quad) PHX_CHECK(build_v2c(m));  // Kuhn boxes enumerate vertex stars in closed form
   const double *dphi, *df, *dud;
   double *o1, *o2, *o3;
   PHX_CHECK(to_device(m, phi_h, loc, m->nv, &dphi, &o1));
@@ -1963,8 +1967,11 @@ extern "C" int phx_assemble_poisson_wd(phx_mesh *m, double pen_coef, double stab
   PHX_CHECK(to_device(m, u_D, loc, m->nv, &dud, &o3));
   PHX_CHECK(phx_begin_timing(m));
   int W = m->gdim == 3 ? 64 : 32;
-  int rc = assemble_with_capacity(m, pen_coef, stab_coef, dphi, df, dud, W, out);
-  if (rc == PHX_ERR_CAPACITY && W < 64) rc = assemble_with_capacity(m, pen_coef, stab_coef, dphi, df, dud, 64, out);
+  int rc = quad ? assemble_wd_quad_with_capacity(m, pen_coef, stab_coef, dphi, df, dud, W, out)
+               : assemble_with_capacity(m, pen_coef, stab_coef, dphi, df, dud, W, out);
+  if (rc == PHX_ERR_CAPACITY && W < 64)
+    rc = quad ? assemble_wd_quad_with_capacity(m, pen_coef, stab_coef, dphi, df, dud, 64, out)
+              : assemble_with_capacity(m, pen_coef, stab_coef, dphi, df, dud, 64, out);
   if (rc == PHX_OK) rc = phx_end_timing(m, 2);
   if (o1) (void)phx_free(o1);
   if (o2) (void)phx_free(o2);
@@ -2016,4 +2023,5 @@ extern "C" int phx_system_export(phx_system *s, int64_t *rowptr, int32_t *col, d
 #include "phx_assemble_flux.inc.hip"
 #include "phx_assemble_flux_quad.inc.hip"
 #include "phx_assemble_el_quad.inc.hip"
+#include "phx_assemble_wd_quad.inc.hip"
 #include "phx_errors.inc.hip"

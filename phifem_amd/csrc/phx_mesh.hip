@@ -581,6 +581,56 @@ static int mesh_attach_inner_box(phx_mesh *m, const double lo[3], const double h
   return PHX_OK;
 }
 
+// ---- caller-supplied rectangular lattices of quadrilaterals --------------------------------------------------------
+// There is no generated quadrilateral box.  A quadrilateral mesh on a tensor lattice whose vertices are NOT numbered in
+// lattice order gets a copy of itself in that order behind it (same cells in the same order and local order, vertices
+// renumbered through v2lat): the weak-Dirichlet system is assembled and solved there, so its rows, columns and dot
+// products -- and with PHX_OPT_DETERMINISTIC its bits and its iteration count -- do not depend on the caller's vertex
+// numbering.  Facets correspond through the (cell, local facet) slots.
+__global__ void k_iota32(int64_t n, int32_t *__restrict__ out) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i < n) out[i] = (int32_t)i;
+}
+__global__ void k_inner_fmap_slots(int64_t n, const int32_t *__restrict__ c2f, const int32_t *__restrict__ ic2f,
+                                   int32_t *__restrict__ fmap) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i < n) fmap[c2f[i]] = ic2f[i];
+}
+
+static int mesh_attach_inner_lattice_copy(phx_mesh *m, const double *coords, const int32_t *cells,
+                                          const std::vector<int32_t> &v2lat, const std::vector<int32_t> &lat2v) {
+  const int64_t nv = m->nv, nc = m->nc;
+  const int d = m->gdim, nvpc = m->ci.nvpc, nfpc = m->ci.nfpc;
+  bool identity = true;
+  for (int64_t v = 0; v < nv && identity; ++v) identity = v2lat[(size_t)v] == (int32_t)v;
+  if (identity) return PHX_OK;
+  std::vector<double> xin((size_t)nv * d);
+  std::vector<int32_t> cin((size_t)nc * nvpc);
+  for (int64_t l = 0; l < nv; ++l)
+    for (int a = 0; a < d; ++a) xin[(size_t)(l * d + a)] = coords[(int64_t)lat2v[(size_t)l] * d + a];
+  for (int64_t i = 0; i < nc * nvpc; ++i) cin[(size_t)i] = v2lat[(size_t)cells[i]];
+  phx_mesh *in = nullptr;
+  PHX_CHECK(phx_mesh_create_from(d, m->cell_type, nv, xin.data(), nc, cin.data(), PHX_HOST, m->device, &in));
+  if (in->nf != m->nf || in->inner) {   // (cannot happen for a renumbered copy; the generic path serves the mesh)
+    phx_mesh_destroy(in);
+    return PHX_OK;
+  }
+  // one stream for both: the pushes of tags and nodal data and the kernels that read them stay ordered
+  PHX_HIP(hipStreamDestroy(in->stream));
+  in->stream = m->stream;
+  in->own_stream = false;
+  m->inner = in;
+  PHX_HIP(phx_malloc(&m->in_cmap, sizeof(int32_t) * (size_t)nc));
+  PHX_HIP(phx_malloc(&m->in_fmap, sizeof(int32_t) * (size_t)m->nf));
+  PHX_HIP(hipMemsetAsync(m->in_fmap, 0xff, sizeof(int32_t) * (size_t)m->nf, m->stream));
+  const dim3 block(256);
+  k_iota32<<<dim3((unsigned)phx_div_up(nc, 256)), block, 0, m->stream>>>(nc, m->in_cmap);
+  k_inner_fmap_slots<<<dim3((unsigned)phx_div_up(nc * nfpc, 256)), block, 0, m->stream>>>(nc * nfpc, m->c2f, in->c2f, m->in_fmap);
+  PHX_HIP(hipGetLastError());
+  PHX_HIP(hipStreamSynchronize(m->stream));
+  return PHX_OK;
+}
+
 // coords / cells at `loc` (host arrays from a caller, or device arrays of a parent mesh: phx_submesh.hip).  The facet
 // numbering and both connectivities are built on the device (phx_topology.inc.hip); PHX_TOPOLOGY_HOST=1 takes the
 // host sort of phx_topology_build_host instead (same numbering; A/B aid, host inputs only).
@@ -629,7 +679,9 @@ int phx_mesh_create_from(int gdim, int cell_type, int64_t nv, const double *coor
   rc = build_boundary_list(m);
   if (rc == PHX_OK) rc = phx_mesh_alloc_common(m);
   if (rc != PHX_OK) return fail(rc);
-  if (loc != PHX_DEVICE && (cell_type == PHX_TRIANGLE || cell_type == PHX_TETRAHEDRON)) {
+  // quadrilaterals: the lattice maps (the sine-transform preconditioner of Q1 systems); there is no generated
+  // quadrilateral box -- mesh_attach_inner_lattice_copy
+  if (loc != PHX_DEVICE && (cell_type == PHX_TRIANGLE || cell_type == PHX_TETRAHEDRON || cell_type == PHX_QUADRILATERAL)) {
     std::vector<int32_t> v2lat, lat2v;
     int64_t ln[3];
     double lh[3], llo[3] = {0, 0, 0}, lhi[3] = {0, 0, 0};
@@ -645,7 +697,10 @@ int phx_mesh_create_from(int gdim, int cell_type, int64_t nv, const double *coor
       }
       static const bool no_inner = getenv("PHX_INNER_BOX") && atoi(getenv("PHX_INNER_BOX")) == 0;   // A/B aid
       if (!no_inner) {
-        rc = mesh_attach_inner_box(m, llo, lhi);   // leaves m->inner == nullptr when the cells are not the Kuhn split
+        // simplices: leaves m->inner == nullptr when the cells are not the Kuhn split; quadrilaterals: a copy in lattice
+        // vertex order, none when the vertices already are
+        rc = cell_type == PHX_QUADRILATERAL ? mesh_attach_inner_lattice_copy(m, coords, cells, v2lat, lat2v)
+                                            : mesh_attach_inner_box(m, llo, lhi);
         if (rc != PHX_OK) return fail(rc);
       }
     }

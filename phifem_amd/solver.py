@@ -3,7 +3,8 @@
 The reference writes this sequence out in each demo (demo/weak-dirichlet/flower/main.py:102-186:
 UFL forms, dolfinx assemble_matrix/assemble_vector, PETSc KSP + MUMPS); ROADMAP.md:15 plans a
 class-based interface for it.  This class is that interface for the P1 x P1 weak-Dirichlet
-Poisson problem, with the element integration, scatter and Krylov solve in HIP.
+Poisson problem (Q1 x Q1 on quadrilateral meshes of rectangles), with the element integration,
+scatter and Krylov solve in HIP.
 """
 import ctypes as C
 import warnings
@@ -70,9 +71,21 @@ class PhiFEMSolver:
         `compute_tags_measures(..., box_mode=False)`; coefficients as main.py:42-43;
         degree = primal_degree = auxiliary degree (main.py:38, 76-78), levelset_degree as main.py:40.
         Degree-2 nodal arrays list the vertex values first, then the edge-midpoint values
-        (`mesh.p2_dof_points()`)."""
+        (`mesh.p2_dof_points()`).
+
+        Quadrilateral meshes (`create_rectangle(..., cell_type="quadrilateral")`, box mode or sub-mesh): Q1 x Q1 with
+        Q1 nodal phi_h, f_h, u_D (degree = levelset_degree = 1) on axis-parallel rectangles in tensor-product vertex
+        order; other quadrilaterals raise NotImplementedError at `assemble`.  Q2 spaces and `coarse_space` are not
+        implemented there."""
         if degree not in (1, 2) or levelset_degree not in (1, 2):
             raise NotImplementedError("Lagrange degrees 1 and 2 are implemented")
+        if getattr(mesh, "cell_type", None) == "quadrilateral":
+            if degree != 1 or levelset_degree != 1:
+                raise NotImplementedError("quadrilateral meshes: Q1 x Q1 with a Q1 level-set (degree = levelset_degree "
+                                          "= 1) is implemented")
+            if coarse_space is not None:
+                raise NotImplementedError("quadrilateral meshes: Q1 x Q1 without coarse_space is implemented (the "
+                                          "coarse-space correction is built for degree 2 on simplicial boxes)")
         if degree == 1 and levelset_degree != 1:
             raise NotImplementedError("a P2 level-set needs degree = 2")
         self.degree, self.levelset_degree = degree, levelset_degree
