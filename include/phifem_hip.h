@@ -82,6 +82,9 @@ const char *phx_last_error(void);          /* [host] */
 int phx_device_count(int *n);              /* [host] 0 GPUs is not an error here */
 /* Return the device memory cached by the library's allocator to the driver. */
 int phx_pool_release(void);
+/* [host] Bytes the allocator has handed out and not got back (all devices) / bytes it keeps cached.  A call that
+ * fails must leave live_bytes where it found it. */
+int phx_pool_stats(int64_t *live_bytes, int64_t *cached_bytes);
 
 /* [host] Detection points on the reference cell / reference facet: restates
  * _reference_{segment,triangle_boundary,square_boundary}_points (mesh_scripts.py:28-92) and

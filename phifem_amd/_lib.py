@@ -46,6 +46,7 @@ SIGNATURES = {
     "phx_last_error": ([], C.c_char_p),
     "phx_device_count": ([_pi], _i),
     "phx_pool_release": ([], _i),
+    "phx_pool_stats": ([_pi64, _pi64], _i),
     "phx_detection_points": ([_i, _i, _i, _vp, _pi64], _i),
     "phx_levelset_points_count": ([_vp, _i, _pi64], _i),
     "phx_levelset_eval_points": ([_vp, _i, _vp, _i, _vp], _i),

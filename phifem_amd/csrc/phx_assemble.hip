@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <initializer_list>
 #include <mutex>
 #include <vector>
 
@@ -1481,8 +1482,9 @@ static int free_slots(Slots &sl) {
   PHX_HIP(phx_free(sl.occ));
   PHX_HIP(phx_free(sl.cols)); PHX_HIP(phx_free(sl.vals)); PHX_HIP(phx_free(sl.overflow)); PHX_HIP(phx_free(sl.clean));
   PHX_HIP(phx_free((void *)sl.off)); PHX_HIP(phx_free((void *)sl.wlog));
+  PHX_HIP(phx_free(sl.emax)); PHX_HIP(phx_free(sl.lo)); PHX_HIP(phx_free(sl.remax)); PHX_HIP(phx_free(sl.rlo));   // an assembly that ended before det_finish
   sl.cols = nullptr; sl.vals = nullptr; sl.overflow = nullptr; sl.clean = nullptr; sl.off = nullptr; sl.wlog = nullptr;
-  sl.occ = nullptr;
+  sl.occ = nullptr; sl.emax = nullptr; sl.lo = nullptr; sl.remax = nullptr; sl.rlo = nullptr;
   return PHX_OK;
 }
 
@@ -1903,6 +1905,139 @@ static int to_device(phx_mesh *m, const double *p, int loc, int64_t n, const dou
   return PHX_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Host scaffold of the secondary assemblers (strong Dirichlet, Neumann / Robin, interface elasticity, Q1 weak
+// Dirichlet): each one reads numbering -> work lists -> slots -> launches -> finish; what it allocates on the way is
+// owned by the two objects below, so every return -- PHX_HIP / PHX_CHECK / PHX_REQUIRE included -- gives it back.
+// ---------------------------------------------------------------------------------------------
+// Device temporaries of one call: the stream is synchronised once and the blocks are freed when the list goes out of
+// scope, so a kernel that is only enqueued may still read them.
+struct DevTemps {
+  hipStream_t stream;
+  std::vector<void *> blocks;
+  explicit DevTemps(hipStream_t st) : stream(st) {}
+  DevTemps(const DevTemps &) = delete;
+  DevTemps &operator=(const DevTemps &) = delete;
+  ~DevTemps() {
+    if (blocks.empty()) return;   // nothing to wait for (device-resident inputs, a call that failed at once)
+    (void)hipStreamSynchronize(stream);
+    for (void *p : blocks) (void)phx_free(p);
+  }
+  template <typename T>
+  hipError_t alloc(T **p, size_t bytes) {
+    const hipError_t e = phx_malloc(p, bytes);
+    if (e == hipSuccess) blocks.push_back(*p);
+    return e;
+  }
+  template <typename T>
+  void adopt(T *p) { if (p) blocks.push_back((void *)p); }   // a block some helper allocated (build_list)
+};
+
+// The system under construction and its slot table: destroyed unless finish() hands the system to the caller
+// (phx_finish_system consumes the slots on the way; free_slots leaves null pointers behind, so freeing twice is safe).
+struct SystemBuild {
+  phx_system *s;
+  Slots sl;
+  SystemBuild(phx_mesh *m, int64_t nent, int64_t nfull, int W) : s(new phx_system()) {
+    s->mesh = m; s->device = m->device; s->nent = nent; s->nfull = nfull; s->slot_cap = W;
+    sl.W = W;
+    sl.cols = nullptr; sl.vals = nullptr; sl.overflow = nullptr;
+  }
+  SystemBuild(const SystemBuild &) = delete;
+  SystemBuild &operator=(const SystemBuild &) = delete;
+  ~SystemBuild() {
+    if (!s) return;
+    (void)hipStreamSynchronize(s->mesh->stream);
+    (void)free_slots(sl);
+    phx_system_destroy(s);
+  }
+  // overflow check, compaction, solver formats; the column keys are full DoF indices below nkey per field
+  int finish(int32_t nkey, phx_system **out) {
+    PHX_CHECK(phx_finish_system(s, sl, nkey));
+    *out = s;
+    s = nullptr;
+    return PHX_OK;
+  }
+};
+
+static int to_device(phx_mesh *m, const double *p, int loc, int64_t n, const double **dev, DevTemps &staged) {
+  double *owned = nullptr;
+  const int rc = to_device(m, p, loc, n, dev, &owned);
+  staged.adopt(owned);
+  return rc;
+}
+
+// slot table of nslots (col, val) pairs, cleared, and the overflow flag
+static int slots_alloc(phx_mesh *m, int64_t nslots, int W, Slots *sl) {
+  sl->W = W;
+  PHX_HIP(phx_malloc(&sl->cols, sizeof(int32_t) * (size_t)nslots));
+  PHX_HIP(phx_malloc(&sl->vals, sizeof(double) * (size_t)nslots));
+  PHX_HIP(phx_malloc(&sl->overflow, sizeof(int)));
+  PHX_HIP(hipMemsetAsync(sl->cols, 0xff, sizeof(int32_t) * (size_t)nslots, m->stream));
+  PHX_HIP(hipMemsetAsync(sl->vals, 0, sizeof(double) * (size_t)nslots, m->stream));
+  PHX_HIP(hipMemsetAsync(sl->overflow, 0, sizeof(int), m->stream));
+  return PHX_OK;
+}
+static int rhs_alloc(phx_mesh *m, phx_system *s) {
+  PHX_HIP(phx_malloc(&s->rhs, sizeof(double) * (size_t)s->n));
+  PHX_HIP(hipMemsetAsync(s->rhs, 0, sizeof(double) * (size_t)s->n, m->stream));
+  return PHX_OK;
+}
+
+__global__ void k_el_numbering(int64_t nent, const uint8_t *__restrict__ flags,
+                               const int32_t *__restrict__ scan, int32_t *__restrict__ dofmap,
+                               int64_t *__restrict__ full_of_active) {
+  const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (e >= nent) return;
+  int32_t a = -1;
+  if (flags[e]) { a = scan[e]; full_of_active[a] = e; }
+  dofmap[e] = a;
+}
+// Active numbering of systems whose DoFs form ONE block of nent entities (all rows count as u rows: Jacobi or the
+// vertex blocks precondition them): flags[e] != 0 marks the active ones.  Leaves n = nu, the map entity -> row in
+// dof_of_vertex_u and its inverse in full_of_active on the system; dof_of_vertex_p is a stub.
+static int number_single_block(phx_mesh *m, phx_system *s, DevTemps &tmp, const uint8_t *flags, int64_t nent,
+                               const char *what_if_empty) {
+  int32_t *scan = nullptr;
+  PHX_HIP(tmp.alloc(&scan, sizeof(int32_t) * (size_t)nent));
+  int32_t n = 0;
+  PHX_CHECK(scan_flags(m, flags, scan, nent, &n));
+  s->n = n; s->nu = n;
+  PHX_REQUIRE(n > 0, PHX_ERR_VALUE, "%s", what_if_empty);
+  PHX_HIP(phx_malloc(&s->dof_of_vertex_u, sizeof(int32_t) * (size_t)nent));
+  PHX_HIP(phx_malloc(&s->dof_of_vertex_p, sizeof(int32_t) * 4));
+  PHX_HIP(phx_malloc(&s->full_of_active, sizeof(int64_t) * (size_t)n));
+  k_el_numbering<<<dim3((unsigned)phx_div_up(nent, 256)), dim3(256), 0, m->stream>>>(nent, flags, scan, s->dof_of_vertex_u,
+                                                                                     s->full_of_active);
+  return PHX_OK;
+}
+
+// The one-sided boundary measure ds as (cell, local facet) entities: the packed entities of ds(100) in box mode
+// (main.py:65), every exterior facet of a sub-mesh as pairs (main.py:74).  Exactly one of the two pointers is set.
+struct DsEntities {
+  int64_t n = 0;
+  const int64_t *packed = nullptr;
+  const int32_t *pairs = nullptr;
+};
+static int ds_entities(phx_mesh *m, DsEntities *ds) {
+  if (m->is_submesh) { ds->n = m->nbf; ds->pairs = m->bfacets; return PHX_OK; }
+  PHX_REQUIRE(phx_collect_entities(m) == PHX_OK, PHX_ERR_VALUE, "integration entities unavailable");
+  ds->n = m->ent_count[0];
+  ds->packed = m->ent_buf[0];
+  return PHX_OK;
+}
+
+// run(W) with the first capacity; while it reports PHX_ERR_CAPACITY, once more with the next one
+template <typename Run>
+static int retry_capacity(std::initializer_list<int> capacities, Run run) {
+  int rc = PHX_ERR_CAPACITY;
+  for (const int W : capacities) {
+    rc = run(W);
+    if (rc != PHX_ERR_CAPACITY) break;
+  }
+  return rc;
+}
+
 // caller-supplied Kuhn box (phx_mesh::inner): tags and nodal data into the numbering of the generated box
 __global__ void k_push_tags(int64_t n, const int32_t *__restrict__ map, const int8_t *__restrict__ src, int8_t *__restrict__ dst) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -2019,6 +2154,7 @@ extern "C" int phx_system_export(phx_system *s, int64_t *rowptr, int32_t *col, d
 
 #include "phx_assemble_p2.inc.hip"
 #include "phx_assemble_sd.inc.hip"
+#include "phx_q1rect.inc.hip"
 #include "phx_assemble_el.inc.hip"
 #include "phx_assemble_flux.inc.hip"
 #include "phx_assemble_flux_quad.inc.hip"

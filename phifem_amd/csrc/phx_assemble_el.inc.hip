@@ -92,15 +92,6 @@ __global__ void k_el_mark_bc(int64_t nbc, int d, int64_t nv, const int32_t *__re
   bc[bcv[i]] = 1;
   for (int a = 0; a < d; ++a) flags[(int64_t)a * nv + bcv[i]] = 1;
 }
-__global__ void k_el_numbering(int64_t nent, const uint8_t *__restrict__ flags,
-                               const int32_t *__restrict__ scan, int32_t *__restrict__ dofmap,
-                               int64_t *__restrict__ full_of_active) {
-  const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (e >= nent) return;
-  int32_t a = -1;
-  if (flags[e]) { a = scan[e]; full_of_active[a] = e; }
-  dofmap[e] = a;
-}
 
 // --- stiffness main.py:185-186,226-227 + source :263-264; one block per cell --------------------
 template <int D>
@@ -479,8 +470,10 @@ static int assemble_el_with_capacity(phx_mesh *m, const double *params, const do
   const int C = 2 * D + 2 * D * D + D;
   const int64_t nent = (int64_t)C * m->nv;
   PHX_REQUIRE(nent < INT32_MAX, PHX_ERR_VALUE, "too many DoFs for 32-bit column keys");
-  phx_system *s = new phx_system();
-  s->mesh = m; s->device = m->device; s->nfull = nent; s->slot_cap = W; s->nent = nent;
+  SystemBuild sys(m, nent, nent, W);
+  DevTemps tmp(m->stream);
+  phx_system *s = sys.s;
+  Slots &sl = sys.sl;
   s->el_nblk = C;
   const dim3 block(256);
   ElArgs A;
@@ -497,40 +490,38 @@ static int assemble_el_with_capacity(phx_mesh *m, const double *params, const do
   const double coef_out = (E[1] / (E[0] + E[1])) * (E[1] / (E[0] + E[1]));
   A.coefW[0] = coef_out; A.coefW[1] = coef_in;
   A.gamma = params[4]; A.sigma = params[5];
-  uint8_t *flags = nullptr, *bc = nullptr;
-  int32_t *scan = nullptr;
-  PHX_HIP(phx_malloc(&flags, (size_t)nent)); PHX_HIP(phx_malloc(&bc, (size_t)m->nv));
-  PHX_HIP(phx_malloc(&scan, sizeof(int32_t) * (size_t)nent));
-  PHX_HIP(hipMemsetAsync(flags, 0, (size_t)nent, m->stream));
+  // ---- active numbering.  flags and scan (5 bytes per DoF entity: 2.3 GB on the 256^3 box) go back before the slot
+  // table is allocated, as do cutv and cap below: each in a list of its own that ends with its block
+  uint8_t *bc = nullptr;
+  PHX_HIP(tmp.alloc(&bc, (size_t)m->nv));
   PHX_HIP(hipMemsetAsync(bc, 0, (size_t)m->nv, m->stream));
   A.bc = bc;
-  const dim3 gcells((unsigned)phx_div_up(m->nc, 256));
-  if (quad) k_el_mark_active<2, 4><<<gcells, block, 0, m->stream>>>(m->nc, A, flags);
-  else if (D == 2) k_el_mark_active<2><<<gcells, block, 0, m->stream>>>(m->nc, A, flags);
-  else k_el_mark_active<3><<<gcells, block, 0, m->stream>>>(m->nc, A, flags);
-  if (nbc > 0) k_el_mark_bc<<<dim3((unsigned)phx_div_up(nbc, 256)), block, 0, m->stream>>>(nbc, D, m->nv, dbcv, flags, bc);
-  int32_t n = 0;
-  PHX_CHECK(scan_flags(m, flags, scan, nent, &n));
-  s->n = n; s->nu = n;
-  PHX_REQUIRE(n > 0, PHX_ERR_VALUE, "no active DoF");
-  PHX_HIP(phx_malloc(&s->dof_of_vertex_u, sizeof(int32_t) * (size_t)nent));
-  PHX_HIP(phx_malloc(&s->dof_of_vertex_p, sizeof(int32_t) * 4));
-  PHX_HIP(phx_malloc(&s->full_of_active, sizeof(int64_t) * (size_t)n));
-  k_el_numbering<<<dim3((unsigned)phx_div_up(nent, 256)), block, 0, m->stream>>>(nent, flags, scan, s->dof_of_vertex_u, s->full_of_active);
-  PHX_HIP(hipStreamSynchronize(m->stream));
-  PHX_HIP(phx_free(flags)); PHX_HIP(phx_free(scan));
+  {
+    DevTemps numbering(m->stream);
+    uint8_t *flags = nullptr;
+    PHX_HIP(numbering.alloc(&flags, (size_t)nent));
+    PHX_HIP(hipMemsetAsync(flags, 0, (size_t)nent, m->stream));
+    const dim3 gcells((unsigned)phx_div_up(m->nc, 256));
+    if (quad) k_el_mark_active<2, 4><<<gcells, block, 0, m->stream>>>(m->nc, A, flags);
+    else if (D == 2) k_el_mark_active<2><<<gcells, block, 0, m->stream>>>(m->nc, A, flags);
+    else k_el_mark_active<3><<<gcells, block, 0, m->stream>>>(m->nc, A, flags);
+    if (nbc > 0) k_el_mark_bc<<<dim3((unsigned)phx_div_up(nbc, 256)), block, 0, m->stream>>>(nbc, D, m->nv, dbcv, flags, bc);
+    PHX_CHECK(number_single_block(m, s, numbering, flags, nent, "no active DoF"));
+  }
+  const int32_t n = (int32_t)s->n;
   A.dofmap = s->dof_of_vertex_u;
+  // ---- work lists
   int32_t *l_cut = nullptr, *l_f3 = nullptr, *l_f4 = nullptr;
   int64_t n_cut = 0, n_f3 = 0, n_f4 = 0;
   PHX_CHECK(build_list(m, m->nc, SelCut{m->cell_tags}, &l_cut, &n_cut));
-  // per-row slot capacities (a uniform W = 512 would need 450 GB for the 256^3 box of BASELINE configs[3])
-  Slots sl;
-  sl.W = W;
+  tmp.adopt(l_cut);
+  // ---- slots: per-row capacities (a uniform W = 512 would need 450 GB for the 256^3 box of BASELINE configs[3])
   int64_t total_slots = 0;
   {
-    uint8_t *cutv = nullptr, *wlog = nullptr;
-    int64_t *cap = nullptr, *off = nullptr;
-    PHX_HIP(phx_malloc(&cutv, (size_t)m->nv));
+    DevTemps caps(m->stream);
+    uint8_t *cutv = nullptr;
+    int64_t *cap = nullptr;
+    PHX_HIP(caps.alloc(&cutv, (size_t)m->nv));
     PHX_HIP(hipMemsetAsync(cutv, 0, (size_t)m->nv, m->stream));
     if (n_cut > 0) {
       const dim3 g((unsigned)phx_div_up(n_cut, 256));
@@ -539,33 +530,30 @@ static int assemble_el_with_capacity(phx_mesh *m, const double *params, const do
     }
     int wbig = 0;
     while ((1 << wbig) < W) ++wbig;
+    uint8_t *wlog = nullptr;   // the slot table owns wlog and off (free_slots)
+    int64_t *off = nullptr;
     PHX_HIP(phx_malloc(&wlog, (size_t)n));
-    PHX_HIP(phx_malloc(&cap, sizeof(int64_t) * (size_t)(n + 1)));
+    sl.wlog = wlog;
+    PHX_HIP(caps.alloc(&cap, sizeof(int64_t) * (size_t)(n + 1)));
     PHX_HIP(phx_malloc(&off, sizeof(int64_t) * (size_t)(n + 1)));
+    sl.off = off;
     k_el_row_caps<<<dim3((unsigned)phx_div_up((int64_t)n + 1, 256)), block, 0, m->stream>>>(
         n, s->full_of_active, m->nv, cutv, wbig, wlog, cap);
     PHX_CHECK(exclusive_sum<int64_t>(m, cap, off, (int64_t)n + 1));
     PHX_HIP(hipMemcpy(&total_slots, off + n, sizeof(int64_t), hipMemcpyDeviceToHost));
-    PHX_HIP(phx_free(cutv)); PHX_HIP(phx_free(cap));
-    sl.off = off;
-    sl.wlog = wlog;
   }
-  PHX_HIP(phx_malloc(&sl.cols, sizeof(int32_t) * (size_t)total_slots));
-  PHX_HIP(phx_malloc(&sl.vals, sizeof(double) * (size_t)total_slots));
-  PHX_HIP(phx_malloc(&sl.overflow, sizeof(int)));
-  PHX_HIP(hipMemsetAsync(sl.cols, 0xff, sizeof(int32_t) * (size_t)total_slots, m->stream));
-  PHX_HIP(hipMemsetAsync(sl.vals, 0, sizeof(double) * (size_t)total_slots, m->stream));
-  PHX_HIP(hipMemsetAsync(sl.overflow, 0, sizeof(int), m->stream));
-  PHX_HIP(phx_malloc(&s->rhs, sizeof(double) * (size_t)n));
-  PHX_HIP(hipMemsetAsync(s->rhs, 0, sizeof(double) * (size_t)n, m->stream));
+  PHX_CHECK(slots_alloc(m, total_slots, W, &sl));
+  PHX_CHECK(rhs_alloc(m, s));
   A.rhs = s->rhs; A.slots = sl;
   PHX_CHECK(build_list(m, m->nf, SelFacetTagInterior{m->facet_tags, m->f2c, 3}, &l_f3, &n_f3));
+  tmp.adopt(l_f3);
   PHX_CHECK(build_list(m, m->nf, SelFacetTagInterior{m->facet_tags, m->f2c, 4}, &l_f4, &n_f4));
+  tmp.adopt(l_f4);
   PHX_CHECK(phx_collect_entities(m));
   uint8_t *touched = nullptr;
   if (m->is_box) {
     // rows of vertices no scattering kernel reaches are written dense and sorted by the gather kernel
-    PHX_HIP(phx_malloc(&touched, (size_t)m->nv));
+    PHX_HIP(tmp.alloc(&touched, (size_t)m->nv));
     PHX_HIP(phx_malloc(&sl.clean, (size_t)n));
     PHX_HIP(hipMemsetAsync(touched, 0, (size_t)m->nv, m->stream));
     PHX_HIP(hipMemsetAsync(sl.clean, 0, (size_t)n, m->stream));
@@ -585,12 +573,7 @@ static int assemble_el_with_capacity(phx_mesh *m, const double *params, const do
   }
   if (!m->is_box) PHX_REQUIRE_GRID(m->nc * 256, "elasticity bulk assembly");
   PHX_REQUIRE_GRID(n_cut * 256, "elasticity cut-cell assembly");
-  int *bad = nullptr;
-  if (quad) {
-    PHX_HIP(phx_malloc(&bad, sizeof(int)));
-    PHX_HIP(hipMemsetAsync(bad, 0, sizeof(int), m->stream));
-    A.bad = bad;
-  }
+  if (quad) PHX_CHECK(rect_bad_alloc(m, tmp, &A.bad));
   // PHX_OPT_DETERMINISTIC: every kernel that adds into the slots or the right-hand side runs twice (Slots)
   bool det = false;
   PHX_CHECK(det_alloc(m, sl, total_slots, n, &det));
@@ -626,24 +609,8 @@ static int assemble_el_with_capacity(phx_mesh *m, const double *params, const do
     PHX_HIP(hipGetLastError());
   }
   PHX_CHECK(det_finish(m, sl, total_slots, n, s->rhs));
-  PHX_HIP(hipStreamSynchronize(m->stream));
-  PHX_HIP(phx_free(l_cut)); PHX_HIP(phx_free(l_f3)); PHX_HIP(phx_free(l_f4)); PHX_HIP(phx_free(bc));
-  PHX_HIP(phx_free(touched));
-  if (quad) {
-    int hbad = 0;
-    PHX_HIP(hipMemcpy(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost));
-    PHX_HIP(phx_free(bad));
-    if (hbad) {
-      PHX_CHECK(free_slots(sl));
-      phx_system_destroy(s);
-      phx_set_error("quadrilateral elasticity assembly covers axis-parallel rectangles only");
-      return PHX_ERR_NOT_IMPLEMENTED;
-    }
-  }
-  const int rc = phx_finish_system(s, sl, (int32_t)nent);
-  if (rc != PHX_OK) { phx_system_destroy(s); return rc; }
-  *out = s;
-  return PHX_OK;
+  if (quad) PHX_CHECK(rect_bad_check(m, A.bad));
+  return sys.finish((int32_t)nent, out);
 }
 
 extern "C" int phx_assemble_elasticity_if(phx_mesh *m, const double *params, const double *phi_h,
@@ -658,28 +625,24 @@ extern "C" int phx_assemble_elasticity_if(phx_mesh *m, const double *params, con
               "cell and facet tags must be computed before assembly");
   PHX_REQUIRE(!m->is_submesh, PHX_ERR_NOT_IMPLEMENTED, "interface elasticity runs in box mode");
   const int D = m->gdim;
+  DevTemps staged(m->stream);
   const double *dphi, *df, *dud;
-  double *o1, *o2, *o3;
-  PHX_CHECK(to_device(m, phi_h, loc, m->nv, &dphi, &o1));
-  PHX_CHECK(to_device(m, f_h, loc, (int64_t)D * m->nv, &df, &o2));
-  PHX_CHECK(to_device(m, u_D, loc, (int64_t)D * m->nv, &dud, &o3));
+  PHX_CHECK(to_device(m, phi_h, loc, m->nv, &dphi, staged));
+  PHX_CHECK(to_device(m, f_h, loc, (int64_t)D * m->nv, &df, staged));
+  PHX_CHECK(to_device(m, u_D, loc, (int64_t)D * m->nv, &dud, staged));
   int32_t *dbcv = nullptr;
   if (nbc > 0) {
     if (loc == PHX_DEVICE) dbcv = (int32_t *)bc_vertices;
     else {
-      PHX_HIP(phx_malloc(&dbcv, sizeof(int32_t) * (size_t)nbc));
+      PHX_HIP(staged.alloc(&dbcv, sizeof(int32_t) * (size_t)nbc));
       PHX_HIP(hipMemcpyAsync(dbcv, bc_vertices, sizeof(int32_t) * (size_t)nbc, hipMemcpyHostToDevice, m->stream));
     }
   }
   PHX_CHECK(phx_begin_timing(m));
-  int W = 256;  // capacity of the rows of cut-cell vertices (the others take 64); doubled on overflow
-  int rc = assemble_el_with_capacity(m, params, dphi, df, dud, dbcv, nbc, W, out);
-  if (rc == PHX_ERR_CAPACITY) { W = 512; rc = assemble_el_with_capacity(m, params, dphi, df, dud, dbcv, nbc, W, out); }
-  if (rc == PHX_ERR_CAPACITY && W < 1024) rc = assemble_el_with_capacity(m, params, dphi, df, dud, dbcv, nbc, 2 * W, out);
+  // W: capacity of the rows of cut-cell vertices (the others take 64)
+  int rc = retry_capacity({256, 512, 1024}, [&](int W) {
+    return assemble_el_with_capacity(m, params, dphi, df, dud, dbcv, nbc, W, out);
+  });
   if (rc == PHX_OK) rc = phx_end_timing(m, 2);
-  if (o1) (void)phx_free(o1);
-  if (o2) (void)phx_free(o2);
-  if (o3) (void)phx_free(o3);
-  if (dbcv && loc != PHX_DEVICE) (void)phx_free(dbcv);
   return rc;
 }

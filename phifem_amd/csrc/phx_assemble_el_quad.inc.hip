@@ -3,9 +3,8 @@
 // cell_type "quadrilateral" of demo/interface-elasticity/main.py:99-108 with the forms :179-235 (bilinear),
 // :255-269 (linear) and the Dirichlet rows of u_in :158-177,237-239,271-277.  Included by phx_assemble.hip after
 // phx_assemble_el.inc.hip (ElArgs, ElB<2>, el_add / el_rhs: the DoF layout, the Dirichlet lifting and the
-// deterministic Slots passes) and phx_assemble_flux_quad.inc.hip (a1 / m1, quad_facet).
-// Cells: axis-parallel rectangles in tensor-product vertex order v0 (0,0), v1 (1,0), v2 (0,1), v3 (1,1); local
-// facets in basix numbering f0 (v0,v1), f1 (v0,v2), f2 (v1,v3), f3 (v2,v3); h_T = the diagonal (CellDiameter).
+// deterministic Slots passes) and phx_q1rect.inc.hip (the rectangle, the Q1 basis, the facet numbering, the Gauss
+// rules: the cell conventions are stated there).
 // f_h, u_D: Q1 nodal vector fields, as on simplices (oracle/elasticity.py).  Restated in tests/elasticity_quad_ref.py.
 //
 // Quadrature is EXACT, so the result equals FFCx's up to round-off:
@@ -16,29 +15,9 @@
 //  * facet integrands: (y . n) v and jump(sigma(u), n) . jump(sigma(v), n) are of degree <= 2 along the facet
 //    (sigma of a Q1 field is linear along an axis-parallel facet): the 2-point Gauss rule (degree 3) is exact.
 //  * the bulk stiffness and the source term use the closed-form 1-D integrals of linear functions on [0, 1].
-// A cell that is not an axis-parallel rectangle sets *A.bad: the assembly then fails with PHX_ERR_NOT_IMPLEMENTED.
-
-struct ElqRect { double hx, hy, h; int32_t v[4]; };
-__device__ __forceinline__ bool elq_rect(const ElArgs &A, int64_t c, ElqRect &R) {
-  double X[4][2];
-  for (int i = 0; i < 4; ++i) {
-    R.v[i] = A.cells[c * 4 + i];
-    X[i][0] = A.x[2 * (int64_t)R.v[i]];
-    X[i][1] = A.x[2 * (int64_t)R.v[i] + 1];
-  }
-  R.hx = X[1][0] - X[0][0];
-  R.hy = X[2][1] - X[0][1];
-  R.h = sqrt(R.hx * R.hx + R.hy * R.hy);
-  const double tx = 1e-12 * fabs(R.hx), ty = 1e-12 * fabs(R.hy);
-  return R.hx > 0.0 && R.hy > 0.0 && fabs(X[1][1] - X[0][1]) <= tx && fabs(X[2][0] - X[0][0]) <= ty &&
-         fabs(X[3][0] - X[1][0]) <= tx && fabs(X[3][1] - X[2][1]) <= ty;
-}
-
-// int_0^1 L_i' L_j for the linear 1-D basis L_0 = 1 - t, L_1 = t
-__device__ __forceinline__ double c1(int i, int j) { (void)j; return i ? 0.5 : -0.5; }
 
 // int_K d_p N_i d_q N_j on a rectangle (closed form, tensor products of 1-D integrals)
-__device__ __forceinline__ double elq_dd(const ElqRect &R, int p, int i, int q, int j) {
+__device__ __forceinline__ double elq_dd(const RectGeo &R, int p, int i, int q, int j) {
   const int ix = i & 1, iy = i >> 1, jx = j & 1, jy = j >> 1;
   if (p == 0 && q == 0) return (R.hy / R.hx) * a1(ix, jx) * m1(iy, jy);
   if (p == 1 && q == 1) return (R.hx / R.hy) * m1(ix, jx) * a1(iy, jy);
@@ -63,8 +42,8 @@ __global__ void __launch_bounds__(128) k_elq_bulk(int64_t nc, ElArgs A) {
   if (c >= nc) return;
   const int t = A.ctags[c] & PHX_TAG_MASK;
   if (t < 1 || t > 3) return;
-  ElqRect R;
-  if (!elq_rect(A, c, R)) { if (threadIdx.x == 0) *A.bad = 1; return; }
+  RectGeo R;
+  if (!rect_load(A.cells, A.x, c, R)) { if (threadIdx.x == 0) *A.bad = 1; return; }
   const int side = threadIdx.x / 64, r = (threadIdx.x / 8) % 8, s = threadIdx.x % 8;
   if (elq_side_on(side, t)) {
     const int a = r / 4, i = r % 4, cc = s / 4, j = s % 4;
@@ -96,28 +75,17 @@ __global__ void __launch_bounds__(256) k_elq_cut(int64_t nlist, const int32_t *_
   __shared__ int npresent;
   __shared__ double sN[NQ][4], sG[NQ][4][2], sW[NQ], sPh[NQ], sGp[NQ][2], sF[NQ][2];
   const int64_t c = list[e];
-  ElqRect R;
-  if (!elq_rect(A, c, R)) { if (threadIdx.x == 0) *A.bad = 1; return; }   // uniform across the workgroup
+  RectGeo R;
+  if (!rect_load(A.cells, A.x, c, R)) { if (threadIdx.x == 0) *A.bad = 1; return; }   // uniform across the workgroup
   if (threadIdx.x == 0) npresent = 0;
   __syncthreads();
   for (int pi = threadIdx.x; pi < B::C * B::C; pi += blockDim.x)
     if (el_cut_pair_present<2>(pi / B::C, pi % B::C)) present[atomicAdd(&npresent, 1)] = (uint16_t)pi;
   if (threadIdx.x < NQ) {
-    const double s15 = 0.7745966692414834 * 0.5;
-    const double gx[3] = {0.5 - s15, 0.5, 0.5 + s15}, gw[3] = {5.0 / 18.0, 8.0 / 18.0, 5.0 / 18.0};
-    const int qx = threadIdx.x / 3, qy = threadIdx.x % 3;
-    const double xi = gx[qx], eta = gx[qy];
-    sW[threadIdx.x] = gw[qx] * gw[qy] * R.hx * R.hy;
+    sW[threadIdx.x] = q1_tab9(threadIdx.x, &R, sN[threadIdx.x], sG[threadIdx.x]);
     double ph = 0.0, gpx = 0.0, gpy = 0.0, f0 = 0.0, f1 = 0.0;
     for (int i = 0; i < 4; ++i) {
-      double val, tx, ty;
-      const double lx = (i & 1) ? xi : 1.0 - xi, ly = (i >> 1) ? eta : 1.0 - eta;
-      val = lx * ly;
-      tx = ((i & 1) ? 1.0 : -1.0) * ly / R.hx;
-      ty = lx * ((i >> 1) ? 1.0 : -1.0) / R.hy;
-      sN[threadIdx.x][i] = val;
-      sG[threadIdx.x][i][0] = tx;
-      sG[threadIdx.x][i][1] = ty;
+      const double val = sN[threadIdx.x][i], tx = sG[threadIdx.x][i][0], ty = sG[threadIdx.x][i][1];
       const double pv = A.phi[R.v[i]];
       ph += pv * val; gpx += pv * tx; gpy += pv * ty;
       f0 += A.f[R.v[i]] * val;
@@ -196,8 +164,8 @@ __global__ void __launch_bounds__(256) k_elq_ds(int64_t nent, const int64_t *__r
   if (e >= nent) return;
   const int64_t c = ent_packed[2 * e + 1] >> 8;
   const int lf = (int)(ent_packed[2 * e + 1] & 0xff);
-  ElqRect R;
-  if (!elq_rect(A, c, R)) { *A.bad = 1; return; }
+  RectGeo R;
+  if (!rect_load(A.cells, A.x, c, R)) { *A.bad = 1; return; }
   int va, vb, axis;
   double sign;
   quad_facet(lf, &va, &vb, &axis, &sign);
@@ -217,22 +185,14 @@ __global__ void __launch_bounds__(256) k_elq_facets(int64_t nlist, const int32_t
   const int64_t e = blockIdx.x;
   if (e >= nlist) return;
   const int64_t f = list[e];
-  const double tq[2] = {0.5 - 0.5 / 1.7320508075688772, 0.5 + 0.5 / 1.7320508075688772};
-  ElqRect R[2];
-  int axis[2];
-  double sgnf[2], fixed[2], hsum = 0.0, len = 0.0;
+  constexpr Gauss2 g2 = gauss2();
+  QuadFacetSide S[2];
+  double hsum = 0.0;
   for (int sd = 0; sd < 2; ++sd) {
-    const int64_t c = A.f2c[2 * f + sd];
-    if (!elq_rect(A, c, R[sd])) { if (threadIdx.x == 0) *A.bad = 1; return; }
-    int lf = 0;
-    for (int k = 0; k < 4; ++k)
-      if (A.c2f[c * 4 + k] == (int32_t)f) lf = k;
-    int va, vb;
-    quad_facet(lf, &va, &vb, &axis[sd], &sgnf[sd]);
-    fixed[sd] = sgnf[sd] > 0.0 ? 1.0 : 0.0;
-    if (sd == 0) len = axis[0] == 0 ? R[0].hy : R[0].hx;
-    hsum += R[sd].h;
+    if (!quad_facet_side(f, sd, A.c2f, A.f2c, A.cells, A.x, S[sd])) { if (threadIdx.x == 0) *A.bad = 1; return; }
+    hsum += S[sd].R.h;
   }
+  const double len = S[0].len;
   const double wgt = A.sigma * 0.5 * hsum * len;
   const double lam = A.lam[side], mu = A.mu[side];
   const int r = threadIdx.x / 16, s = threadIdx.x % 16;
@@ -243,14 +203,15 @@ __global__ void __launch_bounds__(256) k_elq_facets(int64_t nlist, const int32_t
     double J[2][2];   // (sigma(N e) n)_p of the row and the column function
     for (int k = 0; k < 2; ++k) {
       const int sd = k == 0 ? sr : sc, vi = k == 0 ? i : j, comp = k == 0 ? ar : ac;
-      const double xi = axis[sd] == 0 ? fixed[sd] : tq[q], eta = axis[sd] == 1 ? fixed[sd] : tq[q];
-      const double lx = (vi & 1) ? xi : 1.0 - xi, ly = (vi >> 1) ? eta : 1.0 - eta;
-      const double g[2] = {((vi & 1) ? 1.0 : -1.0) * ly / R[sd].hx, lx * ((vi >> 1) ? 1.0 : -1.0) / R[sd].hy};
-      for (int p = 0; p < 2; ++p) J[k][p] = sgnf[sd] * elq_sig(g, lam, mu, comp, p, axis[sd]);
+      const QuadFacetSide &F = S[sd];
+      const double xi = F.axis == 0 ? F.fixed : g2.x[q], eta = F.axis == 1 ? F.fixed : g2.x[q];
+      double val, g[2];
+      q1_at(vi, xi, eta, F.R, &val, &g[0], &g[1]);
+      for (int p = 0; p < 2; ++p) J[k][p] = F.sign * elq_sig(g, lam, mu, comp, p, F.axis);
     }
-    acc += 0.5 * (J[0][0] * J[1][0] + J[0][1] * J[1][1]);
+    acc += g2.w[q] * (J[0][0] * J[1][0] + J[0][1] * J[1][1]);
   }
-  el_add<2>(A, B::ublk(side, ar) * A.nv + R[sr].v[i], B::ublk(side, ac) * A.nv + R[sc].v[j], wgt * acc);
+  el_add<2>(A, B::ublk(side, ar) * A.nv + S[sr].R.v[i], B::ublk(side, ac) * A.nv + S[sc].R.v[j], wgt * acc);
 }
 
 // launched by assemble_el_with_capacity (phx_assemble_el.inc.hip) in place of the simplex element kernels

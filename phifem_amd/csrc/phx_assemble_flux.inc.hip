@@ -221,78 +221,58 @@ static int assemble_flux_with_capacity(phx_mesh *m, const double *params, int fa
   const int D = m->gdim;
   const int64_t nent = (int64_t)(1 + D) * m->nv + m->nc;
   PHX_REQUIRE(nent < INT32_MAX, PHX_ERR_VALUE, "too many DoFs for 32-bit column keys");
-  phx_system *s = new phx_system();
-  s->mesh = m; s->device = m->device; s->nfull = nent; s->slot_cap = W; s->nent = nent;
+  SystemBuild sys(m, nent, nent, W);
+  DevTemps tmp(m->stream);
+  phx_system *s = sys.s;
   const dim3 block(256);
-  std::vector<void *> keep;
   FxArgs A;
   memset(&A, 0, sizeof(A));
   A.cells = m->cells; A.x = m->x; A.ctags = m->cell_tags; A.c2f = m->c2f; A.f2c = m->f2c; A.c2e = m->c2e;
   A.phi = dphi; A.f = df; A.g = dg; A.nv = m->nv;
   A.gamma = params[0]; A.sigma = params[1]; A.kappa = params[2];
-  PHX_CHECK(upload_rule(m, D, qdeg, &A.cut, keep));
+  PHX_CHECK(upload_rule(m, D, qdeg, &A.cut, tmp.blocks));
+  // ---- active numbering.  Jacobi only (every row counts as a u row): the lattice preconditioner on the u rows
+  // (which come first) makes BiCGStab worse here -- the y / p penalty blocks dominate (Robin demo, 200^2: 10072
+  // iterations instead of 2800; 400^2 diverges)
   uint8_t *flags = nullptr;
-  int32_t *scan = nullptr;
-  PHX_HIP(phx_malloc(&flags, (size_t)nent));
-  PHX_HIP(phx_malloc(&scan, sizeof(int32_t) * (size_t)nent));
+  PHX_HIP(tmp.alloc(&flags, (size_t)nent));
   PHX_HIP(hipMemsetAsync(flags, 0, (size_t)nent, m->stream));
   const dim3 gcells((unsigned)phx_div_up(m->nc, 256));
   if (D == 2) k_fx_mark_active<2><<<gcells, block, 0, m->stream>>>(m->nc, A, flags);
   else k_fx_mark_active<3><<<gcells, block, 0, m->stream>>>(m->nc, A, flags);
-  int32_t n = 0;
-  PHX_CHECK(scan_flags(m, flags, scan, nent, &n));
-  PHX_REQUIRE(n > 0, PHX_ERR_VALUE, "no active DoF: no cell is tagged 1 or 2");
-  // Jacobi only: the lattice preconditioner on the u rows (which come first) makes BiCGStab worse here -- the
-  // y / p penalty blocks dominate (Robin demo, 200^2: 10072 iterations instead of 2800; 400^2 diverges)
-  s->n = n; s->nu = n;
-  PHX_HIP(phx_malloc(&s->dof_of_vertex_u, sizeof(int32_t) * (size_t)nent));
-  PHX_HIP(phx_malloc(&s->dof_of_vertex_p, sizeof(int32_t) * 4));
-  PHX_HIP(phx_malloc(&s->full_of_active, sizeof(int64_t) * (size_t)n));
-  k_el_numbering<<<dim3((unsigned)phx_div_up(nent, 256)), block, 0, m->stream>>>(nent, flags, scan, s->dof_of_vertex_u, s->full_of_active);
-  PHX_HIP(hipStreamSynchronize(m->stream));
-  PHX_HIP(phx_free(flags)); PHX_HIP(phx_free(scan));
+  PHX_CHECK(number_single_block(m, s, tmp, flags, nent, "no active DoF: no cell is tagged 1 or 2"));
   A.dofmap = s->dof_of_vertex_u;
-  Slots sl;
-  sl.W = W;
-  PHX_HIP(phx_malloc(&sl.cols, sizeof(int32_t) * (size_t)n * W));
-  PHX_HIP(phx_malloc(&sl.vals, sizeof(double) * (size_t)n * W));
-  PHX_HIP(phx_malloc(&sl.overflow, sizeof(int)));
-  PHX_HIP(hipMemsetAsync(sl.cols, 0xff, sizeof(int32_t) * (size_t)n * W, m->stream));
-  PHX_HIP(hipMemsetAsync(sl.vals, 0, sizeof(double) * (size_t)n * W, m->stream));
-  PHX_HIP(hipMemsetAsync(sl.overflow, 0, sizeof(int), m->stream));
-  PHX_HIP(phx_malloc(&s->rhs, sizeof(double) * (size_t)n));
-  PHX_HIP(hipMemsetAsync(s->rhs, 0, sizeof(double) * (size_t)n, m->stream));
-  A.rhs = s->rhs; A.slots = sl;
+  // ---- work lists and integration entities
   int32_t *l_om = nullptr, *l_cut = nullptr, *l_fac = nullptr;
   int64_t n_om = 0, n_cut = 0, n_fac = 0;
   PHX_CHECK(build_list(m, m->nc, SelOmega{m->cell_tags}, &l_om, &n_om));
+  tmp.adopt(l_om);
   PHX_CHECK(build_list(m, m->nc, SelCut{m->cell_tags}, &l_cut, &n_cut));
+  tmp.adopt(l_cut);
   PHX_CHECK(build_list(m, m->nf, SelFacetTagInterior{m->facet_tags, m->f2c, facet_tag}, &l_fac, &n_fac));
-  const int64_t nds = m->is_submesh ? m->nbf : (phx_collect_entities(m) == PHX_OK ? m->ent_count[0] : -1);
-  PHX_REQUIRE(nds >= 0, PHX_ERR_VALUE, "integration entities unavailable");
-  const int64_t *pk = m->is_submesh ? nullptr : m->ent_buf[0];
-  const int32_t *pr = m->is_submesh ? m->bfacets : nullptr;
+  tmp.adopt(l_fac);
+  DsEntities ds;
+  PHX_CHECK(ds_entities(m, &ds));
   PHX_REQUIRE_GRID(n_om * 16, "Neumann / Robin cell assembly");
   PHX_REQUIRE_GRID(n_fac * 64, "Neumann / Robin facet assembly");
+  // ---- slots
+  PHX_CHECK(slots_alloc(m, (int64_t)s->n * W, W, &sys.sl));
+  PHX_CHECK(rhs_alloc(m, s));
+  A.rhs = s->rhs; A.slots = sys.sl;
+  // ---- element kernels
   if (D == 2) {
     if (n_om) k_fx_bulk<2><<<dim3((unsigned)phx_div_up(n_om * 16, 256)), block, 0, m->stream>>>(n_om, l_om, A);
     if (n_cut) k_fx_cut<2><<<dim3((unsigned)n_cut), dim3(128), 0, m->stream>>>(n_cut, l_cut, A);
-    if (nds) k_fx_ds<2><<<dim3((unsigned)phx_div_up(nds * 64, 256)), block, 0, m->stream>>>(nds, pk, pr, A);
+    if (ds.n) k_fx_ds<2><<<dim3((unsigned)phx_div_up(ds.n * 64, 256)), block, 0, m->stream>>>(ds.n, ds.packed, ds.pairs, A);
     if (n_fac) k_fx_facets<2><<<dim3((unsigned)phx_div_up(n_fac * 64, 256)), block, 0, m->stream>>>(n_fac, l_fac, A);
   } else {
     if (n_om) k_fx_bulk<3><<<dim3((unsigned)phx_div_up(n_om * 16, 256)), block, 0, m->stream>>>(n_om, l_om, A);
     if (n_cut) k_fx_cut<3><<<dim3((unsigned)n_cut), block, 0, m->stream>>>(n_cut, l_cut, A);
-    if (nds) k_fx_ds<3><<<dim3((unsigned)phx_div_up(nds * 64, 256)), block, 0, m->stream>>>(nds, pk, pr, A);
+    if (ds.n) k_fx_ds<3><<<dim3((unsigned)phx_div_up(ds.n * 64, 256)), block, 0, m->stream>>>(ds.n, ds.packed, ds.pairs, A);
     if (n_fac) k_fx_facets<3><<<dim3((unsigned)phx_div_up(n_fac * 64, 256)), block, 0, m->stream>>>(n_fac, l_fac, A);
   }
   PHX_HIP(hipGetLastError());
-  PHX_HIP(hipStreamSynchronize(m->stream));
-  PHX_HIP(phx_free(l_om)); PHX_HIP(phx_free(l_cut)); PHX_HIP(phx_free(l_fac));
-  for (void *p : keep) PHX_HIP(phx_free(p));
-  const int rc = phx_finish_system(s, sl, (int32_t)nent);
-  if (rc != PHX_OK) { phx_system_destroy(s); return rc; }
-  *out = s;
-  return PHX_OK;
+  return sys.finish((int32_t)nent, out);
 }
 
 extern "C" int phx_assemble_poisson_flux(phx_mesh *m, const double *params, int facet_tag, int quadrature_degree,
@@ -303,39 +283,30 @@ extern "C" int phx_assemble_poisson_flux(phx_mesh *m, const double *params, int 
               "cell and facet tags must be computed before assembly");
   PHX_REQUIRE(facet_tag >= 1 && facet_tag <= 6, PHX_ERR_VALUE, "facet_tag must be one of the facet tags 1..6");
   PHX_REQUIRE(quadrature_degree >= 2 && quadrature_degree <= 15, PHX_ERR_VALUE, "quadrature_degree must be in 2..15");
-  if (m->cell_type == PHX_QUADRILATERAL) {
-    // Q1 x Q1^2 x DG0 with a Q2 level-set [nv + nf + nc] (phx_assemble_flux_quad.inc.hip); a Gauss rule of
-    // quadrature_degree / 2 + 1 points per direction integrates that degree exactly
-    const double *qphi, *qf, *qg;
-    double *q1, *q2, *q3;
-    PHX_CHECK(to_device(m, phi_h, loc, m->nv + m->nf + m->nc, &qphi, &q1));
-    PHX_CHECK(to_device(m, f_h, loc, m->nv, &qf, &q2));
-    PHX_CHECK(to_device(m, g_h, loc, m->nv, &qg, &q3));
-    PHX_CHECK(phx_begin_timing(m));
-    const int nq = std::min(8, quadrature_degree / 2 + 1);
-    int rcq = assemble_flux_quad_with_capacity(m, params, facet_tag, nq, qphi, qf, qg, 64, out);
-    if (rcq == PHX_ERR_CAPACITY) rcq = assemble_flux_quad_with_capacity(m, params, facet_tag, nq, qphi, qf, qg, 128, out);
-    if (rcq == PHX_OK) rcq = phx_end_timing(m, 2);
-    if (q1) (void)phx_free(q1);
-    if (q2) (void)phx_free(q2);
-    if (q3) (void)phx_free(q3);
-    return rcq;
-  }
-  PHX_REQUIRE(m->cell_type == PHX_TRIANGLE || m->cell_type == PHX_TETRAHEDRON,
+  const bool quad = m->cell_type == PHX_QUADRILATERAL;
+  PHX_REQUIRE(quad || m->cell_type == PHX_TRIANGLE || m->cell_type == PHX_TETRAHEDRON,
               PHX_ERR_NOT_IMPLEMENTED, "unknown cell type");
-  PHX_CHECK(phx_mesh_build_edges(m));
+  if (!quad) PHX_CHECK(phx_mesh_build_edges(m));
+  // degree-2 level-set: simplices [nv + ne]; quadrilaterals Q2 [nv + nf + nc] (phx_assemble_flux_quad.inc.hip)
+  DevTemps staged(m->stream);
   const double *dphi, *df, *dg;
-  double *o1, *o2, *o3;
-  PHX_CHECK(to_device(m, phi_h, loc, m->nv + m->ne, &dphi, &o1));
-  PHX_CHECK(to_device(m, f_h, loc, m->nv, &df, &o2));
-  PHX_CHECK(to_device(m, g_h, loc, m->nv, &dg, &o3));
+  PHX_CHECK(to_device(m, phi_h, loc, quad ? m->nv + m->nf + m->nc : m->nv + m->ne, &dphi, staged));
+  PHX_CHECK(to_device(m, f_h, loc, m->nv, &df, staged));
+  PHX_CHECK(to_device(m, g_h, loc, m->nv, &dg, staged));
   PHX_CHECK(phx_begin_timing(m));
-  int W = m->gdim == 3 ? 256 : 64;
-  int rc = assemble_flux_with_capacity(m, params, facet_tag, quadrature_degree, dphi, df, dg, W, out);
-  if (rc == PHX_ERR_CAPACITY) rc = assemble_flux_with_capacity(m, params, facet_tag, quadrature_degree, dphi, df, dg, 2 * W, out);
+  int rc;
+  if (quad) {
+    // a Gauss rule of quadrature_degree / 2 + 1 points per direction integrates that degree exactly
+    const int nq = std::min(8, quadrature_degree / 2 + 1);
+    rc = retry_capacity({64, 128}, [&](int W) {
+      return assemble_flux_quad_with_capacity(m, params, facet_tag, nq, dphi, df, dg, W, out);
+    });
+  } else {
+    const int W = m->gdim == 3 ? 256 : 64;
+    rc = retry_capacity({W, 2 * W}, [&](int Wk) {
+      return assemble_flux_with_capacity(m, params, facet_tag, quadrature_degree, dphi, df, dg, Wk, out);
+    });
+  }
   if (rc == PHX_OK) rc = phx_end_timing(m, 2);
-  if (o1) (void)phx_free(o1);
-  if (o2) (void)phx_free(o2);
-  if (o3) (void)phx_free(o3);
   return rc;
 }

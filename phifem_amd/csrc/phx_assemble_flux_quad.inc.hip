@@ -1,10 +1,9 @@
 // Neumann / Robin phi-FEM Poisson on QUADRILATERALS: mixed (u, y, p) in Q1 x Q1^2 x DG0 with a Q2 level-set --
 // the cell type of demo/neumann/square/main.py:49-50 with its forms :113-158 (and those of demo/robin/square/
 // main.py:112-168 with robin_coef != 0).  Included by phx_assemble.hip after phx_assemble_flux.inc.hip (shares
-// FxArgs' conventions, slot_add, the work-list builders).
-// Cells: axis-parallel rectangles in tensor-product vertex order v0 (0,0), v1 (1,0), v2 (0,1), v3 (1,1) -- what
-// dolfinx.mesh.create_rectangle builds; local facets f0 (v0,v1), f1 (v0,v2), f2 (v1,v3), f3 (v2,v3) [3P basix].
-// h_T = the diagonal.  Q2 level-set nodal layout: [vertices (nv), edge midpoints by facet id (nf), cell centres (nc)].
+// FxArgs' conventions, slot_add, the work-list builders) and phx_q1rect.inc.hip (the rectangle, the Q1 basis, the
+// facet numbering: the cell conventions are stated there).
+// Q2 level-set nodal layout: [vertices (nv), edge midpoints by facet id (nf), cell centres (nc)].
 // DoFs: u at vertex v -> v, y_k at vertex v -> (1 + k) nv + v, p on cell c -> 3 nv + c.
 // Cell integrals of the cut cells: tensor Gauss rule, nq points per direction (|grad phi_h| is not polynomial:
 // agreement with FFCx's Gauss-Jacobi rule to quadrature accuracy); bulk cells and edges: closed form / 3-point Gauss.
@@ -36,26 +35,6 @@ __global__ void k_fxq_mark_active(int64_t nc, FxqArgs A, uint8_t *__restrict__ f
   if (t == 2) flags[3 * A.nv + c] = 1;
 }
 
-struct RectGeo { double hx, hy, h; int32_t v[4]; };
-__device__ __forceinline__ bool rect_load(const FxqArgs &A, int64_t c, RectGeo &R) {
-  double X[4][2];
-  for (int i = 0; i < 4; ++i) {
-    R.v[i] = A.cells[c * 4 + i];
-    X[i][0] = A.x[2 * (int64_t)R.v[i]];
-    X[i][1] = A.x[2 * (int64_t)R.v[i] + 1];
-  }
-  R.hx = X[1][0] - X[0][0];
-  R.hy = X[2][1] - X[0][1];
-  R.h = sqrt(R.hx * R.hx + R.hy * R.hy);
-  const double tx = 1e-12 * fabs(R.hx), ty = 1e-12 * fabs(R.hy);
-  return R.hx > 0.0 && R.hy > 0.0 && fabs(X[1][1] - X[0][1]) <= tx && fabs(X[2][0] - X[0][0]) <= ty &&
-         fabs(X[3][0] - X[1][0]) <= tx && fabs(X[3][1] - X[2][1]) <= ty;
-}
-
-// 1-D linear element matrices on [0, 1]: stiffness A1 = [[1,-1],[-1,1]], mass M1 = [[2,1],[1,2]] / 6
-__device__ __forceinline__ double a1(int i, int j) { return i == j ? 1.0 : -1.0; }
-__device__ __forceinline__ double m1(int i, int j) { return (i == j ? 2.0 : 1.0) / 6.0; }
-
 // --- dx((1,2)): neumann main.py:114 (grad u . grad v + u v) and :144 (f v); 16 lanes per cell, closed form ----
 __global__ void __launch_bounds__(256) k_fxq_bulk(int64_t nlist, const int32_t *__restrict__ list, FxqArgs A) {
   const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -64,7 +43,7 @@ __global__ void __launch_bounds__(256) k_fxq_bulk(int64_t nlist, const int32_t *
   if (e >= nlist) return;
   const int i = l / 4, j = l % 4;
   RectGeo R;
-  if (!rect_load(A, list[e], R)) { *A.bad = 1; return; }
+  if (!rect_load(A.cells, A.x, list[e], R)) { *A.bad = 1; return; }
   const int ix = i & 1, iy = i >> 1, jx = j & 1, jy = j >> 1;
   const double K = (R.hy / R.hx) * a1(ix, jx) * m1(iy, jy) + (R.hx / R.hy) * m1(ix, jx) * a1(iy, jy);
   const double Mm = R.hx * R.hy * m1(ix, jx) * m1(iy, jy);
@@ -76,14 +55,6 @@ __global__ void __launch_bounds__(256) k_fxq_bulk(int64_t nlist, const int32_t *
   }
 }
 
-// Q1 value / physical gradient of vertex function i at reference (xi, eta)
-__device__ __forceinline__ void q1_at(int i, double xi, double eta, const RectGeo &R, double *val, double *gx, double *gy) {
-  const double lx = (i & 1) ? xi : 1.0 - xi, ly = (i >> 1) ? eta : 1.0 - eta;
-  const double dx = (i & 1) ? 1.0 : -1.0, dy = (i >> 1) ? 1.0 : -1.0;
-  *val = lx * ly;
-  *gx = dx * ly / R.hx;
-  *gy = lx * dy / R.hy;
-}
 __device__ __forceinline__ void l3_at(double t, double *L, double *dL) {
   L[0] = 2.0 * (t - 0.5) * (t - 1.0); L[1] = 4.0 * t * (1.0 - t); L[2] = 2.0 * t * (t - 0.5);
   dL[0] = 4.0 * t - 3.0; dL[1] = 4.0 - 8.0 * t; dL[2] = 4.0 * t - 1.0;
@@ -133,7 +104,7 @@ __global__ void __launch_bounds__(64) k_fxq_cut(int64_t nlist, const int32_t *__
   if (e >= nlist) return;
   const int64_t c = list[e];
   RectGeo R;
-  if (!rect_load(A, c, R)) { *A.bad = 1; return; }
+  if (!rect_load(A.cells, A.x, c, R)) { *A.bad = 1; return; }
   double ph[9];
   for (int i = 0; i < 4; ++i) ph[i] = A.phi[R.v[i]];
   for (int k = 0; k < 4; ++k) ph[4 + k] = A.phi[A.nv + A.c2f[c * 4 + k]];
@@ -178,13 +149,6 @@ __global__ void __launch_bounds__(64) k_fxq_cut(int64_t nlist, const int32_t *__
   }
 }
 
-// local facet lf of a rectangle: its two vertices, the axis of its outward normal and the sign
-__device__ __forceinline__ void quad_facet(int lf, int *va, int *vb, int *axis, double *sign) {
-  constexpr int FA[4] = {0, 0, 1, 2}, FB[4] = {1, 2, 3, 3}, AX[4] = {1, 0, 0, 1};
-  constexpr double SG[4] = {-1.0, -1.0, 1.0, 1.0};
-  *va = FA[lf]; *vb = FB[lf]; *axis = AX[lf]; *sign = SG[lf];
-}
-
 // --- ds: main.py:115  int_F (y . n) v; 4 lanes per (cell, local facet): (i, j) over the facet's two vertices ----
 __global__ void __launch_bounds__(256) k_fxq_ds(int64_t nent, const int64_t *__restrict__ ent_packed,
                                                 const int32_t *__restrict__ ent_pairs, FxqArgs A) {
@@ -197,7 +161,7 @@ __global__ void __launch_bounds__(256) k_fxq_ds(int64_t nent, const int64_t *__r
   if (ent_packed) { c = ent_packed[2 * e + 1] >> 8; lf = (int)(ent_packed[2 * e + 1] & 0xff); }
   else { c = ent_pairs[2 * e]; lf = ent_pairs[2 * e + 1]; }
   RectGeo R;
-  if (!rect_load(A, c, R)) { *A.bad = 1; return; }
+  if (!rect_load(A.cells, A.x, c, R)) { *A.bad = 1; return; }
   int va, vb, axis;
   double sign;
   quad_facet(lf, &va, &vb, &axis, &sign);
@@ -217,36 +181,26 @@ __global__ void __launch_bounds__(256) k_fxq_facets(int64_t nlist, const int32_t
   if (e >= nlist) return;
   const int a = l / 8, b = l % 8;
   const int64_t f = list[e];
-  // 3-point Gauss on [0, 1]
-  const double s15 = 0.7745966692414834 * 0.5;
-  const double tq[3] = {0.5 - s15, 0.5, 0.5 + s15}, wq[3] = {5.0 / 18.0, 8.0 / 18.0, 5.0 / 18.0};
+  constexpr Gauss3 g3 = gauss3();
   int32_t dofs[8];
   double J[3][8], hsum = 0.0, len = 0.0;
   for (int side = 0; side < 2; ++side) {
-    const int64_t c = A.f2c[2 * f + side];
-    RectGeo R;
-    if (!rect_load(A, c, R)) { *A.bad = 1; return; }
-    int lf = 0;
-    for (int k = 0; k < 4; ++k)
-      if (A.c2f[c * 4 + k] == (int32_t)f) lf = k;
-    int va, vb, axis;
-    double sign;
-    quad_facet(lf, &va, &vb, &axis, &sign);
-    if (side == 0) len = axis == 0 ? R.hy : R.hx;
-    hsum += R.h;
-    const double fixed = sign > 0.0 ? 1.0 : 0.0;
+    QuadFacetSide S;
+    if (!quad_facet_side(f, side, A.c2f, A.f2c, A.cells, A.x, S)) { *A.bad = 1; return; }
+    if (side == 0) len = S.len;
+    hsum += S.R.h;
     for (int q = 0; q < 3; ++q) {
-      const double xi = axis == 0 ? fixed : tq[q], eta = axis == 1 ? fixed : tq[q];
+      const double xi = S.axis == 0 ? S.fixed : g3.x[q], eta = S.axis == 1 ? S.fixed : g3.x[q];
       for (int i = 0; i < 4; ++i) {
         double val, gx, gy;
-        q1_at(i, xi, eta, R, &val, &gx, &gy);
-        J[q][side * 4 + i] = sign * (axis == 0 ? gx : gy);
+        q1_at(i, xi, eta, S.R, &val, &gx, &gy);
+        J[q][side * 4 + i] = S.sign * (S.axis == 0 ? gx : gy);
       }
     }
-    for (int i = 0; i < 4; ++i) dofs[side * 4 + i] = R.v[i];
+    for (int i = 0; i < 4; ++i) dofs[side * 4 + i] = S.R.v[i];
   }
   double acc = 0.0;
-  for (int q = 0; q < 3; ++q) acc += wq[q] * J[q][a] * J[q][b];
+  for (int q = 0; q < 3; ++q) acc += g3.w[q] * J[q][a] * J[q][b];
   slot_add(A.slots, A.dofmap[dofs[a]], dofs[b], A.sigma * 0.5 * hsum * len * acc);
 }
 
@@ -255,8 +209,9 @@ static int assemble_flux_quad_with_capacity(phx_mesh *m, const double *params, i
                                             phx_system **out) {
   const int64_t nent = 3 * m->nv + m->nc;
   PHX_REQUIRE(nent < INT32_MAX, PHX_ERR_VALUE, "too many DoFs for 32-bit column keys");
-  phx_system *s = new phx_system();
-  s->mesh = m; s->device = m->device; s->nfull = nent; s->slot_cap = W; s->nent = nent;
+  SystemBuild sys(m, nent, nent, W);
+  DevTemps tmp(m->stream);
+  phx_system *s = sys.s;
   const dim3 block(256);
   FxqArgs A;
   memset(&A, 0, sizeof(A));
@@ -279,66 +234,37 @@ static int assemble_flux_quad_with_capacity(phx_mesh *m, const double *params, i
       A.gw[i] = 1.0 / ((1.0 - z * z) * pp * pp);
     }
   }
-  int *bad = nullptr;
-  PHX_HIP(phx_malloc(&bad, sizeof(int)));
-  PHX_HIP(hipMemsetAsync(bad, 0, sizeof(int), m->stream));
-  A.bad = bad;
+  PHX_CHECK(rect_bad_alloc(m, tmp, &A.bad));
+  // ---- active numbering: Jacobi only, as on simplices (phx_assemble_flux.inc.hip)
   uint8_t *flags = nullptr;
-  int32_t *scan = nullptr;
-  PHX_HIP(phx_malloc(&flags, (size_t)nent));
-  PHX_HIP(phx_malloc(&scan, sizeof(int32_t) * (size_t)nent));
+  PHX_HIP(tmp.alloc(&flags, (size_t)nent));
   PHX_HIP(hipMemsetAsync(flags, 0, (size_t)nent, m->stream));
   k_fxq_mark_active<<<dim3((unsigned)phx_div_up(m->nc, 256)), block, 0, m->stream>>>(m->nc, A, flags);
-  int32_t n = 0;
-  PHX_CHECK(scan_flags(m, flags, scan, nent, &n));
-  PHX_REQUIRE(n > 0, PHX_ERR_VALUE, "no active DoF: no cell is tagged 1 or 2");
-  s->n = n; s->nu = n;   // Jacobi only, as on simplices (phx_assemble_flux.inc.hip)
-  PHX_HIP(phx_malloc(&s->dof_of_vertex_u, sizeof(int32_t) * (size_t)nent));
-  PHX_HIP(phx_malloc(&s->dof_of_vertex_p, sizeof(int32_t) * 4));
-  PHX_HIP(phx_malloc(&s->full_of_active, sizeof(int64_t) * (size_t)n));
-  k_el_numbering<<<dim3((unsigned)phx_div_up(nent, 256)), block, 0, m->stream>>>(nent, flags, scan, s->dof_of_vertex_u, s->full_of_active);
-  PHX_HIP(hipStreamSynchronize(m->stream));
-  PHX_HIP(phx_free(flags)); PHX_HIP(phx_free(scan));
+  PHX_CHECK(number_single_block(m, s, tmp, flags, nent, "no active DoF: no cell is tagged 1 or 2"));
   A.dofmap = s->dof_of_vertex_u;
-  Slots sl;
-  sl.W = W;
-  PHX_HIP(phx_malloc(&sl.cols, sizeof(int32_t) * (size_t)n * W));
-  PHX_HIP(phx_malloc(&sl.vals, sizeof(double) * (size_t)n * W));
-  PHX_HIP(phx_malloc(&sl.overflow, sizeof(int)));
-  PHX_HIP(hipMemsetAsync(sl.cols, 0xff, sizeof(int32_t) * (size_t)n * W, m->stream));
-  PHX_HIP(hipMemsetAsync(sl.vals, 0, sizeof(double) * (size_t)n * W, m->stream));
-  PHX_HIP(hipMemsetAsync(sl.overflow, 0, sizeof(int), m->stream));
-  PHX_HIP(phx_malloc(&s->rhs, sizeof(double) * (size_t)n));
-  PHX_HIP(hipMemsetAsync(s->rhs, 0, sizeof(double) * (size_t)n, m->stream));
-  A.rhs = s->rhs; A.slots = sl;
+  // ---- work lists and integration entities
   int32_t *l_om = nullptr, *l_cut = nullptr, *l_fac = nullptr;
   int64_t n_om = 0, n_cut = 0, n_fac = 0;
   PHX_CHECK(build_list(m, m->nc, SelOmega{m->cell_tags}, &l_om, &n_om));
+  tmp.adopt(l_om);
   PHX_CHECK(build_list(m, m->nc, SelCut{m->cell_tags}, &l_cut, &n_cut));
+  tmp.adopt(l_cut);
   PHX_CHECK(build_list(m, m->nf, SelFacetTagInterior{m->facet_tags, m->f2c, facet_tag}, &l_fac, &n_fac));
-  const int64_t nds = m->is_submesh ? m->nbf : (phx_collect_entities(m) == PHX_OK ? m->ent_count[0] : -1);
-  PHX_REQUIRE(nds >= 0, PHX_ERR_VALUE, "integration entities unavailable");
-  const int64_t *pk = m->is_submesh ? nullptr : m->ent_buf[0];
-  const int32_t *pr = m->is_submesh ? m->bfacets : nullptr;
+  tmp.adopt(l_fac);
+  DsEntities ds;
+  PHX_CHECK(ds_entities(m, &ds));
   PHX_REQUIRE_GRID(n_om * 16, "Neumann / Robin cell assembly");
   PHX_REQUIRE_GRID(n_fac * 64, "Neumann / Robin facet assembly");
+  // ---- slots
+  PHX_CHECK(slots_alloc(m, (int64_t)s->n * W, W, &sys.sl));
+  PHX_CHECK(rhs_alloc(m, s));
+  A.rhs = s->rhs; A.slots = sys.sl;
+  // ---- element kernels
   if (n_om) k_fxq_bulk<<<dim3((unsigned)phx_div_up(n_om * 16, 256)), block, 0, m->stream>>>(n_om, l_om, A);
   if (n_cut) k_fxq_cut<<<dim3((unsigned)n_cut), dim3(64), 0, m->stream>>>(n_cut, l_cut, A);
-  if (nds) k_fxq_ds<<<dim3((unsigned)phx_div_up(nds * 4, 256)), block, 0, m->stream>>>(nds, pk, pr, A);
+  if (ds.n) k_fxq_ds<<<dim3((unsigned)phx_div_up(ds.n * 4, 256)), block, 0, m->stream>>>(ds.n, ds.packed, ds.pairs, A);
   if (n_fac) k_fxq_facets<<<dim3((unsigned)phx_div_up(n_fac * 64, 256)), block, 0, m->stream>>>(n_fac, l_fac, A);
   PHX_HIP(hipGetLastError());
-  int hbad = 0;
-  PHX_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-  PHX_HIP(hipStreamSynchronize(m->stream));
-  PHX_HIP(phx_free(l_om)); PHX_HIP(phx_free(l_cut)); PHX_HIP(phx_free(l_fac)); PHX_HIP(phx_free(bad));
-  if (hbad) {
-    PHX_HIP(phx_free(sl.cols)); PHX_HIP(phx_free(sl.vals)); PHX_HIP(phx_free(sl.overflow));
-    phx_system_destroy(s);
-    phx_set_error("quadrilateral assembly covers axis-parallel rectangles in tensor-product vertex order");
-    return PHX_ERR_NOT_IMPLEMENTED;
-  }
-  const int rc = phx_finish_system(s, sl, (int32_t)nent);
-  if (rc != PHX_OK) { phx_system_destroy(s); return rc; }
-  *out = s;
-  return PHX_OK;
+  PHX_CHECK(rect_bad_check(m, A.bad));
+  return sys.finish((int32_t)nent, out);
 }

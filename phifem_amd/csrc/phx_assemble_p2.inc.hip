@@ -99,11 +99,12 @@ static int upload_rule(phx_mesh *m, int d, int degree, DevRule *r, std::vector<v
   conical_rule(d, degree, lam, w);
   double *dl = nullptr, *dw = nullptr;
   PHX_HIP(phx_malloc(&dl, sizeof(double) * lam.size()));
+  keep.push_back(dl);   // the caller's list owns each block from here on, also when a later step fails
   PHX_HIP(phx_malloc(&dw, sizeof(double) * w.size()));
+  keep.push_back(dw);
   PHX_HIP(hipMemcpyAsync(dl, lam.data(), sizeof(double) * lam.size(), hipMemcpyHostToDevice, m->stream));
   PHX_HIP(hipMemcpyAsync(dw, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice, m->stream));
   PHX_HIP(hipStreamSynchronize(m->stream));
-  keep.push_back(dl); keep.push_back(dw);
   r->nq = (int)w.size(); r->lam = dl; r->w = dw;
   return PHX_OK;
 }

@@ -276,30 +276,31 @@ static int assemble_sd_impl(phx_mesh *m, double stab_coef, int kphi, const doubl
   using B = LB<D, K>;
   const int64_t nent = K == 1 ? m->nv : m->nv + m->ne;
   PHX_REQUIRE(nent < INT32_MAX, PHX_ERR_VALUE, "too many DoFs for 32-bit column keys");
-  phx_system *s = new phx_system();
-  s->mesh = m; s->device = m->device; s->nfull = nent; s->slot_cap = W; s->nent = nent;
+  SystemBuild sys(m, nent, nent, W);
+  DevTemps tmp(m->stream);
+  phx_system *s = sys.s;
   s->u_vertex_block = K == 1;
   // K = 1: lattice preconditioner with the nodal weight of u = phi w folded in (phx_precond.inc.hip).  K = 2
   // stays with Jacobi: the weight estimated from diag A is off by the vertex / edge difference of the P2
   // diagonal and the refined-lattice solve does not pay (2-D 128^2: 424 vs 408 iterations).
   s->u_weighted = true;
   const dim3 block(256);
-  std::vector<void *> keep;
   SdArgs P;
   memset(&P, 0, sizeof(P));
-  PHX_CHECK(upload_rule(m, D, 2 * K + kphi, &P.cell, keep));
-  PHX_CHECK(upload_rule(m, D - 1, 2 * (K + kphi) - 1, &P.facet, keep));
-  uint8_t *fu = nullptr, *fp = nullptr;
-  int32_t *su = nullptr, *sp = nullptr;
-  PHX_HIP(phx_malloc(&fu, (size_t)nent)); PHX_HIP(phx_malloc(&fp, (size_t)nent));
-  PHX_HIP(phx_malloc(&su, sizeof(int32_t) * (size_t)nent)); PHX_HIP(phx_malloc(&sp, sizeof(int32_t) * (size_t)nent));
-  PHX_HIP(hipMemsetAsync(fu, 0, (size_t)nent, m->stream));
-  PHX_HIP(hipMemsetAsync(fp, 0, (size_t)nent, m->stream));
-  PHX_HIP(hipMemsetAsync(sp, 0, sizeof(int32_t) * (size_t)nent, m->stream));
+  PHX_CHECK(upload_rule(m, D, 2 * K + kphi, &P.cell, tmp.blocks));
+  PHX_CHECK(upload_rule(m, D - 1, 2 * (K + kphi) - 1, &P.facet, tmp.blocks));
   P.A.cells = m->cells; P.A.x = m->x; P.A.ctags = m->cell_tags; P.A.ftags = m->facet_tags;
   P.A.c2f = m->c2f; P.A.f2c = m->f2c; P.A.phi = dphi; P.A.f = df; P.A.ud = nullptr;
   P.A.gamma = 0.0; P.A.sigma = stab_coef; P.A.nv = (int32_t)nent;
   P.c2e = m->c2e; P.nvert = (int32_t)m->nv; P.kphi = kphi;
+  // ---- active numbering: one field (no p rows: fp stays clear)
+  uint8_t *fu = nullptr, *fp = nullptr;
+  int32_t *su = nullptr, *sp = nullptr;
+  PHX_HIP(tmp.alloc(&fu, (size_t)nent)); PHX_HIP(tmp.alloc(&fp, (size_t)nent));
+  PHX_HIP(tmp.alloc(&su, sizeof(int32_t) * (size_t)nent)); PHX_HIP(tmp.alloc(&sp, sizeof(int32_t) * (size_t)nent));
+  PHX_HIP(hipMemsetAsync(fu, 0, (size_t)nent, m->stream));
+  PHX_HIP(hipMemsetAsync(fp, 0, (size_t)nent, m->stream));
+  PHX_HIP(hipMemsetAsync(sp, 0, sizeof(int32_t) * (size_t)nent, m->stream));
   k_sd_mark_active<D, K><<<dim3((unsigned)phx_div_up(m->nc, 256)), block, 0, m->stream>>>(m->nc, P, fu);
   int32_t nu = 0;
   PHX_CHECK(scan_flags(m, fu, su, nent, &nu));
@@ -310,46 +311,30 @@ static int assemble_sd_impl(phx_mesh *m, double stab_coef, int kphi, const doubl
   PHX_HIP(phx_malloc(&s->full_of_active, sizeof(int64_t) * (size_t)s->n));
   k_finish_numbering<<<dim3((unsigned)phx_div_up(nent, 256)), block, 0, m->stream>>>(
       nent, fu, fp, su, sp, nu, s->dof_of_vertex_u, s->dof_of_vertex_p, s->full_of_active);
-  PHX_HIP(hipStreamSynchronize(m->stream));
-  PHX_HIP(phx_free(fu)); PHX_HIP(phx_free(fp)); PHX_HIP(phx_free(su)); PHX_HIP(phx_free(sp));
-  Slots sl;
-  sl.W = W;
-  PHX_HIP(phx_malloc(&sl.cols, sizeof(int32_t) * (size_t)s->n * W));
-  PHX_HIP(phx_malloc(&sl.vals, sizeof(double) * (size_t)s->n * W));
-  PHX_HIP(phx_malloc(&sl.overflow, sizeof(int)));
-  PHX_HIP(hipMemsetAsync(sl.cols, 0xff, sizeof(int32_t) * (size_t)s->n * W, m->stream));
-  PHX_HIP(hipMemsetAsync(sl.vals, 0, sizeof(double) * (size_t)s->n * W, m->stream));
-  PHX_HIP(hipMemsetAsync(sl.overflow, 0, sizeof(int), m->stream));
-  PHX_HIP(phx_malloc(&s->rhs, sizeof(double) * (size_t)s->n));
-  PHX_HIP(hipMemsetAsync(s->rhs, 0, sizeof(double) * (size_t)s->n, m->stream));
-  P.A.du = s->dof_of_vertex_u; P.A.dp = s->dof_of_vertex_p; P.A.rhs = s->rhs; P.A.slots = sl;
+  // ---- work lists and integration entities
   int32_t *l_om = nullptr, *l_fac = nullptr;
   int64_t n_om = 0, n_fac = 0;
   PHX_CHECK(build_list(m, m->nc, SelOmega{m->cell_tags}, &l_om, &n_om));
+  tmp.adopt(l_om);
   PHX_CHECK(build_list(m, m->nf, SelGhostFacet{m->facet_tags, m->f2c}, &l_fac, &n_fac));
+  tmp.adopt(l_fac);
+  DsEntities ds;
+  PHX_CHECK(ds_entities(m, &ds));
   constexpr int GS = B::NB * B::NB <= 16 ? 16 : (B::NB * B::NB <= 64 ? 64 : 128);
-  if (n_om > 0) {
-    PHX_REQUIRE_GRID(n_om * GS, "strong-Dirichlet cell assembly");
+  PHX_REQUIRE_GRID(n_om * GS, "strong-Dirichlet cell assembly");
+  // ---- slots
+  PHX_CHECK(slots_alloc(m, s->n * W, W, &sys.sl));
+  PHX_CHECK(rhs_alloc(m, s));
+  P.A.du = s->dof_of_vertex_u; P.A.dp = s->dof_of_vertex_p; P.A.rhs = s->rhs; P.A.slots = sys.sl;
+  // ---- element kernels
+  if (n_om > 0)
     k_sd_cells<D, K, GS><<<dim3((unsigned)phx_div_up(n_om * GS, 256)), block, 0, m->stream>>>(n_om, l_om, P);
-  }
-  PHX_HIP(hipGetLastError());
-  const int64_t nds = m->is_submesh ? m->nbf : (phx_collect_entities(m) == PHX_OK ? m->ent_count[0] : -1);
-  PHX_REQUIRE(nds >= 0, PHX_ERR_VALUE, "integration entities unavailable");
-  if (nds > 0) {
-    const int64_t *pk = m->is_submesh ? nullptr : m->ent_buf[0];
-    const int32_t *pr = m->is_submesh ? m->bfacets : nullptr;
-    k_sd_ds<D, K, GS><<<dim3((unsigned)phx_div_up(nds * GS, 256)), block, 0, m->stream>>>(nds, pk, pr, P);
-  }
+  if (ds.n > 0)
+    k_sd_ds<D, K, GS><<<dim3((unsigned)phx_div_up(ds.n * GS, 256)), block, 0, m->stream>>>(ds.n, ds.packed, ds.pairs, P);
   if (n_fac > 0)
     k_sd_facets<D, K><<<dim3((unsigned)n_fac), dim3(K == 1 ? 64 : 256), 0, m->stream>>>(n_fac, l_fac, P);
   PHX_HIP(hipGetLastError());
-  PHX_HIP(hipStreamSynchronize(m->stream));
-  PHX_HIP(phx_free(l_om)); PHX_HIP(phx_free(l_fac));
-  for (void *p : keep) PHX_HIP(phx_free(p));
-  const int rc = phx_finish_system(s, sl, (int32_t)nent);
-  if (rc != PHX_OK) { phx_system_destroy(s); return rc; }
-  *out = s;
-  return PHX_OK;
+  return sys.finish((int32_t)nent, out);
 }
 
 static int assemble_sd_with_capacity(phx_mesh *m, double stab_coef, int degree, int kphi, const double *dphi,
@@ -371,16 +356,15 @@ extern "C" int phx_assemble_poisson_sd(phx_mesh *m, double stab_coef, int degree
   PHX_REQUIRE(phi_degree == 1 || phi_degree == 2, PHX_ERR_VALUE, "phi_degree must be 1 or 2");
   if (degree == 2 || phi_degree == 2) PHX_CHECK(phx_mesh_build_edges(m));
   const int64_t nent = m->nv + m->ne;
+  DevTemps staged(m->stream);
   const double *dphi, *df;
-  double *o1, *o2;
-  PHX_CHECK(to_device(m, phi_h, loc, phi_degree == 1 ? m->nv : nent, &dphi, &o1));
-  PHX_CHECK(to_device(m, f_h, loc, degree == 1 ? m->nv : nent, &df, &o2));
+  PHX_CHECK(to_device(m, phi_h, loc, phi_degree == 1 ? m->nv : nent, &dphi, staged));
+  PHX_CHECK(to_device(m, f_h, loc, degree == 1 ? m->nv : nent, &df, staged));
   PHX_CHECK(phx_begin_timing(m));
-  int W = degree == 1 ? (m->gdim == 3 ? 64 : 32) : (m->gdim == 3 ? 256 : 128);
-  int rc = assemble_sd_with_capacity(m, stab_coef, degree, phi_degree, dphi, df, W, out);
-  if (rc == PHX_ERR_CAPACITY) rc = assemble_sd_with_capacity(m, stab_coef, degree, phi_degree, dphi, df, 2 * W, out);
+  const int W = degree == 1 ? (m->gdim == 3 ? 64 : 32) : (m->gdim == 3 ? 256 : 128);
+  int rc = retry_capacity({W, 2 * W}, [&](int Wk) {
+    return assemble_sd_with_capacity(m, stab_coef, degree, phi_degree, dphi, df, Wk, out);
+  });
   if (rc == PHX_OK) rc = phx_end_timing(m, 2);
-  if (o1) (void)phx_free(o1);
-  if (o2) (void)phx_free(o2);
   return rc;
 }

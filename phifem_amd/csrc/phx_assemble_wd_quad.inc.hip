@@ -1,11 +1,8 @@
 // Weak-Dirichlet phi-FEM Poisson on QUADRILATERALS: mixed (u, p) in Q1 x Q1 with Q1 nodal phi_h, f_h, u_D -- the
 // forms of demo/weak-dirichlet/flower/main.py:112-135 (bilinear) and :142-151 (linear), which are independent of the
 // cell type, on the second 2-D cell type of mesh_scripts.py:322-325.  Included by phx_assemble.hip after
-// phx_assemble_flux_quad.inc.hip (RectGeo, a1 / m1, q1_at, quad_facet); dispatched to by phx_assemble_poisson_wd.
-// Cells: axis-parallel rectangles in tensor-product vertex order v0 (0,0), v1 (1,0), v2 (0,1), v3 (1,1); local
-// facets in basix numbering f0 (v0,v1), f1 (v0,v2), f2 (v1,v3), f3 (v2,v3); h_T = the diagonal (CellDiameter),
-// avg(h_T) = the mean of the two diagonals.  A cell that is not such a rectangle sets *A.bad: the assembly then
-// fails with PHX_ERR_NOT_IMPLEMENTED.  Restated in tests/poisson_quad_ref.py.
+// phx_q1rect.inc.hip (the rectangle, the Q1 basis, the facet numbering, the Gauss rules: the cell conventions are
+// stated there); dispatched to by phx_assemble_poisson_wd.  Restated in tests/poisson_quad_ref.py.
 // DoFs, activity and numbering are those of the P1 path (assemble_with_capacity): u at vertex v -> v, p at vertex
 // v -> nv + v; u active on the vertices of cells tagged 1 / 2, p on those of cells tagged 2; u rows first.
 //
@@ -32,25 +29,6 @@ struct WdqArgs {
   int *bad;   // set when a cell is not an axis-parallel rectangle
 };
 
-__device__ __forceinline__ bool wdq_rect(const WdqArgs &A, int64_t c, RectGeo &R) {
-  double X[4][2];
-  for (int i = 0; i < 4; ++i) {
-    R.v[i] = A.cells[c * 4 + i];
-    X[i][0] = A.x[2 * (int64_t)R.v[i]];
-    X[i][1] = A.x[2 * (int64_t)R.v[i] + 1];
-  }
-  R.hx = X[1][0] - X[0][0];
-  R.hy = X[2][1] - X[0][1];
-  R.h = sqrt(R.hx * R.hx + R.hy * R.hy);
-  const double tx = 1e-12 * fabs(R.hx), ty = 1e-12 * fabs(R.hy);
-  return R.hx > 0.0 && R.hy > 0.0 && fabs(X[1][1] - X[0][1]) <= tx && fabs(X[2][0] - X[0][0]) <= ty &&
-         fabs(X[3][0] - X[1][0]) <= tx && fabs(X[3][1] - X[2][1]) <= ty;
-}
-
-// 2-point Gauss on [0, 1] (weights 1/2)
-#define WDQ_G2A (0.5 - 0.5 / 1.7320508075688772)
-#define WDQ_G2B (0.5 + 0.5 / 1.7320508075688772)
-
 // --- dx((1,2)): main.py:113 grad u . grad v and :143 f_h v; 16 lanes per cell, closed form ----------------------
 __global__ void __launch_bounds__(256) k_wdq_bulk(int64_t nlist, const int32_t *__restrict__ list, WdqArgs A) {
   const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -58,7 +36,7 @@ __global__ void __launch_bounds__(256) k_wdq_bulk(int64_t nlist, const int32_t *
   if (e >= nlist) return;
   const int i = (int)(gid & 15) >> 2, j = (int)(gid & 3);
   RectGeo R;
-  if (!wdq_rect(A, list[e], R)) { *A.bad = 1; return; }
+  if (!rect_load(A.cells, A.x, list[e], R)) { *A.bad = 1; return; }
   const int ix = i & 1, iy = i >> 1, jx = j & 1, jy = j >> 1;
   const double K = (R.hy / R.hx) * a1(ix, jx) * m1(iy, jy) + (R.hx / R.hy) * m1(ix, jx) * a1(iy, jy);
   const int32_t row = A.du[R.v[i]];
@@ -78,24 +56,14 @@ __global__ void __launch_bounds__(256) k_wdq_bulk(int64_t nlist, const int32_t *
 __global__ void __launch_bounds__(256) k_wdq_cut(int64_t nlist, const int32_t *__restrict__ list, WdqArgs A) {
   constexpr int NQ = 9;
   __shared__ double sN[NQ][4], sW[NQ];
-  if (threadIdx.x < NQ) {
-    const double s15 = 0.7745966692414834 * 0.5;
-    const double gx[3] = {0.5 - s15, 0.5, 0.5 + s15}, gw[3] = {5.0 / 18.0, 8.0 / 18.0, 5.0 / 18.0};
-    const int qx = threadIdx.x / 3, qy = threadIdx.x % 3;
-    const double xi = gx[qx], eta = gx[qy];
-    sW[threadIdx.x] = gw[qx] * gw[qy];
-    sN[threadIdx.x][0] = (1.0 - xi) * (1.0 - eta);
-    sN[threadIdx.x][1] = xi * (1.0 - eta);
-    sN[threadIdx.x][2] = (1.0 - xi) * eta;
-    sN[threadIdx.x][3] = xi * eta;
-  }
+  if (threadIdx.x < NQ) sW[threadIdx.x] = q1_tab9(threadIdx.x, nullptr, sN[threadIdx.x], nullptr);
   __syncthreads();
   const int64_t gid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   const int64_t e = gid >> 4;
   if (e >= nlist) return;
   const int i = (int)(gid & 15) >> 2, j = (int)(gid & 3);
   RectGeo R;
-  if (!wdq_rect(A, list[e], R)) { *A.bad = 1; return; }
+  if (!rect_load(A.cells, A.x, list[e], R)) { *A.bad = 1; return; }
   double ph[4];
   for (int k = 0; k < 4; ++k) ph[k] = A.phi[R.v[k]];
   double M0 = 0.0, M1 = 0.0, M2 = 0.0;
@@ -142,20 +110,20 @@ __global__ void __launch_bounds__(256) k_wdq_ds(int64_t nent, const int64_t *__r
   if (ent_packed) { c = ent_packed[2 * e + 1] >> 8; lf = (int)(ent_packed[2 * e + 1] & 0xff); }
   else { c = ent_pairs[2 * e]; lf = ent_pairs[2 * e + 1]; }
   RectGeo R;
-  if (!wdq_rect(A, c, R)) { *A.bad = 1; return; }
+  if (!rect_load(A.cells, A.x, c, R)) { *A.bad = 1; return; }
   int va, vb, axis;
   double sign;
   quad_facet(lf, &va, &vb, &axis, &sign);
   if (i != va && i != vb) return;   // v vanishes on the facet
   const double fixed = sign > 0.0 ? 1.0 : 0.0, len = axis == 0 ? R.hy : R.hx;
-  const double tq[2] = {WDQ_G2A, WDQ_G2B};
+  constexpr Gauss2 g2 = gauss2();
   double acc = 0.0;
   for (int q = 0; q < 2; ++q) {
-    const double xi = axis == 0 ? fixed : tq[q], eta = axis == 1 ? fixed : tq[q];
+    const double xi = axis == 0 ? fixed : g2.x[q], eta = axis == 1 ? fixed : g2.x[q];
     double vi, vj, gx, gy, t0, t1;
     q1_at(i, xi, eta, R, &vi, &t0, &t1);
     q1_at(j, xi, eta, R, &vj, &gx, &gy);
-    acc += 0.5 * vi * sign * (axis == 0 ? gx : gy);
+    acc += g2.w[q] * vi * sign * (axis == 0 ? gx : gy);
   }
   slot_add(A.slots, A.du[R.v[i]], R.v[j], -len * acc);
 }
@@ -171,33 +139,26 @@ __global__ void __launch_bounds__(256) k_wdq_facets(int64_t nlist, const int32_t
   if (e >= nlist) return;
   const int l = (int)(gid & 15);
   const int64_t f = list[e];
-  const double tq[2] = {WDQ_G2A, WDQ_G2B};
+  constexpr Gauss2 g2 = gauss2();
   int32_t vd[6] = {0, 0, 0, 0, 0, 0};
   double J[2][6] = {{0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}}, hsum = 0.0, len = 0.0;
   int next = 4;
 #pragma unroll
   for (int side = 0; side < 2; ++side) {
-    const int64_t c = A.f2c[2 * f + side];
-    RectGeo R;
-    if (!wdq_rect(A, c, R)) { *A.bad = 1; return; }
-    int lf = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (A.c2f[c * 4 + k] == (int32_t)f) lf = k;
-    int va, vb, axis;
-    double sign;
-    quad_facet(lf, &va, &vb, &axis, &sign);
-    if (side == 0) len = axis == 0 ? R.hy : R.hx;
+    QuadFacetSide S;
+    if (!quad_facet_side(f, side, A.c2f, A.f2c, A.cells, A.x, S)) { *A.bad = 1; return; }
+    const RectGeo &R = S.R;
+    const int va = S.va, vb = S.vb;
+    if (side == 0) len = S.len;
     hsum += R.h;
-    const double fixed = sign > 0.0 ? 1.0 : 0.0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       double Ji[2];
       for (int q = 0; q < 2; ++q) {
-        const double xi = axis == 0 ? fixed : tq[q], eta = axis == 1 ? fixed : tq[q];
+        const double xi = S.axis == 0 ? S.fixed : g2.x[q], eta = S.axis == 1 ? S.fixed : g2.x[q];
         double val, gx, gy;
         q1_at(i, xi, eta, R, &val, &gx, &gy);
-        Ji[q] = sign * (axis == 0 ? gx : gy);
+        Ji[q] = S.sign * (S.axis == 0 ? gx : gy);
       }
       if (side == 0) {
         vd[i] = R.v[i]; J[0][i] = Ji[0]; J[1][i] = Ji[1];
@@ -231,20 +192,18 @@ __global__ void __launch_bounds__(256) k_wdq_facets(int64_t nlist, const int32_t
 static int assemble_wd_quad_with_capacity(phx_mesh *m, double pen_coef, double stab_coef, const double *dphi,
                                           const double *df, const double *dud, int W, phx_system **out) {
   PHX_REQUIRE(2 * m->nv < INT32_MAX, PHX_ERR_VALUE, "too many DoFs for 32-bit column keys");
-  phx_system *s = new phx_system();
-  s->mesh = m;
-  s->device = m->device;
-  s->nent = m->nv;
-  s->nfull = 2 * m->nv;
-  s->slot_cap = W;
+  SystemBuild sys(m, m->nv, 2 * m->nv, W);
+  DevTemps tmp(m->stream);
+  phx_system *s = sys.s;
+  Slots &sl = sys.sl;
   s->u_vertex_block = true;
   const dim3 block(256);
   // ---- active numbering (assemble_with_capacity)
   uint8_t *fu = nullptr, *fp = nullptr;
   unsigned long long *sup = nullptr;
-  PHX_HIP(phx_malloc(&sup, sizeof(unsigned long long) * (size_t)m->nv));
-  PHX_HIP(phx_malloc(&fu, (size_t)m->nv));
-  PHX_HIP(phx_malloc(&fp, (size_t)m->nv));
+  PHX_HIP(tmp.alloc(&sup, sizeof(unsigned long long) * (size_t)m->nv));
+  PHX_HIP(tmp.alloc(&fu, (size_t)m->nv));
+  PHX_HIP(tmp.alloc(&fp, (size_t)m->nv));
   PHX_HIP(hipMemsetAsync(fu, 0, (size_t)m->nv, m->stream));
   PHX_HIP(hipMemsetAsync(fp, 0, (size_t)m->nv, m->stream));
   k_mark_active<4><<<dim3((unsigned)phx_div_up(phx_div_up(m->nc, 4), 256)), block, 0, m->stream>>>(m->nc, m->cells,
@@ -253,13 +212,7 @@ static int assemble_wd_quad_with_capacity(phx_mesh *m, double pen_coef, double s
   PHX_CHECK(scan_flags_packed(m, fu, fp, sup, &nu, &np, m->nv));
   s->nu = nu;
   s->n = (int64_t)nu + np;
-  if (s->n == 0) {
-    PHX_HIP(hipStreamSynchronize(m->stream));
-    PHX_HIP(phx_free(fu)); PHX_HIP(phx_free(fp)); PHX_HIP(phx_free(sup));
-    delete s;
-    phx_set_error("no active DoF: no cell is tagged 1 or 2");
-    return PHX_ERR_VALUE;
-  }
+  PHX_REQUIRE(s->n > 0, PHX_ERR_VALUE, "no active DoF: no cell is tagged 1 or 2");
   PHX_HIP(phx_malloc(&s->dof_of_vertex_u, sizeof(int32_t) * (size_t)m->nv));
   PHX_HIP(phx_malloc(&s->dof_of_vertex_p, sizeof(int32_t) * (size_t)m->nv));
   PHX_HIP(phx_malloc(&s->full_of_active, sizeof(int64_t) * (size_t)s->n));
@@ -269,37 +222,27 @@ static int assemble_wd_quad_with_capacity(phx_mesh *m, double pen_coef, double s
   int32_t *l_om = nullptr, *l_cut = nullptr, *l_fac = nullptr;
   int64_t n_om = 0, n_cut = 0, n_fac = 0;
   PHX_CHECK(build_list(m, m->nc, SelOmega{m->cell_tags}, &l_om, &n_om));
+  tmp.adopt(l_om);
   PHX_CHECK(build_list(m, m->nc, SelCut{m->cell_tags}, &l_cut, &n_cut));
+  tmp.adopt(l_cut);
   PHX_CHECK(build_list(m, m->nf, SelGhostFacet{m->facet_tags, m->f2c}, &l_fac, &n_fac));
-  // main.py:74: ds = every exterior facet of the sub-mesh; main.py:65: ds = ds_bdy(100)
-  const int64_t nds = m->is_submesh ? m->nbf : (phx_collect_entities(m) == PHX_OK ? m->ent_count[0] : -1);
-  PHX_REQUIRE(nds >= 0, PHX_ERR_VALUE, "integration entities unavailable");
-  const int64_t *pk = m->is_submesh ? nullptr : m->ent_buf[0];
-  const int32_t *pr = m->is_submesh ? m->bfacets : nullptr;
+  tmp.adopt(l_fac);
+  DsEntities ds;
+  PHX_CHECK(ds_entities(m, &ds));
   PHX_REQUIRE_GRID(n_om * 16, "quadrilateral cell assembly");
   PHX_REQUIRE_GRID(n_fac * 16, "quadrilateral facet assembly");
-  PHX_REQUIRE_GRID(nds * 16, "quadrilateral boundary assembly");
+  PHX_REQUIRE_GRID(ds.n * 16, "quadrilateral boundary assembly");
   // ---- slots
-  Slots sl;
-  sl.W = W;
   const int64_t nslots = s->n * W;
-  PHX_HIP(phx_malloc(&sl.cols, sizeof(int32_t) * (size_t)nslots));
-  PHX_HIP(phx_malloc(&sl.vals, sizeof(double) * (size_t)nslots));
-  PHX_HIP(phx_malloc(&sl.overflow, sizeof(int)));
-  PHX_HIP(hipMemsetAsync(sl.cols, 0xff, sizeof(int32_t) * (size_t)nslots, m->stream));
-  PHX_HIP(hipMemsetAsync(sl.vals, 0, sizeof(double) * (size_t)nslots, m->stream));
-  PHX_HIP(hipMemsetAsync(sl.overflow, 0, sizeof(int), m->stream));
-  PHX_HIP(phx_malloc(&s->rhs, sizeof(double) * (size_t)s->n));
-  PHX_HIP(hipMemsetAsync(s->rhs, 0, sizeof(double) * (size_t)s->n, m->stream));
-  int *bad = nullptr;
-  PHX_HIP(phx_malloc(&bad, sizeof(int)));
-  PHX_HIP(hipMemsetAsync(bad, 0, sizeof(int), m->stream));
+  PHX_CHECK(slots_alloc(m, nslots, W, &sl));
+  PHX_CHECK(rhs_alloc(m, s));
   WdqArgs A;
   A.cells = m->cells; A.c2f = m->c2f; A.f2c = m->f2c; A.x = m->x;
   A.phi = dphi; A.f = df; A.ud = dud;
   A.du = s->dof_of_vertex_u; A.dp = s->dof_of_vertex_p; A.nv = (int32_t)m->nv;
-  A.gamma = pen_coef; A.sigma = stab_coef; A.rhs = s->rhs; A.bad = bad;
-  // PHX_OPT_DETERMINISTIC: exponent pass, then the exact accumulation pass (Slots)
+  A.gamma = pen_coef; A.sigma = stab_coef; A.rhs = s->rhs;
+  PHX_CHECK(rect_bad_alloc(m, tmp, &A.bad));
+  // ---- element kernels.  PHX_OPT_DETERMINISTIC: exponent pass, then the exact accumulation pass (Slots)
   bool det = false;
   PHX_CHECK(det_alloc(m, sl, nslots, s->n, &det));
   for (int pass = det ? 1 : 0; pass <= (det ? 2 : 0); ++pass) {
@@ -307,24 +250,11 @@ static int assemble_wd_quad_with_capacity(phx_mesh *m, double pen_coef, double s
     A.slots = sl;
     if (n_om) k_wdq_bulk<<<dim3((unsigned)phx_div_up(n_om * 16, 256)), block, 0, m->stream>>>(n_om, l_om, A);
     if (n_cut) k_wdq_cut<<<dim3((unsigned)phx_div_up(n_cut * 16, 256)), block, 0, m->stream>>>(n_cut, l_cut, A);
-    if (nds) k_wdq_ds<<<dim3((unsigned)phx_div_up(nds * 16, 256)), block, 0, m->stream>>>(nds, pk, pr, A);
+    if (ds.n) k_wdq_ds<<<dim3((unsigned)phx_div_up(ds.n * 16, 256)), block, 0, m->stream>>>(ds.n, ds.packed, ds.pairs, A);
     if (n_fac) k_wdq_facets<<<dim3((unsigned)phx_div_up(n_fac * 16, 256)), block, 0, m->stream>>>(n_fac, l_fac, A);
     PHX_HIP(hipGetLastError());
   }
   PHX_CHECK(det_finish(m, sl, nslots, s->n, s->rhs));
-  int hbad = 0;
-  PHX_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, m->stream));
-  PHX_HIP(hipStreamSynchronize(m->stream));
-  PHX_HIP(phx_free(fu)); PHX_HIP(phx_free(fp)); PHX_HIP(phx_free(sup));
-  PHX_HIP(phx_free(l_om)); PHX_HIP(phx_free(l_cut)); PHX_HIP(phx_free(l_fac)); PHX_HIP(phx_free(bad));
-  if (hbad) {
-    PHX_HIP(phx_free(sl.cols)); PHX_HIP(phx_free(sl.vals)); PHX_HIP(phx_free(sl.overflow));
-    phx_system_destroy(s);
-    phx_set_error("quadrilateral assembly covers axis-parallel rectangles in tensor-product vertex order");
-    return PHX_ERR_NOT_IMPLEMENTED;
-  }
-  const int rc = phx_finish_system(s, sl, (int32_t)m->nv);
-  if (rc != PHX_OK) { phx_system_destroy(s); return rc; }
-  *out = s;
-  return PHX_OK;
+  PHX_CHECK(rect_bad_check(m, A.bad));
+  return sys.finish((int32_t)m->nv, out);
 }

@@ -210,18 +210,10 @@ k_cell_errors_quad(int64_t ncells, const int32_t *__restrict__ list, const int32
   double s[4] = {0.0, 0.0, 0.0, 0.0};   // l2, h10, |I u_ex|^2, |grad I u_ex|^2 of this cell
   if (i < ncells) {
     const int64_t c = list ? list[i] : i;
-    int32_t v[4];
-    double X[4][2];
-    for (int k = 0; k < 4; ++k) {
-      v[k] = cells[c * 4 + k];
-      X[k][0] = x[2 * (int64_t)v[k]];
-      X[k][1] = x[2 * (int64_t)v[k] + 1];
-    }
-    const double hx = X[1][0] - X[0][0], hy = X[2][1] - X[0][1];
-    const double tx = 1e-12 * fabs(hx), ty = 1e-12 * fabs(hy);
-    if (!(hx > 0.0 && hy > 0.0 && fabs(X[1][1] - X[0][1]) <= tx && fabs(X[2][0] - X[0][0]) <= ty &&
-          fabs(X[3][0] - X[1][0]) <= tx && fabs(X[3][1] - X[2][1]) <= ty))
-      *bad = 1;
+    RectGeo R;
+    if (!rect_load(cells, x, c, R)) *bad = 1;
+    const int32_t *v = R.v;
+    const double hx = R.hx, hy = R.hy;
     for (int cp = 0; cp < ncomp; ++cp) {
       double e[NB], r[NB], un[4];
       for (int k = 0; k < 4; ++k) un[k] = uh[(int64_t)cp * ndh + v[k]];
@@ -292,25 +284,20 @@ static int cell_errors_quad(phx_mesh *m, int ncomp, const double *duh, const dou
     }
   }
   hipStream_t st = m->stream;
+  DevTemps tmp(st);
   double *partial = nullptr, *dsum = nullptr;
   int *bad = nullptr;
   const int64_t nblocks = phx_div_up(ncells, ERR_THREADS);
-  PHX_HIP(phx_malloc(&partial, sizeof(double) * (size_t)nblocks * 4));
-  PHX_HIP(phx_malloc(&dsum, sizeof(double) * 4));
-  PHX_HIP(phx_malloc(&bad, sizeof(int)));
-  PHX_HIP(hipMemsetAsync(bad, 0, sizeof(int), st));
+  PHX_HIP(tmp.alloc(&partial, sizeof(double) * (size_t)nblocks * 4));
+  PHX_HIP(tmp.alloc(&dsum, sizeof(double) * 4));
+  PHX_CHECK(rect_bad_alloc(m, tmp, &bad));
   PHX_REQUIRE_GRID(nblocks * ERR_THREADS, "cell errors");
   k_cell_errors_quad<<<dim3((unsigned)nblocks), dim3(ERR_THREADS), 0, st>>>(
       ncells, dlist, m->cells, m->x, ncomp, m->nv, duh, duref, T, dl2, dh10, partial, bad);
   k_sum_partials<<<dim3(1), dim3(256), 0, st>>>(nblocks, partial, dsum);
   PHX_HIP(hipGetLastError());
-  int hbad = 0;
   PHX_HIP(hipMemcpyAsync(norms_host, dsum, sizeof(double) * 4, hipMemcpyDeviceToHost, st));
-  PHX_HIP(hipMemcpyAsync(&hbad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
-  PHX_HIP(hipStreamSynchronize(st));
-  PHX_HIP(phx_free(partial)); PHX_HIP(phx_free(dsum)); PHX_HIP(phx_free(bad));
-  PHX_REQUIRE(!hbad, PHX_ERR_NOT_IMPLEMENTED, "error evaluation on quadrilaterals covers axis-parallel rectangles only");
-  return PHX_OK;
+  return rect_bad_check(m, bad);
 }
 
 template <int D>

@@ -123,6 +123,14 @@ void phx_pool_trim(void) {
 
 extern "C" int phx_pool_release(void) { phx_pool_trim(); return PHX_OK; }
 
+extern "C" int phx_pool_stats(int64_t *live_bytes, int64_t *cached_bytes) {
+  Pool &P = pool();
+  std::lock_guard<std::mutex> lk(P.mu);
+  if (live_bytes) *live_bytes = (int64_t)P.live_bytes;
+  if (cached_bytes) *cached_bytes = (int64_t)P.cached;
+  return PHX_OK;
+}
+
 extern "C" int phx_version(void) { return 1; }
 extern "C" const char *phx_last_error(void) { return g_err; }
 extern "C" int phx_device_count(int *n) {
