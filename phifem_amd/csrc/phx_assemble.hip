@@ -89,10 +89,10 @@ __global__ void k_finish_numbering_packed(int64_t nv, const uint8_t *__restrict_
 // slot with a CAS; values accumulate with hardware f64 atomics (global_atomic_add_f64).
 // ---------------------------------------------------------------------------------------------
 struct Slots {
-  int32_t *cols;
-  double *vals;
-  int W;
-  int *overflow;
+  int32_t *cols = nullptr;
+  double *vals = nullptr;
+  int W = 0;
+  int *overflow = nullptr;
   // clean[row] = c > 0: the row has one writer (the gather kernel) that stored its c entries at slots
   // 0 .. c-1 in ascending column order: no hashing, no sort at compaction.  nullptr: no such rows.
   uint8_t *clean = nullptr;
@@ -1088,10 +1088,8 @@ static int det_finish(phx_mesh *m, Slots &sl, int64_t nslots, int64_t nrows, dou
 }
 
 template <typename Pred>
-static int build_list(phx_mesh *m, int64_t n, Pred pred, int32_t **list, int64_t *count,
-                      std::vector<void *> *later = nullptr, const int32_t *known_counts = nullptr,
-                      int64_t known_total = -1) {
-  return phx_select_indices(m->stream, n, pred, list, count, later, known_counts, known_total);
+static int build_list(phx_mesh *m, int64_t n, Pred pred, int32_t **list, int64_t *count) {
+  return phx_select_indices(m->stream, n, pred, list, count);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1355,28 +1353,6 @@ static int scan_flags_packed(phx_mesh *m, const uint8_t *fa, const uint8_t *fb, 
   return PHX_OK;
 }
 
-// two flag arrays scanned behind each other, both totals with ONE host round trip
-static int scan_flags2(phx_mesh *m, const uint8_t *fa, int32_t *oa, int32_t *ta, const uint8_t *fb, int32_t *ob,
-                       int32_t *tb, int64_t n) {
-  auto ia = rocprim::make_transform_iterator(fa, U8ToI32());
-  auto ib = rocprim::make_transform_iterator(fb, U8ToI32());
-  size_t bytes = 0;
-  PHX_HIP(phx_exclusive_sum(nullptr, bytes, ia, oa, (size_t)(n), m->stream));
-  void *tmp = nullptr;
-  PHX_HIP(phx_malloc(&tmp, bytes ? bytes : 16));
-  PHX_HIP(phx_exclusive_sum(tmp, bytes, ia, oa, (size_t)(n), m->stream));
-  PHX_HIP(phx_exclusive_sum(tmp, bytes, ib, ob, (size_t)(n), m->stream));
-  int32_t last[2] = {0, 0};
-  uint8_t lastf[2] = {0, 0};
-  const phx_rb_item rb[4] = {{oa + (n - 1), 4, &last[0]}, {fa + (n - 1), 1, &lastf[0]}, {ob + (n - 1), 4, &last[1]},
-                             {fb + (n - 1), 1, &lastf[1]}};
-  PHX_CHECK(phx_read_back(m->stream, rb, 4));
-  PHX_HIP(phx_free(tmp));
-  *ta = last[0] + (int32_t)lastf[0];
-  *tb = last[1] + (int32_t)lastf[1];
-  return PHX_OK;
-}
-
 extern "C" int phx_system_destroy(phx_system *s) {
   if (!s) return PHX_OK;
   // the mesh handle may already be gone (interpreter shutdown destroys in arbitrary order)
@@ -1604,310 +1580,9 @@ static int csr_from_slots(phx_system *s, Slots &sl, int32_t nent) {
   return PHX_OK;
 }
 
-static int assemble_with_capacity(phx_mesh *m, double pen_coef, double stab_coef,
-                                  const double *dphi, const double *df, const double *dud, int W,
-                                  phx_system **out) {
-  phx_system *s = new phx_system();
-  s->mesh = m;
-  s->device = m->device;
-  s->nent = m->nv;
-  s->nfull = 2 * m->nv;
-  s->slot_cap = W;
-  s->u_vertex_block = true;
-  const int D = m->gdim;
-  const dim3 block(256);
-  // ---- active numbering
-  uint8_t *fu = nullptr, *fp = nullptr;
-  unsigned long long *sup = nullptr;
-  PHX_HIP(phx_malloc(&sup, sizeof(unsigned long long) * (size_t)m->nv));
-  // the single-layer tagging pass left the vertex flags behind (inside cells; cells that stayed cut): no walk over the cells
-  static const bool no_act = getenv("PHX_NO_ACT_FLAGS") != nullptr;   // A/B aid
-  const int from_tags = (m->act_valid && m->act_in && m->act_cut && !no_act) ? 1 : 0;
-  PHX_HIP(phx_malloc(&fu, (size_t)m->nv));
-  PHX_HIP(phx_malloc(&fp, (size_t)m->nv));
-  if (from_tags) {
-    k_flags_from_tagging<<<dim3((unsigned)phx_div_up(m->nv, 256)), block, 0, m->stream>>>(m->nv, m->act_in, m->act_cut, fu, fp);
-  } else {
-    PHX_HIP(hipMemsetAsync(fu, 0, (size_t)m->nv, m->stream));
-    PHX_HIP(hipMemsetAsync(fp, 0, (size_t)m->nv, m->stream));
-    const dim3 gcells((unsigned)phx_div_up(phx_div_up(m->nc, 4), 256));
-    if (D == 2) k_mark_active<3><<<gcells, block, 0, m->stream>>>(m->nc, m->cells, m->cell_tags, fu, fp);
-    else k_mark_active<4><<<gcells, block, 0, m->stream>>>(m->nc, m->cells, m->cell_tags, fu, fp);
-  }
-  int32_t nu = 0, np = 0;
-  PHX_CHECK(scan_flags_packed(m, fu, fp, sup, &nu, &np, m->nv));
-  s->nu = nu;
-  s->n = (int64_t)nu + np;
-  if (s->n == 0) {
-    PHX_HIP(hipStreamSynchronize(m->stream));
-    PHX_HIP(phx_free(fu)); PHX_HIP(phx_free(fp)); PHX_HIP(phx_free(sup));
-    if (!m->allow_empty) {
-      delete s;
-      phx_set_error("no active DoF: no cell is tagged 1 or 2");
-      return PHX_ERR_VALUE;
-    }
-    // PHX_OPT_ALLOW_EMPTY (slab drivers): a system without rows that still takes part in the collectives
-    int rc = PHX_OK;
-    if (phx_malloc(&s->dof_of_vertex_u, sizeof(int32_t) * (size_t)m->nv) != hipSuccess ||
-        phx_malloc(&s->dof_of_vertex_p, sizeof(int32_t) * (size_t)m->nv) != hipSuccess ||
-        hipMemsetAsync(s->dof_of_vertex_u, 0xff, sizeof(int32_t) * (size_t)m->nv, m->stream) != hipSuccess ||
-        hipMemsetAsync(s->dof_of_vertex_p, 0xff, sizeof(int32_t) * (size_t)m->nv, m->stream) != hipSuccess)
-      rc = PHX_ERR_HIP;
-    if (rc == PHX_OK) rc = phx_system_build_empty(s);
-    if (rc != PHX_OK) { phx_system_destroy(s); return rc; }
-    *out = s;
-    return PHX_OK;
-  }
-  PHX_HIP(phx_malloc(&s->dof_of_vertex_u, sizeof(int32_t) * (size_t)m->nv));
-  PHX_HIP(phx_malloc(&s->dof_of_vertex_p, sizeof(int32_t) * (size_t)m->nv));
-  PHX_HIP(phx_malloc(&s->full_of_active, sizeof(int64_t) * (size_t)s->n));
-  k_finish_numbering_packed<<<dim3((unsigned)phx_div_up(m->nv, 256)), block, 0, m->stream>>>(
-      m->nv, fu, fp, sup, nu, s->dof_of_vertex_u, s->dof_of_vertex_p, s->full_of_active, 0);
-  // temporaries whose last kernel is only enqueued: freed behind the synchronisation in front of finish_*
-  std::vector<void *> later = {fu, fp, sup};
-  // ---- element kernels run over compacted work lists
-  int32_t *l_cut = nullptr, *l_fac = nullptr;
-  int64_t n_cut = 0, n_fac = 0;
-  PHX_CHECK(build_list(m, m->nc, SelCut{m->cell_tags}, &l_cut, &n_cut, &later,
-                       m->sel_cut_valid ? m->sel_counts_cut : nullptr,         // counted by the cell tagging kernel:
-                       m->sel_cut_valid ? m->tag_hist[2] : -1));               // the cut cells ARE the cells tagged 2
-  PHX_CHECK(build_list(m, m->nf, SelGhostFacet{m->facet_tags, m->f2c}, &l_fac, &n_fac, &later,
-                       m->sel_counts_valid ? m->sel_counts[0] : nullptr,     // counted by the facet tagging kernel
-                       m->sel_counts_valid ? m->sel_total[0] : -1));
-  Slots sl;
-  sl.W = W;
-  sl.cols = nullptr; sl.vals = nullptr; sl.overflow = nullptr;
-  PHX_HIP(phx_malloc(&s->rhs, sizeof(double) * (size_t)s->n));
-  PHX_HIP(hipMemsetAsync(s->rhs, 0, sizeof(double) * (size_t)s->n, m->stream));
-  AsmArgs A;
-  A.cells = m->cells; A.x = m->x; A.ctags = m->cell_tags; A.ftags = m->facet_tags;
-  A.c2f = m->c2f; A.f2c = m->f2c; A.du = s->dof_of_vertex_u; A.dp = s->dof_of_vertex_p;
-  A.phi = dphi; A.f = df; A.ud = dud; A.gamma = pen_coef; A.sigma = stab_coef;
-  A.rhs = s->rhs; A.nv = (int32_t)m->nv;
-  uint8_t *touched = nullptr;
-  int32_t *stored_rows = nullptr;   // structured systems without a CSR copy: active indices of the rows that are stored
-  int64_t n_stored_rows = 0;
-  const bool structured = m->is_box && !m->is_submesh && m->structured != 0;
-  static const bool cut_scatter = getenv("PHX_CUT_SCATTER") && atoi(getenv("PHX_CUT_SCATTER")) != 0;   // A/B aid
-  // box slots (BoxCodes) for the stored rows of structured systems; PHX_BOX_SLOTS=0: the hashed slots (A/B aid)
-  const char *bs_env = getenv("PHX_BOX_SLOTS");
-  const bool box_slots = structured && !m->export_csr && !m->deterministic && !cut_scatter && !(bs_env && atoi(bs_env) == 0);
-  const BoxCodes *codes = nullptr;
-  if (box_slots) {
-    codes = box_codes(m->device, D);
-    PHX_REQUIRE(codes != nullptr && codes->ncode <= PHX_BOX_MAXCODE, PHX_ERR_HIP, "box slot code table");
-    sl.ncode = codes->ncode;
-    sl.bn0 = (int32_t)(m->box_n[0] + 1);
-    sl.bn1 = D == 3 ? (int32_t)(m->box_n[1] + 1) : 0x7fffffff;
-  }
-  int64_t slot_rows = s->n;
-  if (m->is_box && !m->is_submesh) {
-    // rows of vertices no scattering kernel reaches are written dense and sorted by the gather kernel
-    PHX_CHECK(phx_collect_entities(m));
-    PHX_HIP(phx_malloc(&touched, (size_t)m->nv));
-    PHX_HIP(hipMemsetAsync(touched, 0, (size_t)m->nv, m->stream));
-    if (!box_slots) {   // box slots place every entry at its code: no clean rows
-      PHX_HIP(phx_malloc(&sl.clean, (size_t)s->n));
-      PHX_HIP(hipMemsetAsync(sl.clean, 0, (size_t)s->n, m->stream));
-    }
-    constexpr int TB = 256;
-    if (n_cut > 0) {
-      const dim3 g((unsigned)phx_div_up(n_cut, TB));
-      if (D == 2) k_mark_cells<3><<<g, dim3(TB), 0, m->stream>>>(n_cut, l_cut, m->cells, touched);
-      else k_mark_cells<4><<<g, dim3(TB), 0, m->stream>>>(n_cut, l_cut, m->cells, touched);
-    }
-    if (n_fac > 0) {
-      const dim3 g((unsigned)phx_div_up(n_fac, TB));
-      if (D == 2) k_mark_facet_cells<3><<<g, dim3(TB), 0, m->stream>>>(n_fac, l_fac, m->f2c, m->cells, touched);
-      else k_mark_facet_cells<4><<<g, dim3(TB), 0, m->stream>>>(n_fac, l_fac, m->f2c, m->cells, touched);
-    }
-    if (m->ent_count[0] > 0) {
-      const dim3 g((unsigned)phx_div_up(m->ent_count[0], TB));
-      if (D == 2) k_mark_entity_cells<3><<<g, dim3(TB), 0, m->stream>>>(m->ent_count[0], m->ent_buf[0], m->cells, touched);
-      else k_mark_entity_cells<4><<<g, dim3(TB), 0, m->stream>>>(m->ent_count[0], m->ent_buf[0], m->cells, touched);
-    }
-    A.touched = touched;
-  }
-  if (structured) {
-    // C0 rows (translation-invariant interior rows) are applied from a stencil: no slots, no stored entries
-    s->structured = true;
-    s->u_unscaled = true;
-    PHX_HIP(phx_malloc(&s->c0, (size_t)s->n));
-    PHX_HIP(phx_malloc(&s->diag, sizeof(double) * (size_t)s->n));
-    PHX_HIP(phx_malloc(&s->stencil, sizeof(double) * 8));
-    PHX_HIP(hipMemsetAsync(s->c0, 0, (size_t)s->n, m->stream));
-    PHX_HIP(hipMemsetAsync(s->diag, 0, sizeof(double) * (size_t)s->n, m->stream));
-    PHX_HIP(hipMemsetAsync(s->stencil, 0, sizeof(double) * 8, m->stream));
-    const BoxDims bd{{m->box_n[0], m->box_n[1], m->box_n[2]}, {m->box_h[0], m->box_h[1], m->box_h[2]}};
-    const dim3 g((unsigned)phx_div_up(m->nv, 256));
-    if (D == 2) k_mark_c0<2><<<g, block, 0, m->stream>>>(m->nv, bd, s->dof_of_vertex_u, m->cell_tags, touched, s->c0);
-    else k_mark_c0<3><<<g, block, 0, m->stream>>>(m->nv, bd, s->dof_of_vertex_u, m->cell_tags, touched, s->c0);
-    if (D == 2) k_box_stencil<2><<<1, 1, 0, m->stream>>>(bd, s->stencil);
-    else k_box_stencil<3><<<1, 1, 0, m->stream>>>(bd, s->stencil);
-    A.c0 = s->c0; A.diag = s->diag; A.stencil = s->stencil;
-    A.store_c0 = m->export_csr ? 1 : 0;
-    if (!m->export_csr) {
-      // only the stored rows get slots: offsets from the rank among the non-C0 rows
-      int32_t *rank = nullptr, nstored_before_last = 0;
-      uint8_t *notc0 = nullptr;
-      PHX_HIP(phx_malloc(&rank, sizeof(int32_t) * (size_t)s->n));
-      PHX_HIP(phx_malloc(&notc0, (size_t)s->n));
-      k_not_flags<<<dim3((unsigned)phx_div_up(s->n, 256)), block, 0, m->stream>>>(s->n, s->c0, notc0);
-      int32_t nstored = 0;
-      PHX_CHECK(scan_flags(m, notc0, rank, s->n, &nstored));
-      (void)nstored_before_last;
-      slot_rows = nstored;
-      int64_t *off = nullptr;
-      uint8_t *wl = nullptr;
-      PHX_HIP(phx_malloc(&off, sizeof(int64_t) * (size_t)s->n));
-      PHX_HIP(phx_malloc(&wl, (size_t)s->n));
-      int lg = 0;
-      while ((1 << lg) < W) ++lg;
-      k_slot_offsets<<<dim3((unsigned)phx_div_up(s->n, 256)), block, 0, m->stream>>>(s->n, box_slots ? sl.ncode : W, lg,
-                                                                                   s->c0, rank, off, wl);
-      sl.off = off; sl.wlog = wl;
-      if (nstored > 0) {   // the stored rows as a list: work list of the row kernel (mode 2)
-        PHX_HIP(phx_malloc(&stored_rows, sizeof(int32_t) * (size_t)nstored));
-        k_flagged_list<<<dim3((unsigned)phx_div_up(s->n, 256)), block, 0, m->stream>>>(s->n, notc0, rank, stored_rows);
-        n_stored_rows = nstored;
-      }
-      later.push_back(rank); later.push_back(notc0);
-    }
-  }
-  // ---- slots (of the stored rows)
-  {
-    const size_t ns = (size_t)std::max<int64_t>(slot_rows, 1) * (box_slots ? sl.ncode : W);
-    PHX_HIP(phx_malloc(&sl.vals, sizeof(double) * ns));
-    PHX_HIP(phx_malloc(&sl.overflow, sizeof(int)));
-    if (box_slots) {   // occupancy and values only: no keys
-      PHX_HIP(phx_malloc(&sl.occ, ns));
-      PHX_HIP(hipMemsetAsync(sl.occ, 0, ns, m->stream));
-    } else {
-      PHX_HIP(phx_malloc(&sl.cols, sizeof(int32_t) * ns));
-      PHX_HIP(hipMemsetAsync(sl.cols, 0xff, sizeof(int32_t) * ns, m->stream));
-    }
-    PHX_HIP(hipMemsetAsync(sl.vals, 0, sizeof(double) * ns, m->stream));
-    PHX_HIP(hipMemsetAsync(sl.overflow, 0, sizeof(int), m->stream));
-  }
-  // PHX_OPT_DETERMINISTIC on an unstructured mesh or a sub-mesh: the element kernels run twice (exponent pass, exact
-  // accumulation pass; Slots), so matrix and right-hand side are the same bits on every run.  (Kuhn boxes gather most of
-  // their rows in closed form and keep plain atomics for the rest.)
-  bool det = false;
-  const int64_t det_slots = (int64_t)std::max<int64_t>(slot_rows, 1) * W;
-  if (!m->is_box) PHX_CHECK(det_alloc(m, sl, det_slots, s->n, &det));
-  for (int pass = det ? 1 : 0; pass <= (det ? 2 : 0); ++pass) {
-  sl.pass = pass;
-  A.slots = sl;
-  {
-    if (m->is_box) {
-      const BoxDims bd{{m->box_n[0], m->box_n[1], m->box_n[2]}, {m->box_h[0], m->box_h[1], m->box_h[2]}};
-      const dim3 g((unsigned)phx_div_up(m->nv, 256));
-      const int mode = stored_rows ? 1 : 0;
-      if (D == 2) k_assemble_rows_box<2><<<g, block, 0, m->stream>>>(m->nv, bd, A, mode, nullptr, nullptr, s->nu);
-      else k_assemble_rows_box<3><<<g, block, 0, m->stream>>>(m->nv, bd, A, mode, nullptr, nullptr, s->nu);
-      if (stored_rows && n_stored_rows > 0) {
-        const dim3 g2((unsigned)phx_div_up(n_stored_rows, 256));
-        if (D == 2) k_assemble_rows_box<2><<<g2, block, 0, m->stream>>>(n_stored_rows, bd, A, 2, stored_rows, s->full_of_active, s->nu);
-        else k_assemble_rows_box<3><<<g2, block, 0, m->stream>>>(n_stored_rows, bd, A, 2, stored_rows, s->full_of_active, s->nu);
-      }
-    } else {
-      const dim3 g((unsigned)phx_div_up(m->nv, ROW_THREADS)), b(ROW_THREADS);
-      if (D == 2) k_assemble_rows<2><<<g, b, 0, m->stream>>>(m->nv, m->v2c_ptr, m->v2c_idx, A);
-      else k_assemble_rows<3><<<g, b, 0, m->stream>>>(m->nv, m->v2c_ptr, m->v2c_idx, A);
-    }
-  }
-  if (n_cut > 0 && m->is_box && !cut_scatter) {
-    // Kuhn box: the cut-cell terms as row gathers (no atomics)
-    const BoxDims bd{{m->box_n[0], m->box_n[1], m->box_n[2]}, {m->box_h[0], m->box_h[1], m->box_h[2]}};
-    const int64_t npd = s->n - s->nu;
-    const dim3 g((unsigned)phx_div_up(std::max<int64_t>(npd, 1), 256));
-    if (D == 2) k_assemble_cut_rows_box<2><<<g, block, 0, m->stream>>>(npd, s->full_of_active + s->nu, bd, A);
-    else k_assemble_cut_rows_box<3><<<g, block, 0, m->stream>>>(npd, s->full_of_active + s->nu, bd, A);
-  } else if (n_cut > 0) {
-    // 64 lanes per cut cell.  Measured at 256^3 (1.1e6 cut cells): 64 lanes per cell 2.1 ms, 8 lanes (one
-    // tensor row each) 2.6 ms, one lane per cell 2.7 ms -- the dependent hash probes of a lane serialise;
-    // the ghost-penalty facets behave the other way round (one lane per facet: 2.8 -> 1.5 ms).
-    PHX_REQUIRE_GRID(n_cut * 64, "cut-cell assembly");
-    const dim3 g((unsigned)phx_div_up(n_cut * 64, 256));
-    if (D == 2) k_assemble_cut<2><<<g, block, 0, m->stream>>>(n_cut, l_cut, A);
-    else k_assemble_cut<3><<<g, block, 0, m->stream>>>(n_cut, l_cut, A);
-  }
-  PHX_HIP(hipGetLastError());
-  if (m->is_submesh) {
-    // main.py:74: ds = every exterior facet of the sub-mesh
-    if (m->nbf > 0) {
-      const dim3 g((unsigned)phx_div_up(m->nbf * 16, 256));
-      if (D == 2) k_assemble_ds<2><<<g, block, 0, m->stream>>>(m->nbf, nullptr, m->bfacets, A);
-      else k_assemble_ds<3><<<g, block, 0, m->stream>>>(m->nbf, nullptr, m->bfacets, A);
-    }
-  } else {
-    PHX_CHECK(phx_collect_entities(m));  // main.py:65: ds = ds_bdy(100)
-    if (m->ent_count[0] > 0) {
-      const dim3 g((unsigned)phx_div_up(m->ent_count[0] * 16, 256));
-      if (D == 2) k_assemble_ds<2><<<g, block, 0, m->stream>>>(m->ent_count[0], m->ent_buf[0], nullptr, A);
-      else k_assemble_ds<3><<<g, block, 0, m->stream>>>(m->ent_count[0], m->ent_buf[0], nullptr, A);
-    }
-  }
-  PHX_HIP(hipGetLastError());
-  if (n_fac > 0) {
-    // (Per-class macro-element tables for generated boxes -- vertices as anchor + class offsets, the tensor w Jd Jd^T from
-    // a table, no f2c / cells / c2f / coordinate loads and no simplex geometry per facet -- were measured at 1.46 ms against
-    // 1.49 ms for this kernel at 256^3: the 5e7 hashed f64 atomics are the whole cost.  Not kept.)
-    const dim3 g((unsigned)phx_div_up(n_fac, 256));
-    if (D == 2) k_assemble_facets<2><<<g, block, 0, m->stream>>>(n_fac, l_fac, A);
-    else k_assemble_facets<3><<<g, block, 0, m->stream>>>(n_fac, l_fac, A);
-  }
-  PHX_HIP(hipGetLastError());
-  }   // passes
-  PHX_CHECK(det_finish(m, sl, det_slots, s->n, s->rhs));
-  PHX_HIP(hipStreamSynchronize(m->stream));
-  for (void *q : later) PHX_HIP(phx_free(q));
-  PHX_HIP(phx_free(l_cut)); PHX_HIP(phx_free(l_fac));
-  if (touched) PHX_HIP(phx_free(touched));
-  if (stored_rows) PHX_HIP(phx_free(stored_rows));
-  {
-    const int rc = structured ? finish_structured(s, sl, (int32_t)m->nv, m->export_csr != 0)
-                              : phx_finish_system(s, sl, (int32_t)m->nv);
-    if (rc != PHX_OK) { phx_system_destroy(s); return rc; }
-  }
-  *out = s;
-  return PHX_OK;
-}
-
-static int build_v2c(phx_mesh *m) {
-  if (m->v2c_ptr) return PHX_OK;
-  const int nvpc = m->ci.nvpc;
-  const int64_t tot = m->nc * nvpc;
-  unsigned long long *cnt = nullptr;
-  PHX_HIP(phx_malloc(&cnt, sizeof(unsigned long long) * (size_t)(m->nv + 1)));
-  PHX_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * (size_t)(m->nv + 1), m->stream));
-  PHX_HIP(phx_malloc(&m->v2c_ptr, sizeof(int64_t) * (size_t)(m->nv + 1)));
-  PHX_HIP(phx_malloc(&m->v2c_idx, sizeof(int32_t) * (size_t)tot));
-  const dim3 block(256), grid((unsigned)phx_div_up(tot, 256));
-  k_v2c_count<<<grid, block, 0, m->stream>>>(m->nc, nvpc, m->cells, cnt);
-  PHX_CHECK(exclusive_sum<int64_t>(m, (const int64_t *)cnt, m->v2c_ptr, m->nv + 1));
-  PHX_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * (size_t)(m->nv + 1), m->stream));
-  k_v2c_fill<<<grid, block, 0, m->stream>>>(m->nc, nvpc, m->cells, m->v2c_ptr, cnt, m->v2c_idx);
-  PHX_HIP(hipGetLastError());
-  PHX_HIP(hipStreamSynchronize(m->stream));
-  PHX_HIP(phx_free(cnt));
-  return PHX_OK;
-}
-
-static int to_device(phx_mesh *m, const double *p, int loc, int64_t n, const double **dev,
-                     double **owned) {
-  *owned = nullptr;
-  PHX_REQUIRE(p != nullptr, PHX_ERR_VALUE, "NULL nodal array");
-  if (loc == PHX_DEVICE) { *dev = p; return PHX_OK; }
-  PHX_HIP(phx_malloc(owned, sizeof(double) * (size_t)n));
-  PHX_HIP(hipMemcpyAsync(*owned, p, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, m->stream));
-  *dev = *owned;
-  return PHX_OK;
-}
-
 // ---------------------------------------------------------------------------------------------
-// Host scaffold of the secondary assemblers (strong Dirichlet, Neumann / Robin, interface elasticity, Q1 weak
-// Dirichlet): each one reads numbering -> work lists -> slots -> launches -> finish; what it allocates on the way is
+// Host scaffold of the assemblers (weak Dirichlet P1 / P2 / Q1, strong Dirichlet, Neumann / Robin, interface
+// elasticity): each one reads numbering -> work lists -> slots -> launches -> finish; what it allocates on the way is
 // owned by the two objects below, so every return -- PHX_HIP / PHX_CHECK / PHX_REQUIRE included -- gives it back.
 // ---------------------------------------------------------------------------------------------
 // Device temporaries of one call: the stream is synchronised once and the blocks are freed when the list goes out of
@@ -1933,38 +1608,51 @@ struct DevTemps {
   void adopt(T *p) { if (p) blocks.push_back((void *)p); }   // a block some helper allocated (build_list)
 };
 
-// The system under construction and its slot table: destroyed unless finish() hands the system to the caller
-// (phx_finish_system consumes the slots on the way; free_slots leaves null pointers behind, so freeing twice is safe).
+// The system under construction and its slot table: destroyed unless a finish hands the system to the caller
+// (the finishing calls consume the slots on the way; free_slots leaves null pointers behind, so freeing twice is safe).
 struct SystemBuild {
   phx_system *s;
   Slots sl;
+  // device tables the finishing call still reads (structured P2: the lattice flags).  Freed with this object: behind
+  // the finishing call, which returns with the stream drained, or behind the synchronisation of a failed build.
+  std::vector<void *> held;
   SystemBuild(phx_mesh *m, int64_t nent, int64_t nfull, int W) : s(new phx_system()) {
     s->mesh = m; s->device = m->device; s->nent = nent; s->nfull = nfull; s->slot_cap = W;
     sl.W = W;
-    sl.cols = nullptr; sl.vals = nullptr; sl.overflow = nullptr;
   }
   SystemBuild(const SystemBuild &) = delete;
   SystemBuild &operator=(const SystemBuild &) = delete;
   ~SystemBuild() {
-    if (!s) return;
-    (void)hipStreamSynchronize(s->mesh->stream);
-    (void)free_slots(sl);
-    phx_system_destroy(s);
+    if (s) {
+      (void)hipStreamSynchronize(s->mesh->stream);
+      (void)free_slots(sl);
+      phx_system_destroy(s);
+    }
+    for (void *p : held) (void)phx_free(p);
   }
-  // overflow check, compaction, solver formats; the column keys are full DoF indices below nkey per field
-  int finish(int32_t nkey, phx_system **out) {
-    PHX_CHECK(phx_finish_system(s, sl, nkey));
+  // fin(s, sl) turns the slots into the solver formats (finish_structured, the structured P2 build, the empty system)
+  template <typename Finish>
+  int finish_with(Finish fin, phx_system **out) {
+    PHX_CHECK(fin(s, sl));
     *out = s;
     s = nullptr;
     return PHX_OK;
   }
+  // overflow check, compaction, solver formats; the column keys are full DoF indices below nkey per field
+  int finish(int32_t nkey, phx_system **out) {
+    return finish_with([nkey](phx_system *s, Slots &sl) { return phx_finish_system(s, sl, nkey); }, out);
+  }
 };
 
+// nodal input of n doubles where the kernels can read it: a device array as it is, a host array as a staged copy
 static int to_device(phx_mesh *m, const double *p, int loc, int64_t n, const double **dev, DevTemps &staged) {
-  double *owned = nullptr;
-  const int rc = to_device(m, p, loc, n, dev, &owned);
-  staged.adopt(owned);
-  return rc;
+  PHX_REQUIRE(p != nullptr, PHX_ERR_VALUE, "NULL nodal array");
+  if (loc == PHX_DEVICE) { *dev = p; return PHX_OK; }
+  double *copy = nullptr;
+  PHX_HIP(staged.alloc(&copy, sizeof(double) * (size_t)n));
+  PHX_HIP(hipMemcpyAsync(copy, p, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, m->stream));
+  *dev = copy;
+  return PHX_OK;
 }
 
 // slot table of nslots (col, val) pairs, cleared, and the overflow flag
@@ -2038,6 +1726,302 @@ static int retry_capacity(std::initializer_list<int> capacities, Run run) {
   return rc;
 }
 
+// ---------------------------------------------------------------------------------------------
+// P1 x P1 weak Dirichlet on triangles and tetrahedra: the steps of assemble_with_capacity
+// ---------------------------------------------------------------------------------------------
+// what one step hands to the next; the device blocks belong to the caller's DevTemps
+struct P1Work {
+  int32_t *l_cut = nullptr, *l_fac = nullptr;   // cut cells, ghost-penalty facets
+  int64_t n_cut = 0, n_fac = 0;
+  uint8_t *touched = nullptr;                   // Kuhn boxes: vertices a scattering kernel reaches
+  int32_t *stored_rows = nullptr;   // structured systems without a CSR copy: active indices of the rows that are stored
+  int64_t n_stored_rows = 0;
+  int64_t slot_rows = 0;                        // rows that own slots
+  bool box_slots = false;
+};
+
+// Active numbering.  Leaves nu and n on the system and, unless n == 0 (which passes only with PHX_OPT_ALLOW_EMPTY), the
+// DoF maps.
+static int p1_number(phx_mesh *m, phx_system *s, DevTemps &tmp) {
+  const dim3 block(256);
+  uint8_t *fu = nullptr, *fp = nullptr;
+  unsigned long long *sup = nullptr;
+  PHX_HIP(tmp.alloc(&sup, sizeof(unsigned long long) * (size_t)m->nv));
+  PHX_HIP(tmp.alloc(&fu, (size_t)m->nv));
+  PHX_HIP(tmp.alloc(&fp, (size_t)m->nv));
+  // the single-layer tagging pass left the vertex flags behind (inside cells; cells that stayed cut): no walk over the cells
+  if (m->act_valid && m->act_in && m->act_cut) {
+    k_flags_from_tagging<<<dim3((unsigned)phx_div_up(m->nv, 256)), block, 0, m->stream>>>(m->nv, m->act_in, m->act_cut, fu, fp);
+  } else {
+    PHX_HIP(hipMemsetAsync(fu, 0, (size_t)m->nv, m->stream));
+    PHX_HIP(hipMemsetAsync(fp, 0, (size_t)m->nv, m->stream));
+    const dim3 gcells((unsigned)phx_div_up(phx_div_up(m->nc, 4), 256));
+    if (m->gdim == 2) k_mark_active<3><<<gcells, block, 0, m->stream>>>(m->nc, m->cells, m->cell_tags, fu, fp);
+    else k_mark_active<4><<<gcells, block, 0, m->stream>>>(m->nc, m->cells, m->cell_tags, fu, fp);
+  }
+  int32_t nu = 0, np = 0;
+  PHX_CHECK(scan_flags_packed(m, fu, fp, sup, &nu, &np, m->nv));
+  s->nu = nu;
+  s->n = (int64_t)nu + np;
+  PHX_REQUIRE(s->n > 0 || m->allow_empty, PHX_ERR_VALUE, "no active DoF: no cell is tagged 1 or 2");
+  if (s->n == 0) return PHX_OK;
+  PHX_HIP(phx_malloc(&s->dof_of_vertex_u, sizeof(int32_t) * (size_t)m->nv));
+  PHX_HIP(phx_malloc(&s->dof_of_vertex_p, sizeof(int32_t) * (size_t)m->nv));
+  PHX_HIP(phx_malloc(&s->full_of_active, sizeof(int64_t) * (size_t)s->n));
+  k_finish_numbering_packed<<<dim3((unsigned)phx_div_up(m->nv, 256)), block, 0, m->stream>>>(
+      m->nv, fu, fp, sup, nu, s->dof_of_vertex_u, s->dof_of_vertex_p, s->full_of_active, 0);
+  return PHX_OK;
+}
+
+// PHX_OPT_ALLOW_EMPTY (slab drivers): a system without rows that still takes part in the collectives
+static int p1_finish_empty(phx_system *s, Slots &) {
+  phx_mesh *m = s->mesh;
+  PHX_HIP(phx_malloc(&s->dof_of_vertex_u, sizeof(int32_t) * (size_t)m->nv));
+  PHX_HIP(phx_malloc(&s->dof_of_vertex_p, sizeof(int32_t) * (size_t)m->nv));
+  PHX_HIP(hipMemsetAsync(s->dof_of_vertex_u, 0xff, sizeof(int32_t) * (size_t)m->nv, m->stream));
+  PHX_HIP(hipMemsetAsync(s->dof_of_vertex_p, 0xff, sizeof(int32_t) * (size_t)m->nv, m->stream));
+  return phx_system_build_empty(s);
+}
+
+// Work lists of the element kernels.  Where the tagging kernels counted the selection, the total is known on the host
+// and the fill pass is only enqueued: its scratch joins the temporaries (phx_select_indices).
+static int p1_work_lists(phx_mesh *m, DevTemps &tmp, P1Work &w) {
+  PHX_CHECK(phx_select_indices(m->stream, m->nc, SelCut{m->cell_tags}, &w.l_cut, &w.n_cut, &tmp.blocks,
+                               m->sel_cut_valid ? m->sel_counts_cut : nullptr,      // counted by the cell tagging kernel:
+                               m->sel_cut_valid ? m->tag_hist[2] : -1));            // the cut cells ARE the cells tagged 2
+  tmp.adopt(w.l_cut);
+  PHX_CHECK(phx_select_indices(m->stream, m->nf, SelGhostFacet{m->facet_tags, m->f2c}, &w.l_fac, &w.n_fac, &tmp.blocks,
+                               m->sel_counts_valid ? m->sel_counts[0] : nullptr,    // counted by the facet tagging kernel
+                               m->sel_counts_valid ? m->sel_total[0] : -1));
+  tmp.adopt(w.l_fac);
+  return PHX_OK;
+}
+
+// Kuhn boxes: rows of vertices no scattering kernel reaches are written dense and sorted by the gather kernel
+static int p1_mark_touched(phx_mesh *m, phx_system *s, Slots &sl, DevTemps &tmp, P1Work &w) {
+  const int D = m->gdim;
+  PHX_CHECK(phx_collect_entities(m));
+  PHX_HIP(tmp.alloc(&w.touched, (size_t)m->nv));
+  PHX_HIP(hipMemsetAsync(w.touched, 0, (size_t)m->nv, m->stream));
+  if (!w.box_slots) {   // box slots place every entry at its code: no clean rows
+    PHX_HIP(phx_malloc(&sl.clean, (size_t)s->n));
+    PHX_HIP(hipMemsetAsync(sl.clean, 0, (size_t)s->n, m->stream));
+  }
+  constexpr int TB = 256;
+  if (w.n_cut > 0) {
+    const dim3 g((unsigned)phx_div_up(w.n_cut, TB));
+    if (D == 2) k_mark_cells<3><<<g, dim3(TB), 0, m->stream>>>(w.n_cut, w.l_cut, m->cells, w.touched);
+    else k_mark_cells<4><<<g, dim3(TB), 0, m->stream>>>(w.n_cut, w.l_cut, m->cells, w.touched);
+  }
+  if (w.n_fac > 0) {
+    const dim3 g((unsigned)phx_div_up(w.n_fac, TB));
+    if (D == 2) k_mark_facet_cells<3><<<g, dim3(TB), 0, m->stream>>>(w.n_fac, w.l_fac, m->f2c, m->cells, w.touched);
+    else k_mark_facet_cells<4><<<g, dim3(TB), 0, m->stream>>>(w.n_fac, w.l_fac, m->f2c, m->cells, w.touched);
+  }
+  if (m->ent_count[0] > 0) {
+    const dim3 g((unsigned)phx_div_up(m->ent_count[0], TB));
+    if (D == 2) k_mark_entity_cells<3><<<g, dim3(TB), 0, m->stream>>>(m->ent_count[0], m->ent_buf[0], m->cells, w.touched);
+    else k_mark_entity_cells<4><<<g, dim3(TB), 0, m->stream>>>(m->ent_count[0], m->ent_buf[0], m->cells, w.touched);
+  }
+  return PHX_OK;
+}
+
+// Structured systems: C0 rows (translation-invariant interior rows) are applied from a stencil: no slots, no stored
+// entries.  Without a CSR copy only the stored rows get slots, at offsets from their rank among the non-C0 rows.
+static int p1_stored_row_layout(phx_mesh *m, phx_system *s, Slots &sl, DevTemps &tmp, const BoxDims &bd, P1Work &w) {
+  const int D = m->gdim;
+  const dim3 block(256), g((unsigned)phx_div_up(m->nv, 256)), gn((unsigned)phx_div_up(s->n, 256));
+  s->structured = true;
+  s->u_unscaled = true;
+  PHX_HIP(phx_malloc(&s->c0, (size_t)s->n));
+  PHX_HIP(phx_malloc(&s->diag, sizeof(double) * (size_t)s->n));
+  PHX_HIP(phx_malloc(&s->stencil, sizeof(double) * 8));
+  PHX_HIP(hipMemsetAsync(s->c0, 0, (size_t)s->n, m->stream));
+  PHX_HIP(hipMemsetAsync(s->diag, 0, sizeof(double) * (size_t)s->n, m->stream));
+  PHX_HIP(hipMemsetAsync(s->stencil, 0, sizeof(double) * 8, m->stream));
+  if (D == 2) k_mark_c0<2><<<g, block, 0, m->stream>>>(m->nv, bd, s->dof_of_vertex_u, m->cell_tags, w.touched, s->c0);
+  else k_mark_c0<3><<<g, block, 0, m->stream>>>(m->nv, bd, s->dof_of_vertex_u, m->cell_tags, w.touched, s->c0);
+  if (D == 2) k_box_stencil<2><<<1, 1, 0, m->stream>>>(bd, s->stencil);
+  else k_box_stencil<3><<<1, 1, 0, m->stream>>>(bd, s->stencil);
+  if (m->export_csr) return PHX_OK;   // then every row, C0 included, sits in the slots
+  int32_t *rank = nullptr;
+  uint8_t *notc0 = nullptr;
+  PHX_HIP(tmp.alloc(&rank, sizeof(int32_t) * (size_t)s->n));
+  PHX_HIP(tmp.alloc(&notc0, (size_t)s->n));
+  k_not_flags<<<gn, block, 0, m->stream>>>(s->n, s->c0, notc0);
+  int32_t nstored = 0;
+  PHX_CHECK(scan_flags(m, notc0, rank, s->n, &nstored));
+  w.slot_rows = nstored;
+  int64_t *off = nullptr;
+  uint8_t *wl = nullptr;
+  PHX_HIP(phx_malloc(&off, sizeof(int64_t) * (size_t)s->n));
+  sl.off = off;
+  PHX_HIP(phx_malloc(&wl, (size_t)s->n));
+  sl.wlog = wl;
+  int lg = 0;
+  while ((1 << lg) < sl.W) ++lg;
+  k_slot_offsets<<<gn, block, 0, m->stream>>>(s->n, w.box_slots ? sl.ncode : sl.W, lg, s->c0, rank, off, wl);
+  if (nstored > 0) {   // the stored rows as a list: work list of the row kernel (mode 2)
+    PHX_HIP(tmp.alloc(&w.stored_rows, sizeof(int32_t) * (size_t)nstored));
+    k_flagged_list<<<gn, block, 0, m->stream>>>(s->n, notc0, rank, w.stored_rows);
+    w.n_stored_rows = nstored;
+  }
+  return PHX_OK;
+}
+
+// Slots of the rows that own some: box-code slots (occupancy and values only: no keys) or hashed (col, val) pairs
+static int p1_slots_alloc(phx_mesh *m, Slots &sl, const P1Work &w) {
+  const size_t ns = (size_t)std::max<int64_t>(w.slot_rows, 1) * (w.box_slots ? sl.ncode : sl.W);
+  if (!w.box_slots) return slots_alloc(m, (int64_t)ns, sl.W, &sl);
+  PHX_HIP(phx_malloc(&sl.vals, sizeof(double) * ns));
+  PHX_HIP(phx_malloc(&sl.overflow, sizeof(int)));
+  PHX_HIP(phx_malloc(&sl.occ, ns));
+  PHX_HIP(hipMemsetAsync(sl.occ, 0, ns, m->stream));
+  PHX_HIP(hipMemsetAsync(sl.vals, 0, sizeof(double) * ns, m->stream));
+  PHX_HIP(hipMemsetAsync(sl.overflow, 0, sizeof(int), m->stream));
+  return PHX_OK;
+}
+
+// The element kernels of one pass, in stream order: vertex rows, cut cells, boundary term, ghost penalty
+static int p1_launch_pass(phx_mesh *m, phx_system *s, const BoxDims &bd, const AsmArgs &A, const P1Work &w) {
+  const int D = m->gdim;
+  const dim3 block(256);
+  if (m->is_box) {
+    const dim3 g((unsigned)phx_div_up(m->nv, 256));
+    const int mode = w.stored_rows ? 1 : 0;
+    if (D == 2) k_assemble_rows_box<2><<<g, block, 0, m->stream>>>(m->nv, bd, A, mode, nullptr, nullptr, s->nu);
+    else k_assemble_rows_box<3><<<g, block, 0, m->stream>>>(m->nv, bd, A, mode, nullptr, nullptr, s->nu);
+    if (w.stored_rows && w.n_stored_rows > 0) {
+      const dim3 g2((unsigned)phx_div_up(w.n_stored_rows, 256));
+      if (D == 2) k_assemble_rows_box<2><<<g2, block, 0, m->stream>>>(w.n_stored_rows, bd, A, 2, w.stored_rows, s->full_of_active, s->nu);
+      else k_assemble_rows_box<3><<<g2, block, 0, m->stream>>>(w.n_stored_rows, bd, A, 2, w.stored_rows, s->full_of_active, s->nu);
+    }
+  } else {
+    const dim3 g((unsigned)phx_div_up(m->nv, ROW_THREADS)), b(ROW_THREADS);
+    if (D == 2) k_assemble_rows<2><<<g, b, 0, m->stream>>>(m->nv, m->v2c_ptr, m->v2c_idx, A);
+    else k_assemble_rows<3><<<g, b, 0, m->stream>>>(m->nv, m->v2c_ptr, m->v2c_idx, A);
+  }
+  if (w.n_cut > 0 && m->is_box) {
+    // Kuhn box: the cut-cell terms as row gathers (no atomics)
+    const int64_t npd = s->n - s->nu;
+    const dim3 g((unsigned)phx_div_up(std::max<int64_t>(npd, 1), 256));
+    if (D == 2) k_assemble_cut_rows_box<2><<<g, block, 0, m->stream>>>(npd, s->full_of_active + s->nu, bd, A);
+    else k_assemble_cut_rows_box<3><<<g, block, 0, m->stream>>>(npd, s->full_of_active + s->nu, bd, A);
+  } else if (w.n_cut > 0) {
+    // 64 lanes per cut cell.  Measured at 256^3 (1.1e6 cut cells): 64 lanes per cell 2.1 ms, 8 lanes (one
+    // tensor row each) 2.6 ms, one lane per cell 2.7 ms -- the dependent hash probes of a lane serialise;
+    // the ghost-penalty facets behave the other way round (one lane per facet: 2.8 -> 1.5 ms).
+    PHX_REQUIRE_GRID(w.n_cut * 64, "cut-cell assembly");
+    const dim3 g((unsigned)phx_div_up(w.n_cut * 64, 256));
+    if (D == 2) k_assemble_cut<2><<<g, block, 0, m->stream>>>(w.n_cut, w.l_cut, A);
+    else k_assemble_cut<3><<<g, block, 0, m->stream>>>(w.n_cut, w.l_cut, A);
+  }
+  PHX_HIP(hipGetLastError());
+  DsEntities ds;   // main.py:65: ds = ds_bdy(100); main.py:74: every exterior facet of the sub-mesh
+  PHX_CHECK(ds_entities(m, &ds));
+  if (ds.n > 0) {
+    const dim3 g((unsigned)phx_div_up(ds.n * 16, 256));
+    if (D == 2) k_assemble_ds<2><<<g, block, 0, m->stream>>>(ds.n, ds.packed, ds.pairs, A);
+    else k_assemble_ds<3><<<g, block, 0, m->stream>>>(ds.n, ds.packed, ds.pairs, A);
+  }
+  PHX_HIP(hipGetLastError());
+  if (w.n_fac > 0) {
+    // (Per-class macro-element tables for generated boxes -- vertices as anchor + class offsets, the tensor w Jd Jd^T from
+    // a table, no f2c / cells / c2f / coordinate loads and no simplex geometry per facet -- were measured at 1.46 ms against
+    // 1.49 ms for this kernel at 256^3: the 5e7 hashed f64 atomics are the whole cost.  Not kept.)
+    const dim3 g((unsigned)phx_div_up(w.n_fac, 256));
+    if (D == 2) k_assemble_facets<2><<<g, block, 0, m->stream>>>(w.n_fac, w.l_fac, A);
+    else k_assemble_facets<3><<<g, block, 0, m->stream>>>(w.n_fac, w.l_fac, A);
+  }
+  PHX_HIP(hipGetLastError());
+  return PHX_OK;
+}
+
+// Everything between the numbering and the finish: matrix into the slots, right-hand side onto the system
+static int p1_fill_slots(phx_mesh *m, phx_system *s, Slots &sl, DevTemps &tmp, bool structured, AsmArgs &A) {
+  P1Work w;
+  PHX_CHECK(p1_work_lists(m, tmp, w));
+  PHX_CHECK(rhs_alloc(m, s));
+  A.du = s->dof_of_vertex_u; A.dp = s->dof_of_vertex_p; A.rhs = s->rhs;
+  // box slots (BoxCodes) for the stored rows of structured systems; PHX_BOX_SLOTS=0: the hashed slots (A/B aid)
+  const char *bs_env = getenv("PHX_BOX_SLOTS");
+  w.box_slots = structured && !m->export_csr && !m->deterministic && !(bs_env && atoi(bs_env) == 0);
+  if (w.box_slots) {
+    const BoxCodes *codes = box_codes(m->device, m->gdim);
+    PHX_REQUIRE(codes != nullptr && codes->ncode <= PHX_BOX_MAXCODE, PHX_ERR_HIP, "box slot code table");
+    sl.ncode = codes->ncode;
+    sl.bn0 = (int32_t)(m->box_n[0] + 1);
+    sl.bn1 = m->gdim == 3 ? (int32_t)(m->box_n[1] + 1) : 0x7fffffff;
+  }
+  const BoxDims bd{{m->box_n[0], m->box_n[1], m->box_n[2]}, {m->box_h[0], m->box_h[1], m->box_h[2]}};
+  w.slot_rows = s->n;
+  if (m->is_box && !m->is_submesh) {
+    PHX_CHECK(p1_mark_touched(m, s, sl, tmp, w));
+    A.touched = w.touched;
+  }
+  if (structured) {
+    PHX_CHECK(p1_stored_row_layout(m, s, sl, tmp, bd, w));
+    A.c0 = s->c0; A.diag = s->diag; A.stencil = s->stencil;
+    A.store_c0 = m->export_csr ? 1 : 0;
+  }
+  PHX_CHECK(p1_slots_alloc(m, sl, w));
+  // PHX_OPT_DETERMINISTIC on an unstructured mesh or a sub-mesh: the element kernels run twice (exponent pass, exact
+  // accumulation pass; Slots), so matrix and right-hand side are the same bits on every run.  (Kuhn boxes gather most of
+  // their rows in closed form and keep plain atomics for the rest.)
+  bool det = false;
+  const int64_t det_slots = (int64_t)std::max<int64_t>(w.slot_rows, 1) * sl.W;
+  if (!m->is_box) PHX_CHECK(det_alloc(m, sl, det_slots, s->n, &det));
+  for (int pass = det ? 1 : 0; pass <= (det ? 2 : 0); ++pass) {
+    sl.pass = pass;
+    A.slots = sl;
+    PHX_CHECK(p1_launch_pass(m, s, bd, A, w));
+  }
+  return det_finish(m, sl, det_slots, s->n, s->rhs);
+}
+
+static int assemble_with_capacity(phx_mesh *m, double pen_coef, double stab_coef,
+                                  const double *dphi, const double *df, const double *dud, int W,
+                                  phx_system **out) {
+  SystemBuild sys(m, m->nv, 2 * m->nv, W);
+  phx_system *s = sys.s;
+  s->u_vertex_block = true;
+  const bool structured = m->is_box && !m->is_submesh && m->structured != 0;
+  AsmArgs A;
+  A.cells = m->cells; A.x = m->x; A.ctags = m->cell_tags; A.ftags = m->facet_tags;
+  A.c2f = m->c2f; A.f2c = m->f2c;
+  A.phi = dphi; A.f = df; A.ud = dud; A.gamma = pen_coef; A.sigma = stab_coef;
+  A.nv = (int32_t)m->nv;
+  {
+    DevTemps tmp(m->stream);   // its end is the one synchronisation in front of the finish
+    PHX_CHECK(p1_number(m, s, tmp));
+    if (s->n > 0) PHX_CHECK(p1_fill_slots(m, s, sys.sl, tmp, structured, A));
+  }
+  if (s->n == 0) return sys.finish_with(p1_finish_empty, out);
+  if (structured)
+    return sys.finish_with([m](phx_system *s, Slots &sl) { return finish_structured(s, sl, (int32_t)m->nv, m->export_csr != 0); }, out);
+  return sys.finish((int32_t)m->nv, out);
+}
+
+static int build_v2c(phx_mesh *m) {
+  if (m->v2c_ptr) return PHX_OK;
+  const int nvpc = m->ci.nvpc;
+  const int64_t tot = m->nc * nvpc;
+  unsigned long long *cnt = nullptr;
+  PHX_HIP(phx_malloc(&cnt, sizeof(unsigned long long) * (size_t)(m->nv + 1)));
+  PHX_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * (size_t)(m->nv + 1), m->stream));
+  PHX_HIP(phx_malloc(&m->v2c_ptr, sizeof(int64_t) * (size_t)(m->nv + 1)));
+  PHX_HIP(phx_malloc(&m->v2c_idx, sizeof(int32_t) * (size_t)tot));
+  const dim3 block(256), grid((unsigned)phx_div_up(tot, 256));
+  k_v2c_count<<<grid, block, 0, m->stream>>>(m->nc, nvpc, m->cells, cnt);
+  PHX_CHECK(exclusive_sum<int64_t>(m, (const int64_t *)cnt, m->v2c_ptr, m->nv + 1));
+  PHX_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned long long) * (size_t)(m->nv + 1), m->stream));
+  k_v2c_fill<<<grid, block, 0, m->stream>>>(m->nc, nvpc, m->cells, m->v2c_ptr, cnt, m->v2c_idx);
+  PHX_HIP(hipGetLastError());
+  PHX_HIP(hipStreamSynchronize(m->stream));
+  PHX_HIP(phx_free(cnt));
+  return PHX_OK;
+}
+
 // caller-supplied Kuhn box (phx_mesh::inner): tags and nodal data into the numbering of the generated box
 __global__ void k_push_tags(int64_t n, const int32_t *__restrict__ map, const int8_t *__restrict__ src, int8_t *__restrict__ dst) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -2063,21 +2047,20 @@ static int assemble_poisson_wd_on_inner(phx_mesh *m, double pen_coef, double sta
   for (int i = 0; i < 4; ++i) in->tag_hist[i] = m->tag_hist[i];
   for (int i = 0; i < 8; ++i) in->ftag_hist[i] = m->ftag_hist[i];
   in->has_exterior_override = m->has_exterior_override;
-  const double *src[3], *dev[3];
-  double *owned[3] = {nullptr, nullptr, nullptr}, *perm[3] = {nullptr, nullptr, nullptr};
-  src[0] = phi_h; src[1] = f_h; src[2] = u_D;
+  DevTemps tmp(st);   // host inputs staged on the device, and all three in the numbering of the generated box
+  const double *src[3] = {phi_h, f_h, u_D}, *dev[3];
+  double *perm[3] = {nullptr, nullptr, nullptr};
   const dim3 gv((unsigned)phx_div_up(m->nv, 256));
   for (int k = 0; k < 3; ++k) {
-    PHX_CHECK(to_device(m, src[k], loc, m->nv, &dev[k], &owned[k]));
-    PHX_HIP(phx_malloc(&perm[k], sizeof(double) * (size_t)m->nv));
+    PHX_CHECK(to_device(m, src[k], loc, m->nv, &dev[k], tmp));
+    PHX_HIP(tmp.alloc(&perm[k], sizeof(double) * (size_t)m->nv));
     k_gather_nodal<<<gv, block, 0, st>>>(m->nv, m->lat2v, dev[k], perm[k]);
   }
   PHX_HIP(hipGetLastError());
-  const int rc = phx_assemble_poisson_wd(in, pen_coef, stab_coef, perm[0], perm[1], perm[2], PHX_DEVICE, out);
-  PHX_HIP(hipStreamSynchronize(st));
-  for (int k = 0; k < 3; ++k) { if (owned[k]) (void)phx_free(owned[k]); (void)phx_free(perm[k]); }
-  if (rc == PHX_OK) { (*out)->out_vertex = m->lat2v; (*out)->outer = m; }
-  return rc;
+  PHX_CHECK(phx_assemble_poisson_wd(in, pen_coef, stab_coef, perm[0], perm[1], perm[2], PHX_DEVICE, out));
+  (*out)->out_vertex = m->lat2v;
+  (*out)->outer = m;
+  return PHX_OK;
 }
 
 static int assemble_wd_quad_with_capacity(phx_mesh *m, double pen_coef, double stab_coef, const double *dphi,
@@ -2095,22 +2078,18 @@ extern "C" int phx_assemble_poisson_wd(phx_mesh *m, double pen_coef, double stab
   // a caller-supplied mesh that is a Kuhn box in disguise: assemble (and later solve) on the generated box behind it
   if (m->inner) return assemble_poisson_wd_on_inner(m, pen_coef, stab_coef, phi_h, f_h, u_D, loc, out);
   if (!m->is_box && !quad) PHX_CHECK(build_v2c(m));  // Kuhn boxes enumerate vertex stars in closed form
+  DevTemps staged(m->stream);
   const double *dphi, *df, *dud;
-  double *o1, *o2, *o3;
-  PHX_CHECK(to_device(m, phi_h, loc, m->nv, &dphi, &o1));
-  PHX_CHECK(to_device(m, f_h, loc, m->nv, &df, &o2));
-  PHX_CHECK(to_device(m, u_D, loc, m->nv, &dud, &o3));
+  PHX_CHECK(to_device(m, phi_h, loc, m->nv, &dphi, staged));
+  PHX_CHECK(to_device(m, f_h, loc, m->nv, &df, staged));
+  PHX_CHECK(to_device(m, u_D, loc, m->nv, &dud, staged));
   PHX_CHECK(phx_begin_timing(m));
-  int W = m->gdim == 3 ? 64 : 32;
-  int rc = quad ? assemble_wd_quad_with_capacity(m, pen_coef, stab_coef, dphi, df, dud, W, out)
-               : assemble_with_capacity(m, pen_coef, stab_coef, dphi, df, dud, W, out);
-  if (rc == PHX_ERR_CAPACITY && W < 64)
-    rc = quad ? assemble_wd_quad_with_capacity(m, pen_coef, stab_coef, dphi, df, dud, 64, out)
-              : assemble_with_capacity(m, pen_coef, stab_coef, dphi, df, dud, 64, out);
+  const auto run = [&](int W) {
+    return quad ? assemble_wd_quad_with_capacity(m, pen_coef, stab_coef, dphi, df, dud, W, out)
+                : assemble_with_capacity(m, pen_coef, stab_coef, dphi, df, dud, W, out);
+  };
+  int rc = m->gdim == 3 ? run(64) : retry_capacity({32, 64}, run);
   if (rc == PHX_OK) rc = phx_end_timing(m, 2);
-  if (o1) (void)phx_free(o1);
-  if (o2) (void)phx_free(o2);
-  if (o3) (void)phx_free(o3);
   return rc;
 }
 

@@ -230,7 +230,7 @@ static int assemble_flux_with_capacity(phx_mesh *m, const double *params, int fa
   A.cells = m->cells; A.x = m->x; A.ctags = m->cell_tags; A.c2f = m->c2f; A.f2c = m->f2c; A.c2e = m->c2e;
   A.phi = dphi; A.f = df; A.g = dg; A.nv = m->nv;
   A.gamma = params[0]; A.sigma = params[1]; A.kappa = params[2];
-  PHX_CHECK(upload_rule(m, D, qdeg, &A.cut, tmp.blocks));
+  PHX_CHECK(upload_rule(m, D, qdeg, &A.cut, tmp));
   // ---- active numbering.  Jacobi only (every row counts as a u row): the lattice preconditioner on the u rows
   // (which come first) makes BiCGStab worse here -- the y / p penalty blocks dominate (Robin demo, 200^2: 10072
   // iterations instead of 2800; 400^2 diverges)

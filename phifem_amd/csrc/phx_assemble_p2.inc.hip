@@ -94,14 +94,12 @@ struct DevRule {
   const double *w;
 };
 
-static int upload_rule(phx_mesh *m, int d, int degree, DevRule *r, std::vector<void *> &keep) {
+static int upload_rule(phx_mesh *m, int d, int degree, DevRule *r, DevTemps &keep) {
   std::vector<double> lam, w;
   conical_rule(d, degree, lam, w);
   double *dl = nullptr, *dw = nullptr;
-  PHX_HIP(phx_malloc(&dl, sizeof(double) * lam.size()));
-  keep.push_back(dl);   // the caller's list owns each block from here on, also when a later step fails
-  PHX_HIP(phx_malloc(&dw, sizeof(double) * w.size()));
-  keep.push_back(dw);
+  PHX_HIP(keep.alloc(&dl, sizeof(double) * lam.size()));
+  PHX_HIP(keep.alloc(&dw, sizeof(double) * w.size()));
   PHX_HIP(hipMemcpyAsync(dl, lam.data(), sizeof(double) * lam.size(), hipMemcpyHostToDevice, m->stream));
   PHX_HIP(hipMemcpyAsync(dw, w.data(), sizeof(double) * w.size(), hipMemcpyHostToDevice, m->stream));
   PHX_HIP(hipStreamSynchronize(m->stream));
@@ -598,41 +596,25 @@ __global__ void __launch_bounds__(256) k_p2_facets(int64_t nlist, const int32_t 
   }
 }
 
+// work lists of the element kernels; the blocks belong to the caller's DevTemps
+struct P2Work {
+  int32_t *l_om = nullptr, *l_cut = nullptr, *l_fac = nullptr;
+  int64_t n_om = 0, n_cut = 0, n_fac = 0;
+};
+
 #include "phx_assemble_p2s.inc.hip"
 
-static int assemble_p2_with_capacity(phx_mesh *m, double pen_coef, double stab_coef, int kphi,
-                                     const double *dphi, const double *df, const double *dud,
-                                     int W, phx_system **out) {
+// Active numbering of the P2 x P2 DoFs (vertices, then edges)
+static int p2_number(phx_mesh *m, phx_system *s, const P2Args &P, int64_t nent) {
   const int D = m->gdim;
-  const int64_t nent = m->nv + m->ne;
-  // 3-D Kuhn boxes: structured system -- the interior rows are applied from stencils, only the band around Gamma_h is
-  // assembled and stored (phx_assemble_p2s.inc.hip).  Not with PHX_OPT_EXPORT_CSR (the export wants every row).
-  const bool structured = D == 3 && m->is_box && !m->is_submesh && m->structured != 0 && !m->export_csr;
-  PHX_REQUIRE(nent < INT32_MAX - 2 && (structured || 2 * nent < INT32_MAX), PHX_ERR_VALUE,
-              "too many P2 DoFs for 32-bit column keys");
-  phx_system *s = new phx_system();
-  s->mesh = m; s->device = m->device; s->nfull = 2 * nent; s->slot_cap = W; s->nent = nent;
-  s->u_p2_block = true;
   const dim3 block(256);
-  std::vector<void *> keep;
-  P2Args P;
-  memset(&P, 0, sizeof(P));
-  PHX_CHECK(upload_rule(m, D, 4, &P.cell, keep));
-  PHX_CHECK(upload_rule(m, D, 4 + 2 * kphi, &P.cut, keep));
-  PHX_CHECK(upload_rule(m, D - 1, 3, &P.facet, keep));
-  PHX_REQUIRE(P.cut.nq <= P2_CUT_NQMAX(D), PHX_ERR_VALUE, "cut-cell rule larger than the tables of k_p2_cut");
-  PHX_REQUIRE(P.facet.nq <= P2_FACET_NQMAX, PHX_ERR_VALUE, "facet rule larger than the tables of k_p2_facets");
-  // facet rules carry D barycentric coordinates per point
+  DevTemps tmp(m->stream);   // its end is the synchronisation behind the numbering
   uint8_t *fu = nullptr, *fp = nullptr;
   int32_t *su = nullptr, *sp = nullptr;
-  PHX_HIP(phx_malloc(&fu, (size_t)nent)); PHX_HIP(phx_malloc(&fp, (size_t)nent));
-  PHX_HIP(phx_malloc(&su, sizeof(int32_t) * (size_t)nent)); PHX_HIP(phx_malloc(&sp, sizeof(int32_t) * (size_t)nent));
+  PHX_HIP(tmp.alloc(&fu, (size_t)nent)); PHX_HIP(tmp.alloc(&fp, (size_t)nent));
+  PHX_HIP(tmp.alloc(&su, sizeof(int32_t) * (size_t)nent)); PHX_HIP(tmp.alloc(&sp, sizeof(int32_t) * (size_t)nent));
   PHX_HIP(hipMemsetAsync(fu, 0, (size_t)nent, m->stream));
   PHX_HIP(hipMemsetAsync(fp, 0, (size_t)nent, m->stream));
-  P.A.cells = m->cells; P.A.x = m->x; P.A.ctags = m->cell_tags; P.A.ftags = m->facet_tags;
-  P.A.c2f = m->c2f; P.A.f2c = m->f2c; P.A.phi = dphi; P.A.f = df; P.A.ud = dud;
-  P.A.gamma = pen_coef; P.A.sigma = stab_coef; P.A.nv = (int32_t)nent;
-  P.c2e = m->c2e; P.nvert = (int32_t)m->nv; P.kphi = kphi;
   const dim3 gcells((unsigned)phx_div_up(m->nc, 256));
   if (D == 2) k_p2_mark_active<2><<<gcells, block, 0, m->stream>>>(m->nc, P, fu, fp);
   else k_p2_mark_active<3><<<gcells, block, 0, m->stream>>>(m->nc, P, fu, fp);
@@ -646,89 +628,109 @@ static int assemble_p2_with_capacity(phx_mesh *m, double pen_coef, double stab_c
   PHX_HIP(phx_malloc(&s->full_of_active, sizeof(int64_t) * (size_t)s->n));
   k_finish_numbering<<<dim3((unsigned)phx_div_up(nent, 256)), block, 0, m->stream>>>(
       nent, fu, fp, su, sp, nu, s->dof_of_vertex_u, s->dof_of_vertex_p, s->full_of_active);
-  PHX_HIP(hipStreamSynchronize(m->stream));
-  PHX_HIP(phx_free(fu)); PHX_HIP(phx_free(fp)); PHX_HIP(phx_free(su)); PHX_HIP(phx_free(sp));
-  Slots sl;
-  sl.W = W;
-  sl.cols = nullptr; sl.vals = nullptr; sl.overflow = nullptr;
-  PHX_HIP(phx_malloc(&s->rhs, sizeof(double) * (size_t)s->n));
-  PHX_HIP(hipMemsetAsync(s->rhs, 0, sizeof(double) * (size_t)s->n, m->stream));
+  return PHX_OK;
+}
+
+// The element kernels of one pass, in stream order: cells, cut cells, boundary term, ghost penalty
+static int p2_launch_pass(phx_mesh *m, const P2Args &P, const P2Work &w, const DsEntities &ds) {
+  const int D = m->gdim;
+  const dim3 block(256);
+  if (w.n_om > 0) {
+    const dim3 gom((unsigned)std::min<int64_t>(phx_div_up(w.n_om, 4), 4096));
+    if (D == 2) k_p2_cells<2><<<gom, block, 0, m->stream>>>(w.n_om, w.l_om, P);
+    else k_p2_cells<3><<<gom, block, 0, m->stream>>>(w.n_om, w.l_om, P);
+  }
+  if (w.n_cut > 0) {
+    const dim3 gcut((unsigned)std::min<int64_t>(phx_div_up(w.n_cut, 4), 4096));
+    if (D == 2) k_p2_cut<2><<<gcut, block, 0, m->stream>>>(w.n_cut, w.l_cut, P);
+    else k_p2_cut<3><<<gcut, block, 0, m->stream>>>(w.n_cut, w.l_cut, P);
+  }
+  PHX_HIP(hipGetLastError());
+  if (ds.n > 0) {
+    if (D == 2) k_p2_ds<2, 64><<<dim3((unsigned)phx_div_up(ds.n * 64, 256)), block, 0, m->stream>>>(ds.n, ds.packed, ds.pairs, P);
+    else k_p2_ds<3, 128><<<dim3((unsigned)phx_div_up(ds.n * 128, 256)), block, 0, m->stream>>>(ds.n, ds.packed, ds.pairs, P);
+  }
+  if (w.n_fac > 0) {
+    const dim3 gfac((unsigned)std::min<int64_t>(phx_div_up(w.n_fac, 4), 4096));
+    if (D == 2) k_p2_facets<2><<<gfac, block, 0, m->stream>>>(w.n_fac, w.l_fac, P);
+    else k_p2_facets<3><<<gfac, block, 0, m->stream>>>(w.n_fac, w.l_fac, P);
+  }
+  PHX_HIP(hipGetLastError());
+  return PHX_OK;
+}
+
+// Everything in front of the finish: quadrature rules, numbering, work lists, slots, element kernels
+static int p2_fill_slots(phx_mesh *m, SystemBuild &sys, DevTemps &tmp, bool structured, P2Args &P, P2SPrep *prep) {
+  const int D = m->gdim;
+  phx_system *s = sys.s;
+  Slots &sl = sys.sl;
+  PHX_CHECK(upload_rule(m, D, 4, &P.cell, tmp));
+  PHX_CHECK(upload_rule(m, D, 4 + 2 * P.kphi, &P.cut, tmp));
+  PHX_CHECK(upload_rule(m, D - 1, 3, &P.facet, tmp));   // facet rules carry D barycentric coordinates per point
+  PHX_REQUIRE(P.cut.nq <= P2_CUT_NQMAX(D), PHX_ERR_VALUE, "cut-cell rule larger than the tables of k_p2_cut");
+  PHX_REQUIRE(P.facet.nq <= P2_FACET_NQMAX, PHX_ERR_VALUE, "facet rule larger than the tables of k_p2_facets");
+  PHX_CHECK(p2_number(m, s, P, s->nent));
+  PHX_CHECK(rhs_alloc(m, s));
   P.A.du = s->dof_of_vertex_u; P.A.dp = s->dof_of_vertex_p; P.A.rhs = s->rhs;
-  int32_t *l_om = nullptr, *l_cut = nullptr, *l_fac = nullptr;
-  int64_t n_om = 0, n_cut = 0, n_fac = 0;
-  PHX_CHECK(build_list(m, m->nc, SelCut{m->cell_tags}, &l_cut, &n_cut));
-  PHX_CHECK(build_list(m, m->nf, SelGhostFacet{m->facet_tags, m->f2c}, &l_fac, &n_fac));
-  P2SPrep prep;
+  P2Work w;
+  PHX_CHECK(build_list(m, m->nc, SelCut{m->cell_tags}, &w.l_cut, &w.n_cut));
+  tmp.adopt(w.l_cut);
+  PHX_CHECK(build_list(m, m->nf, SelGhostFacet{m->facet_tags, m->f2c}, &w.l_fac, &w.n_fac));
+  tmp.adopt(w.l_fac);
   if (structured) {
     s->structured = true;
     s->u_unscaled = true;
     P.pneg = 1;
-    const int rcp = p2s_prepare(s, P, sl, l_fac, n_fac, W, &prep);
-    if (rcp != PHX_OK) { (void)phx_free(l_cut); (void)phx_free(l_fac); phx_system_destroy(s); return rcp; }
-    l_om = prep.l_cells; n_om = prep.n_cells;
+    PHX_CHECK(p2s_prepare(sys, tmp, P, w, prep));
   } else {
-    PHX_HIP(phx_malloc(&sl.cols, sizeof(int32_t) * (size_t)s->n * W));
-    PHX_HIP(phx_malloc(&sl.vals, sizeof(double) * (size_t)s->n * W));
-    PHX_HIP(phx_malloc(&sl.overflow, sizeof(int)));
-    PHX_HIP(hipMemsetAsync(sl.cols, 0xff, sizeof(int32_t) * (size_t)s->n * W, m->stream));
-    PHX_HIP(hipMemsetAsync(sl.vals, 0, sizeof(double) * (size_t)s->n * W, m->stream));
-    PHX_HIP(hipMemsetAsync(sl.overflow, 0, sizeof(int), m->stream));
-    PHX_CHECK(build_list(m, m->nc, SelOmega{m->cell_tags}, &l_om, &n_om));
+    PHX_CHECK(slots_alloc(m, s->n * (int64_t)sl.W, sl.W, &sl));
+    PHX_CHECK(build_list(m, m->nc, SelOmega{m->cell_tags}, &w.l_om, &w.n_om));
+    tmp.adopt(w.l_om);
   }
   // PHX_OPT_DETERMINISTIC: the element kernels run twice (exponent pass, exact accumulation pass; Slots)
-  const int64_t nslots = structured ? prep.slot_rows * (int64_t)W + 64 : s->n * (int64_t)W;
+  const int64_t nslots = structured ? prep->slot_rows * (int64_t)sl.W + 64 : s->n * (int64_t)sl.W;
   bool det = false;
   PHX_CHECK(det_alloc(m, sl, nslots, s->n, &det));
-  const int64_t nds = m->is_submesh ? m->nbf : (phx_collect_entities(m) == PHX_OK ? m->ent_count[0] : -1);
-  PHX_REQUIRE(nds >= 0, PHX_ERR_VALUE, "integration entities unavailable");
+  DsEntities ds;
+  PHX_CHECK(ds_entities(m, &ds));
   for (int pass = det ? 1 : 0; pass <= (det ? 2 : 0); ++pass) {
     sl.pass = pass;
     P.A.slots = sl;
-    if (n_om > 0) {
-      const dim3 gom((unsigned)std::min<int64_t>(phx_div_up(n_om, 4), 4096));
-      if (D == 2) k_p2_cells<2><<<gom, block, 0, m->stream>>>(n_om, l_om, P);
-      else k_p2_cells<3><<<gom, block, 0, m->stream>>>(n_om, l_om, P);
-    }
-    if (n_cut > 0) {
-      const dim3 gcut((unsigned)std::min<int64_t>(phx_div_up(n_cut, 4), 4096));
-      if (D == 2) k_p2_cut<2><<<gcut, block, 0, m->stream>>>(n_cut, l_cut, P);
-      else k_p2_cut<3><<<gcut, block, 0, m->stream>>>(n_cut, l_cut, P);
-    }
-    PHX_HIP(hipGetLastError());
-    if (nds > 0) {
-      const int64_t *pk = m->is_submesh ? nullptr : m->ent_buf[0];
-      const int32_t *pr = m->is_submesh ? m->bfacets : nullptr;
-      if (D == 2) k_p2_ds<2, 64><<<dim3((unsigned)phx_div_up(nds * 64, 256)), block, 0, m->stream>>>(nds, pk, pr, P);
-      else k_p2_ds<3, 128><<<dim3((unsigned)phx_div_up(nds * 128, 256)), block, 0, m->stream>>>(nds, pk, pr, P);
-    }
-    if (n_fac > 0) {
-      const dim3 gfac((unsigned)std::min<int64_t>(phx_div_up(n_fac, 4), 4096));
-      if (D == 2) k_p2_facets<2><<<gfac, block, 0, m->stream>>>(n_fac, l_fac, P);
-      else k_p2_facets<3><<<gfac, block, 0, m->stream>>>(n_fac, l_fac, P);
-    }
-    PHX_HIP(hipGetLastError());
+    PHX_CHECK(p2_launch_pass(m, P, w, ds));
   }
-  PHX_CHECK(det_finish(m, sl, nslots, s->n, s->rhs));
-  PHX_HIP(hipGetLastError());
-  PHX_HIP(hipStreamSynchronize(m->stream));
-  PHX_HIP(phx_free(l_om)); PHX_HIP(phx_free(l_cut)); PHX_HIP(phx_free(l_fac));
-  for (void *p : keep) PHX_HIP(phx_free(p));
-  if (structured) {
-    int rc = check_overflow(m, sl);
-    if (rc == PHX_OK) {
-      const phx_slot_view sv{sl.cols, sl.vals, sl.W, sl.clean, sl.off, sl.wlog, true};
-      rc = phx_system_build_structured_p2(s, sv, (int32_t)nent, prep.latc0, prep.latc0i);
-      (void)free_slots(sl);
-    }
-    (void)phx_free(prep.latc0); (void)phx_free(prep.latc0i); (void)phx_free(prep.coefM);
-    if (rc != PHX_OK) { phx_system_destroy(s); return rc; }
-    *out = s;
-    return PHX_OK;
+  return det_finish(m, sl, nslots, s->n, s->rhs);
+}
+
+static int assemble_p2_with_capacity(phx_mesh *m, double pen_coef, double stab_coef, int kphi,
+                                     const double *dphi, const double *df, const double *dud,
+                                     int W, phx_system **out) {
+  const int D = m->gdim;
+  const int64_t nent = m->nv + m->ne;
+  // 3-D Kuhn boxes: structured system -- the interior rows are applied from stencils, only the band around Gamma_h is
+  // assembled and stored (phx_assemble_p2s.inc.hip).  Not with PHX_OPT_EXPORT_CSR (the export wants every row).
+  const bool structured = D == 3 && m->is_box && !m->is_submesh && m->structured != 0 && !m->export_csr;
+  PHX_REQUIRE(nent < INT32_MAX - 2 && (structured || 2 * nent < INT32_MAX), PHX_ERR_VALUE,
+              "too many P2 DoFs for 32-bit column keys");
+  SystemBuild sys(m, nent, 2 * nent, W);
+  sys.s->u_p2_block = true;
+  P2Args P;
+  memset(&P, 0, sizeof(P));
+  P.A.cells = m->cells; P.A.x = m->x; P.A.ctags = m->cell_tags; P.A.ftags = m->facet_tags;
+  P.A.c2f = m->c2f; P.A.f2c = m->f2c; P.A.phi = dphi; P.A.f = df; P.A.ud = dud;
+  P.A.gamma = pen_coef; P.A.sigma = stab_coef; P.A.nv = (int32_t)nent;
+  P.c2e = m->c2e; P.nvert = (int32_t)m->nv; P.kphi = kphi;
+  P2SPrep prep;
+  {
+    DevTemps tmp(m->stream);   // its end is the synchronisation in front of the finish
+    PHX_CHECK(p2_fill_slots(m, sys, tmp, structured, P, &prep));
   }
-  const int rc = phx_finish_system(s, sl, (int32_t)nent);
-  if (rc != PHX_OK) { phx_system_destroy(s); return rc; }
-  *out = s;
-  return PHX_OK;
+  if (!structured) return sys.finish((int32_t)nent, out);
+  return sys.finish_with([&](phx_system *s, Slots &sl) {
+    PHX_CHECK(check_overflow(m, sl));
+    const phx_slot_view sv{sl.cols, sl.vals, sl.W, sl.clean, sl.off, sl.wlog, true};
+    PHX_CHECK(phx_system_build_structured_p2(s, sv, (int32_t)nent, prep.latc0, prep.latc0i));
+    return free_slots(sl);
+  }, out);
 }
 
 extern "C" int phx_assemble_poisson_wd_p2(phx_mesh *m, double pen_coef, double stab_coef,
@@ -742,18 +744,16 @@ extern "C" int phx_assemble_poisson_wd_p2(phx_mesh *m, double pen_coef, double s
   PHX_REQUIRE(phi_degree == 1 || phi_degree == 2, PHX_ERR_VALUE, "phi_degree must be 1 or 2");
   PHX_CHECK(phx_mesh_build_edges(m));
   const int64_t nent = m->nv + m->ne;
+  DevTemps staged(m->stream);
   const double *dphi, *df, *dud;
-  double *o1, *o2, *o3;
-  PHX_CHECK(to_device(m, phi_h, loc, phi_degree == 1 ? m->nv : nent, &dphi, &o1));
-  PHX_CHECK(to_device(m, f_h, loc, nent, &df, &o2));
-  PHX_CHECK(to_device(m, u_D, loc, nent, &dud, &o3));
+  PHX_CHECK(to_device(m, phi_h, loc, phi_degree == 1 ? m->nv : nent, &dphi, staged));
+  PHX_CHECK(to_device(m, f_h, loc, nent, &df, staged));
+  PHX_CHECK(to_device(m, u_D, loc, nent, &dud, staged));
   PHX_CHECK(phx_begin_timing(m));
-  int W = m->gdim == 3 ? 256 : 128;
-  int rc = assemble_p2_with_capacity(m, pen_coef, stab_coef, phi_degree, dphi, df, dud, W, out);
-  if (rc == PHX_ERR_CAPACITY) rc = assemble_p2_with_capacity(m, pen_coef, stab_coef, phi_degree, dphi, df, dud, 2 * W, out);
+  const int W = m->gdim == 3 ? 256 : 128;
+  int rc = retry_capacity({W, 2 * W}, [&](int Wk) {
+    return assemble_p2_with_capacity(m, pen_coef, stab_coef, phi_degree, dphi, df, dud, Wk, out);
+  });
   if (rc == PHX_OK) rc = phx_end_timing(m, 2);
-  if (o1) (void)phx_free(o1);
-  if (o2) (void)phx_free(o2);
-  if (o3) (void)phx_free(o3);
   return rc;
 }

@@ -197,17 +197,14 @@ static phx_p2_lattice p2s_lattice(const phx_mesh *m) {
 // Everything between the active numbering and the element kernels of a structured P2 assembly: C0 / c0i flags, the
 // stencil tables, slots for the stored rows only, right-hand side and diagonal of the c0i rows, the cell work list.
 struct P2SPrep {
-  uint8_t *latc0 = nullptr, *latc0i = nullptr;   // [F0 F1 F2]
-  int32_t *l_cells = nullptr;
-  int64_t n_cells = 0;
-  double *coefM = nullptr;
+  uint8_t *latc0 = nullptr, *latc0i = nullptr;   // [F0 F1 F2]; the system build reads them (SystemBuild::held)
   int64_t slot_rows = 0;
 };
 
-static int p2s_prepare(phx_system *s, P2Args &P, Slots &sl, const int32_t *l_fac, int64_t n_fac, int W, P2SPrep *out) {
+// the lattice and the stencil tables of the C0 rows on the system; *coefM: the mass stencils (right-hand side of c0i rows)
+static int p2s_upload_tables(phx_system *s, DevTemps &tmp, double **coefM) {
   phx_mesh *m = s->mesh;
   hipStream_t st = m->stream;
-  const dim3 block(256);
   const int64_t nent = s->nent;
   phx_p2_struct *ps = new phx_p2_struct();
   s->p2s = ps;
@@ -225,10 +222,10 @@ static int p2s_prepare(phx_system *s, P2Args &P, Slots &sl, const int32_t *l_fac
     for (int o = 0; o < 125; ++o)
       if (K[(size_t)cls * 125 + o] != 0.0) mask[cls >> 1][o >> 6] |= 1ull << (o & 63);
   PHX_HIP(phx_malloc(&ps->coef, sizeof(double) * 1000));
-  PHX_HIP(phx_malloc(&out->coefM, sizeof(double) * 1000));
+  PHX_HIP(tmp.alloc(coefM, sizeof(double) * 1000));
   PHX_HIP(phx_malloc(&ps->mask, sizeof(mask)));
   PHX_HIP(hipMemcpyAsync(ps->coef, K.data(), sizeof(double) * 1000, hipMemcpyHostToDevice, st));
-  PHX_HIP(hipMemcpyAsync(out->coefM, M.data(), sizeof(double) * 1000, hipMemcpyHostToDevice, st));
+  PHX_HIP(hipMemcpyAsync(*coefM, M.data(), sizeof(double) * 1000, hipMemcpyHostToDevice, st));
   PHX_HIP(hipMemcpyAsync(ps->mask, mask, sizeof(mask), hipMemcpyHostToDevice, st));
   std::vector<double> tabE(500), tabO(500);
   unsigned linemask[4] = {0, 0, 0, 0};
@@ -248,9 +245,26 @@ static int p2s_prepare(phx_system *s, P2Args &P, Slots &sl, const int32_t *l_fac
   PHX_HIP(hipMemcpyAsync(ps->tabO, tabO.data(), sizeof(double) * 500, hipMemcpyHostToDevice, st));
   PHX_HIP(hipMemcpyAsync(ps->linemask, linemask, sizeof(linemask), hipMemcpyHostToDevice, st));
   PHX_HIP(hipStreamSynchronize(st));   // K, M, mask, tab are host temporaries
+  return PHX_OK;
+}
+
+// C0 / c0i flags, slots of the stored rows, right-hand side and diagonal of the rows the stencils apply
+static int p2s_stored_rows(SystemBuild &sys, P2Args &P, const int32_t *l_fac, int64_t n_fac, const double *coefM,
+                           P2SPrep *out) {
+  phx_system *s = sys.s;
+  Slots &sl = sys.sl;
+  phx_mesh *m = s->mesh;
+  hipStream_t st = m->stream;
+  const dim3 block(256);
+  const int64_t nent = s->nent;
+  const int W = sl.W;
+  const phx_p2_struct *ps = s->p2s;
+  const phx_p2_lattice &L = ps->lat;
+  const int64_t NF = L.F[0] * L.F[1] * L.F[2];
+  DevTemps loc(st);   // its end is the synchronisation behind k_p2s_rows
   // ---- C0 on the fine lattice, c0i by erosion with the 5 x 5 x 5 box
   uint8_t *bad = nullptr, *tmp = nullptr;
-  PHX_HIP(phx_malloc(&bad, (size_t)nent));
+  PHX_HIP(loc.alloc(&bad, (size_t)nent));
   PHX_HIP(hipMemsetAsync(bad, 0, (size_t)nent, st));
   k_p2s_mark_bad_cells<<<dim3((unsigned)phx_div_up(m->nc, 256)), block, 0, st>>>(m->nc, P, bad);
   if (n_fac > 0) k_p2s_mark_bad_facets<<<dim3((unsigned)phx_div_up(n_fac, 256)), block, 0, st>>>(n_fac, l_fac, P, bad);
@@ -258,8 +272,10 @@ static int p2s_prepare(phx_system *s, P2Args &P, Slots &sl, const int32_t *l_fac
   if (m->ent_count[0] > 0)
     k_p2s_mark_bad_ents<<<dim3((unsigned)phx_div_up(m->ent_count[0], 256)), block, 0, st>>>(m->ent_count[0], m->ent_buf[0], P, bad);
   PHX_HIP(phx_malloc(&out->latc0, (size_t)NF));
+  sys.held.push_back(out->latc0);
   PHX_HIP(phx_malloc(&out->latc0i, (size_t)NF));
-  PHX_HIP(phx_malloc(&tmp, (size_t)NF));
+  sys.held.push_back(out->latc0i);
+  PHX_HIP(loc.alloc(&tmp, (size_t)NF));
   PHX_HIP(hipMemsetAsync(out->latc0, 0, (size_t)NF, st));
   const dim3 gent((unsigned)phx_div_up(nent, 256)), gfine((unsigned)phx_div_up(NF, 256));
   k_p2s_lat_c0<<<gent, block, 0, st>>>(nent, L, s->dof_of_vertex_u, bad, out->latc0);
@@ -273,8 +289,8 @@ static int p2s_prepare(phx_system *s, P2Args &P, Slots &sl, const int32_t *l_fac
   // ---- slots of the stored rows
   int32_t *rank = nullptr, nstored = 0;
   uint8_t *notc0 = nullptr;
-  PHX_HIP(phx_malloc(&rank, sizeof(int32_t) * (size_t)s->n));
-  PHX_HIP(phx_malloc(&notc0, (size_t)s->n));
+  PHX_HIP(loc.alloc(&rank, sizeof(int32_t) * (size_t)s->n));
+  PHX_HIP(loc.alloc(&notc0, (size_t)s->n));
   const dim3 gn((unsigned)phx_div_up(s->n, 256));
   k_not_flags<<<gn, block, 0, st>>>(s->n, s->c0, notc0);
   PHX_CHECK(scan_flags(m, notc0, rank, s->n, &nstored));
@@ -282,28 +298,31 @@ static int p2s_prepare(phx_system *s, P2Args &P, Slots &sl, const int32_t *l_fac
   int64_t *off = nullptr;
   uint8_t *wl = nullptr;
   PHX_HIP(phx_malloc(&off, sizeof(int64_t) * (size_t)s->n));
+  sl.off = off;
   PHX_HIP(phx_malloc(&wl, (size_t)s->n));
+  sl.wlog = wl;
   int lg = 0;
   while ((1 << lg) < W) ++lg;
   k_p2s_slot_offsets<<<gn, block, 0, st>>>(s->n, W, lg, s->c0, rank, (int64_t)nstored * W, off, wl);
-  sl.off = off; sl.wlog = wl;
-  const size_t ns = (size_t)nstored * W + 64;
-  PHX_HIP(phx_malloc(&sl.cols, sizeof(int32_t) * ns));
-  PHX_HIP(phx_malloc(&sl.vals, sizeof(double) * ns));
-  PHX_HIP(phx_malloc(&sl.overflow, sizeof(int)));
-  PHX_HIP(hipMemsetAsync(sl.cols, 0xff, sizeof(int32_t) * ns, st));
-  PHX_HIP(hipMemsetAsync(sl.vals, 0, sizeof(double) * ns, st));
-  PHX_HIP(hipMemsetAsync(sl.overflow, 0, sizeof(int), st));
+  PHX_CHECK(slots_alloc(m, (int64_t)nstored * W + 64, W, &sl));
   // ---- right-hand side and diagonal of the rows the stencils apply
   PHX_HIP(phx_malloc(&s->diag, sizeof(double) * (size_t)s->n));
   PHX_HIP(hipMemsetAsync(s->diag, 0, sizeof(double) * (size_t)s->n, st));
-  k_p2s_rows<<<gfine, block, 0, st>>>(NF, L, out->latc0i, s->dof_of_vertex_u, ps->coef, out->coefM, P.A.f, s->rhs, s->diag);
+  k_p2s_rows<<<gfine, block, 0, st>>>(NF, L, out->latc0i, s->dof_of_vertex_u, ps->coef, coefM, P.A.f, s->rhs, s->diag);
   PHX_HIP(hipGetLastError());
-  PHX_HIP(hipStreamSynchronize(st));
-  PHX_HIP(phx_free(bad)); PHX_HIP(phx_free(tmp)); PHX_HIP(phx_free(rank)); PHX_HIP(phx_free(notc0));
+  return PHX_OK;
+}
+
+static int p2s_prepare(SystemBuild &sys, DevTemps &tmp, P2Args &P, P2Work &w, P2SPrep *out) {
+  phx_system *s = sys.s;
+  phx_mesh *m = s->mesh;
+  double *coefM = nullptr;
+  PHX_CHECK(p2s_upload_tables(s, tmp, &coefM));
+  PHX_CHECK(p2s_stored_rows(sys, P, w.l_fac, w.n_fac, coefM, out));
   // ---- cells that touch a stored row
   P.A.c0 = s->c0;
   PHX_CHECK(build_list(m, m->nc, SelP2StoredCell{m->cell_tags, m->cells, m->c2e, (int32_t)m->nv, s->dof_of_vertex_u, s->c0},
-                       &out->l_cells, &out->n_cells));
+                       &w.l_om, &w.n_om));
+  tmp.adopt(w.l_om);
   return PHX_OK;
 }

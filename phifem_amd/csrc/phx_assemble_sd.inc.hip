@@ -287,8 +287,8 @@ static int assemble_sd_impl(phx_mesh *m, double stab_coef, int kphi, const doubl
   const dim3 block(256);
   SdArgs P;
   memset(&P, 0, sizeof(P));
-  PHX_CHECK(upload_rule(m, D, 2 * K + kphi, &P.cell, tmp.blocks));
-  PHX_CHECK(upload_rule(m, D - 1, 2 * (K + kphi) - 1, &P.facet, tmp.blocks));
+  PHX_CHECK(upload_rule(m, D, 2 * K + kphi, &P.cell, tmp));
+  PHX_CHECK(upload_rule(m, D - 1, 2 * (K + kphi) - 1, &P.facet, tmp));
   P.A.cells = m->cells; P.A.x = m->x; P.A.ctags = m->cell_tags; P.A.ftags = m->facet_tags;
   P.A.c2f = m->c2f; P.A.f2c = m->f2c; P.A.phi = dphi; P.A.f = df; P.A.ud = nullptr;
   P.A.gamma = 0.0; P.A.sigma = stab_coef; P.A.nv = (int32_t)nent;

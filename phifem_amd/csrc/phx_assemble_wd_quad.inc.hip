@@ -198,7 +198,7 @@ static int assemble_wd_quad_with_capacity(phx_mesh *m, double pen_coef, double s
   Slots &sl = sys.sl;
   s->u_vertex_block = true;
   const dim3 block(256);
-  // ---- active numbering (assemble_with_capacity)
+  // ---- active numbering (as p1_number, always from the cells)
   uint8_t *fu = nullptr, *fp = nullptr;
   unsigned long long *sup = nullptr;
   PHX_HIP(tmp.alloc(&sup, sizeof(unsigned long long) * (size_t)m->nv));

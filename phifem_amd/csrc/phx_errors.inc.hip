@@ -381,31 +381,29 @@ extern "C" int phx_cell_errors(phx_mesh *m, int ncomp, int degree_h, const doubl
   if (ncells == 0) { for (int k = 0; k < 4; ++k) norms[k] = 0.0; return PHX_OK; }
   const int D = m->gdim, NB = quad ? 16 : (D == 3 ? 20 : 10);
   const int64_t ndh = degree_h == 1 ? m->nv : m->nv + m->ne;
+  DevTemps staged(m->stream);   // host arrays: copies of the inputs, device room for the per-cell results
   const double *duh, *duref;
-  double *o1, *o2, *dl2 = l2_local, *dh10 = h10_local;
+  double *dl2 = l2_local, *dh10 = h10_local;
   int32_t *dlist = nullptr;
-  PHX_CHECK(to_device(m, u_h, loc, ndh * ncomp, &duh, &o1));
-  PHX_CHECK(to_device(m, u_ref, loc, ncells * NB * ncomp, &duref, &o2));
+  PHX_CHECK(to_device(m, u_h, loc, ndh * ncomp, &duh, staged));
+  PHX_CHECK(to_device(m, u_ref, loc, ncells * NB * ncomp, &duref, staged));
   if (loc != PHX_DEVICE) {
-    PHX_HIP(phx_malloc(&dl2, sizeof(double) * (size_t)ncells));
-    PHX_HIP(phx_malloc(&dh10, sizeof(double) * (size_t)ncells));
+    PHX_HIP(staged.alloc(&dl2, sizeof(double) * (size_t)ncells));
+    PHX_HIP(staged.alloc(&dh10, sizeof(double) * (size_t)ncells));
     if (cell_list) {
       for (int64_t i = 0; i < ncells; ++i)
         PHX_REQUIRE(cell_list[i] >= 0 && cell_list[i] < m->nc, PHX_ERR_VALUE, "cell index out of range");
-      PHX_HIP(phx_malloc(&dlist, sizeof(int32_t) * (size_t)ncells));
+      PHX_HIP(staged.alloc(&dlist, sizeof(int32_t) * (size_t)ncells));
       PHX_HIP(hipMemcpyAsync(dlist, cell_list, sizeof(int32_t) * (size_t)ncells, hipMemcpyHostToDevice, m->stream));
     }
   }
   const int32_t *lst = loc == PHX_DEVICE ? cell_list : dlist;
-  int rc = quad ? cell_errors_quad(m, ncomp, duh, duref, ncells, lst, dl2, dh10, norms)
-           : D == 2 ? cell_errors_impl<2>(m, ncomp, degree_h, duh, duref, ncells, lst, dl2, dh10, norms)
-                    : cell_errors_impl<3>(m, ncomp, degree_h, duh, duref, ncells, lst, dl2, dh10, norms);
-  if (rc == PHX_OK && loc != PHX_DEVICE) {
+  PHX_CHECK(quad ? cell_errors_quad(m, ncomp, duh, duref, ncells, lst, dl2, dh10, norms)
+            : D == 2 ? cell_errors_impl<2>(m, ncomp, degree_h, duh, duref, ncells, lst, dl2, dh10, norms)
+                     : cell_errors_impl<3>(m, ncomp, degree_h, duh, duref, ncells, lst, dl2, dh10, norms));
+  if (loc != PHX_DEVICE) {
     PHX_HIP(hipMemcpy(l2_local, dl2, sizeof(double) * (size_t)ncells, hipMemcpyDeviceToHost));
     PHX_HIP(hipMemcpy(h10_local, dh10, sizeof(double) * (size_t)ncells, hipMemcpyDeviceToHost));
   }
-  if (loc != PHX_DEVICE) { (void)phx_free(dl2); (void)phx_free(dh10); (void)phx_free(dlist); }
-  if (o1) (void)phx_free(o1);
-  if (o2) (void)phx_free(o2);
-  return rc;
+  return PHX_OK;
 }
