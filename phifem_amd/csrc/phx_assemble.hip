@@ -2088,7 +2088,12 @@ extern "C" int phx_assemble_poisson_wd(phx_mesh *m, double pen_coef, double stab
     return quad ? assemble_wd_quad_with_capacity(m, pen_coef, stab_coef, dphi, df, dud, W, out)
                 : assemble_with_capacity(m, pen_coef, stab_coef, dphi, df, dud, W, out);
   };
-  int rc = m->gdim == 3 ? run(64) : retry_capacity({32, 64}, run);
+  // The first capacity holds every row of a mesh with the connectivity of a Kuhn lattice.  The later ones are for
+  // caller-supplied meshes with vertices of high valence: a Delaunay mesh of random points already has rows of 59 entries
+  // in 3-D.  Behind the last one the assembly is refused (PHX_ERR_CAPACITY).
+  int rc = quad           ? retry_capacity({32, 64}, run)
+           : m->gdim == 3 ? retry_capacity({64, 128, 256}, run)
+                          : retry_capacity({32, 64, 128}, run);
   if (rc == PHX_OK) rc = phx_end_timing(m, 2);
   return rc;
 }

@@ -441,7 +441,8 @@ __global__ void k_el_bc_rows(int64_t nbc, int d, ElArgs A, const int32_t *__rest
 
 // slot capacity class per active row: rows of DoFs at vertices of cut cells get `wbig` (log2), the bulk
 // rows (u_in / u_out away from the interface: at most 15 neighbours x 3 components = 45 entries, 54 next to
-// the cut layer) get 64 slots.  Measured at 24^3: longest row 225, 45 % of the rows at most 64.
+// the cut layer) get 64 slots.  Measured at 24^3: longest row 225, 45 % of the rows at most 64.  (Meshes that are not
+// generated boxes or rectangles flag every vertex in `cutv`: no 64-slot class there.)
 __global__ void k_el_row_caps(int64_t n, const int64_t *__restrict__ full_of_active, int64_t nv,
                               const uint8_t *__restrict__ cutv, int wbig, uint8_t *__restrict__ wlog,
                               int64_t *__restrict__ cap) {
@@ -522,8 +523,12 @@ static int assemble_el_with_capacity(phx_mesh *m, const double *params, const do
     uint8_t *cutv = nullptr;
     int64_t *cap = nullptr;
     PHX_HIP(caps.alloc(&cutv, (size_t)m->nv));
-    PHX_HIP(hipMemsetAsync(cutv, 0, (size_t)m->nv, m->stream));
-    if (n_cut > 0) {
+    // The 64-slot class is for generated boxes and rectangles, where the valence of a vertex is bounded.  On any other
+    // simplicial mesh it is not (21 neighbours in 3-D, 32 in 2-D already overfill 64 slots, and a retry would never reach
+    // those rows): every vertex counts as a cut-cell vertex there, so every row gets the capacity under trial.
+    const bool bulk64 = m->is_box || quad;
+    PHX_HIP(hipMemsetAsync(cutv, bulk64 ? 0 : 1, (size_t)m->nv, m->stream));
+    if (bulk64 && n_cut > 0) {
       const dim3 g((unsigned)phx_div_up(n_cut, 256));
       if (D == 2 && !quad) k_mark_cells<3><<<g, block, 0, m->stream>>>(n_cut, l_cut, m->cells, cutv);
       else k_mark_cells<4><<<g, block, 0, m->stream>>>(n_cut, l_cut, m->cells, cutv);
