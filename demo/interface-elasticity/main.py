@@ -4,10 +4,11 @@ path: the counterpart of the reference's demo/interface-elasticity/main.py with 
 (E_in = 1, E_out = 1e-3, nu = 0.3, phi = 1 - r^2, all degrees 1, box [-1.5,1.5]^2, h-refinement
 loop with relative error slopes).
 
-    python main.py [--iterations 4] [--mesh-size 0.2] [--cell-type {triangle,quadrilateral}]
+    python main.py [--iterations 4] [--mesh-size 0.2] [--cell-type {triangle,quadrilateral}] [--refine]
 
-The reference refines with dolfinx.mesh.refine; the structured background mesh is simply
-regenerated with twice the cells.  Errors as in the reference: u_h and the exact solution in the
+The reference refines with dolfinx.mesh.refine; by default the structured background mesh is simply
+regenerated with twice the cells, with --refine the loop calls `phifem_amd.refine(mesh)` as the reference
+does (main.py:390; red refinement of the Kuhn box: the box of twice the cells in another numbering).  Errors as in the reference: u_h and the exact solution in the
 degree-3 Lagrange space (Q3 on quadrilaterals), cell-wise H10 / L2 integrals
 (`phifem_amd.postprocess.cell_errors`).  --cell-type is the reference's `cell_type` parameter
 (main.py:93,99-108): triangles (default) or quadrilaterals, with Q1 spaces on the latter.
@@ -64,12 +65,17 @@ def main():
     ap.add_argument("--iterations", type=int, default=4)
     ap.add_argument("--mesh-size", type=float, default=0.2)
     ap.add_argument("--cell-type", choices=["triangle", "quadrilateral"], default="triangle")
+    ap.add_argument("--refine", action="store_true", help="refine the previous mesh instead of regenerating it")
     args = ap.parse_args()
     f = source()
     n = int(round(3.0 / args.mesh_size))
     dofs, h10s, l2s = [], [], []
+    mesh = None
     for it in range(args.iterations):
-        mesh = P.create_rectangle([[-1.5, -1.5], [1.5, 1.5]], [n, n], cell_type=args.cell_type)
+        if args.refine and mesh is not None:
+            mesh = P.refine(mesh)
+        else:
+            mesh = P.create_rectangle([[-1.5, -1.5], [1.5, 1.5]], [n, n], cell_type=args.cell_type)
         x = mesh.x
         phi = 1.0 - (x ** 2).sum(axis=1)
         with warnings.catch_warnings():
@@ -77,6 +83,8 @@ def main():
             P.compute_tags_measures(mesh, NodalFunction(phi), 1, box_mode=True)
         i, j = np.arange(mesh.nv) % (n + 1), np.arange(mesh.nv) // (n + 1)
         bc = np.flatnonzero((i == 0) | (i == n) | (j == 0) | (j == n))
+        if args.refine:      # refined meshes number their vertices level by level: the box boundary by coordinates
+            bc = np.flatnonzero(np.abs(x).max(axis=1) == 1.5)
         ue = exact_solution(x)
         solver = P.InterfaceElasticitySolver(mesh, E_in, nu_in, E_out, nu_out, 1.0, 1.0)
         info = solver.assemble(phi, f(x), ue, bc)

@@ -308,6 +308,52 @@ int phx_partition_layout(phx_mesh *m, int nparts, const int32_t *part, int rank,
  * result is a BOX-MODE mesh: the facets on its rim are cuts, not boundary -- assemble with the transferred tags. */
 int phx_submesh_create_from_flags(phx_mesh *m, const uint8_t *flags, int loc, phx_mesh **sub);
 
+/* --- uniform regular refinement and the nested coarse -> fine transfer ----------------------
+ * Stands in for dolfinx.mesh.refine (demo/interface-elasticity/main.py:390) with red (2-D) / Bey (3-D) refinement;
+ * tests/refine_ref.py restates the rules in numpy.  Purely topological: no float is compared.
+ *
+ * Fine vertices = the degree-2 Lagrange DoF points of the coarse mesh in the layout above, computed by the kernel of
+ * phx_lagrange_dof_points(m, 2): coarse vertex v stays v; simplices: the midpoint of edge e is nv + e; quadrilaterals:
+ * the midpoint of facet f is nv + f, the centre of cell c is nv + nf + c.
+ * Child k of coarse cell c is fine cell nchild * c + k (parent of a fine cell = cell / nchild).  Children in LOCAL
+ * degree-2 nodes -- 0 .. nvpc-1 the cell's vertices as stored, nvpc + k its local edge k (basix order, PHX_ARR_C2E) or
+ * local facet k (quadrilaterals), last the quadrilateral's centre; m_ij = node of the edge (i, j):
+ *   triangle       (v0, m01, m02) (m01, v1, m12) (m02, m12, v2) (m12, m02, m01)
+ *   tetrahedron    Bey's rule, interior diagonal m02 - m13:
+ *                  (v0, m01, m02, m03) (m01, v1, m12, m13) (m02, m12, v2, m23) (m03, m13, m23, v3)
+ *                  (m01, m02, m03, m13) (m01, m02, m12, m13) (m02, m03, m13, m23) (m02, m12, m13, m23)
+ *   quadrilateral  b, l, r, t = midpoints of local facets 0..3, ctr the centre (tensor-product order kept):
+ *                  (v0, b, l, ctr) (b, v1, ctr, r) (l, ctr, v2, t) (ctr, r, t, v3)
+ * Children need not keep the parent's orientation sign.
+ *
+ * phx_mesh_refine: *fine is an ordinary untagged mesh with its own stream, facet numbering and boundary list,
+ * remembering which mesh it was refined from.  When a lattice stands behind the coarse mesh (generated boxes, caller
+ * meshes recognised as lattices) the fine arrays are read back once and the fine mesh is what phx_mesh_create makes of
+ * them (same lattice detection, same generated box or lattice copy behind it); for every other mesh no mesh array
+ * returns to the host in this call.  PHX_ERR_VALUE: slab with declared cut faces (phx_mesh_set_slab_faces), fine
+ * counts beyond the 32-bit id limits (checked before anything is allocated); PHX_ERR_NOT_IMPLEMENTED: other cell types.
+ *
+ * phx_prolongate: in[ncomp][coarse ndofs(degree)] -> out[ncomp][fine ndofs(degree)], component-major, at loc_in /
+ * loc_out.  The Lagrange spaces are nested: the fine function equals the coarse one pointwise.  `fine` must be the
+ * direct result of phx_mesh_refine(coarse), else PHX_ERR_VALUE.
+ *   degree 1 (all three cell types): copy at coarse vertices, 0.5 u_p + 0.5 u_q at midpoints,
+ *     ((0.25 u0 + 0.25 u1) + 0.25 u2) + 0.25 u3 at quadrilateral centres -- bit for bit the coordinate arithmetic.
+ *   degree 2 (simplices): fine vertex DoFs are copies of the coarse vertex / edge DoFs; a fine edge DoF is the parent
+ *     cell's P2 function at the fine edge's midpoint, sum_d w[d] u[dof d of the parent] over the parent's local DoFs d
+ *     in ascending LOCAL order with zero weights skipped (weights 0, -1/8, 1/4, 3/8, 1/2, 3/4).
+ *     DETERMINISM RULE: a fine edge seen from several parent cells is written by the LOWEST-NUMBERED parent cell (an
+ *     integer min pass, then one write pass; no floating-point atomics), so every run gives the same bits.
+ *   PHX_ERR_NOT_IMPLEMENTED: degree 2 on quadrilaterals, degree 3.
+ * Both calls release every temporary on failure (phx_pool_stats live bytes return to where they were).
+ *
+ * [host] phx_refine_tables: children[nchild][nvpc] in the local nodes above, *nchild, and for simplices
+ * p2_weights[nchild][nepc][ndof2] (ndof2 = nvpc + nepc): the weights of child k's local edge j (basix order on the
+ * child's vertices).  Any output may be NULL. */
+int phx_mesh_refine(phx_mesh *m, phx_mesh **fine);
+int phx_prolongate(phx_mesh *coarse, phx_mesh *fine, int degree, int ncomp, const double *in, int loc_in,
+                   double *out, int loc_out);
+int phx_refine_tables(int cell_type, int32_t *children, int *nchild, double *p2_weights);
+
 /* ------------------------------------------------------------------ assembly --------- */
 /* Weak-Dirichlet phi-FEM Poisson, mixed (u,p) in P1 x P1: bilinear form
  * demo/weak-dirichlet/flower/main.py:112-135 + assemble_matrix :137-139, linear form :142-151 +

@@ -103,6 +103,9 @@ SIGNATURES = {
     "phx_partition_cells": ([_vp, _i, _vp, _vp, _i], _i),
     "phx_partition_layout": ([_vp, _i, _vp, _i, _vp, _vp, _i], _i),
     "phx_submesh_create_from_flags": ([_vp, _vp, _i, C.POINTER(_vp)], _i),
+    "phx_mesh_refine": ([_vp, C.POINTER(_vp)], _i),
+    "phx_prolongate": ([_vp, _vp, _i, _i, _vp, _i, _vp, _i], _i),
+    "phx_refine_tables": ([_i, _vp, _pi, _vp], _i),
     "phx_assemble_poisson_wd": ([_vp, _d, _d, _vp, _vp, _vp, _i, C.POINTER(_vp)], _i),
     "phx_assemble_poisson_wd_p2": ([_vp, _d, _d, _vp, _i, _vp, _vp, _i, C.POINTER(_vp)], _i),
     "phx_assemble_poisson_sd": ([_vp, _d, _i, _vp, _i, _vp, _i, C.POINTER(_vp)], _i),

@@ -2075,8 +2075,11 @@ extern "C" int phx_assemble_poisson_wd(phx_mesh *m, double pen_coef, double stab
               "assembly supports triangles, tetrahedra and quadrilaterals (axis-parallel rectangles) only");
   PHX_REQUIRE(m->have_cell_tags && m->have_facet_tags, PHX_ERR_VALUE,
               "cell and facet tags must be computed before assembly");
-  // a caller-supplied mesh that is a Kuhn box in disguise: assemble (and later solve) on the generated box behind it
-  if (m->inner) return assemble_poisson_wd_on_inner(m, pen_coef, stab_coef, phi_h, f_h, u_D, loc, out);
+  // a caller-supplied mesh that is a Kuhn box in disguise: assemble (and later solve) on the generated box behind it.
+  // Not with PHX_OPT_DETERMINISTIC: the generated box keeps plain atomics for its scattered terms (p1_fill_slots), so
+  // its matrix changes in the last bit from run to run; the caller's own mesh takes the exact two-pass accumulation
+  // and keeps the lattice preconditioner through its vertex maps (the quadrilateral lattice copy is exact already)
+  if (m->inner && (quad || !m->deterministic)) return assemble_poisson_wd_on_inner(m, pen_coef, stab_coef, phi_h, f_h, u_D, loc, out);
   if (!m->is_box && !quad) PHX_CHECK(build_v2c(m));  // Kuhn boxes enumerate vertex stars in closed form
   DevTemps staged(m->stream);
   const double *dphi, *df, *dud;

@@ -74,7 +74,13 @@ struct phx_cell_info {
 };
 int phx_get_cell_info(int cell_type, phx_cell_info *ci);
 
+uint64_t phx_next_mesh_uid(void);   // phx_mesh.hip: 1, 2, ... never reused within a process
+
 struct phx_mesh {
+  uint64_t uid = phx_next_mesh_uid();
+  // uniform refinement (phx_refine.inc.hip): uid of the mesh this one was refined from (0: none), children per cell
+  uint64_t refined_from = 0;
+  int refine_nchild = 0;
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -90,9 +96,10 @@ struct phx_mesh {
   // slab of a partitioned box: facets on an ARTIFICIAL end plane are not background-boundary
   // facets; they stay untagged (0) and are left out of the `ds` detection
   uint8_t *facet_exempt = nullptr;  // [nf] or NULL
+  bool slab_cut = false;            // phx_mesh_set_slab_faces declared a cut face
   // vertex -> incident cells (CSR), built on first assembly: rows of the stiffness block are
   // gathered by their owning vertex instead of scattered with atomics
-  // edges (P2 DoFs): 2-D edges ARE the facets; 3-D boxes use a closed form, others a host sort
+  // edges (P2 DoFs): 2-D edges ARE the facets; 3-D boxes use a closed form, others a device sort
   int64_t ne = 0;
   int32_t *c2e = nullptr;    // [nc*nepc], local edge k per basix: tri (1,2),(0,2),(0,1);
                              // tet (2,3),(1,3),(1,2),(0,3),(0,2),(0,1)

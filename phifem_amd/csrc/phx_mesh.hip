@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <atomic>
 #include <vector>
 
 #include "phx_common.h"
@@ -129,6 +130,11 @@ extern "C" int phx_pool_stats(int64_t *live_bytes, int64_t *cached_bytes) {
   if (live_bytes) *live_bytes = (int64_t)P.live_bytes;
   if (cached_bytes) *cached_bytes = (int64_t)P.cached;
   return PHX_OK;
+}
+
+uint64_t phx_next_mesh_uid(void) {
+  static std::atomic<uint64_t> next{0};
+  return ++next;
 }
 
 extern "C" int phx_version(void) { return 1; }
@@ -959,6 +965,7 @@ extern "C" int phx_mesh_set_slab_faces(phx_mesh *m, int lower_is_cut, int upper_
         upper_is_cut, m->box_plane, m->box_nlast, m->facet_exempt);
   PHX_HIP(hipGetLastError());
   PHX_HIP(hipStreamSynchronize(m->stream));
+  m->slab_cut = lower_is_cut || upper_is_cut;
   m->have_facet_tags = false;
   m->have_entities = false;
   return PHX_OK;
@@ -1021,6 +1028,71 @@ __global__ void k_edge_vertices(int64_t nc, int nvpc, int nepc, int is_tet,
   }
 }
 
+// slot i = (cell, local edge) of a tetrahedral mesh -> key (lower vertex << 32) | upper vertex
+__global__ void k_edge_keys(int64_t n, const int32_t *__restrict__ cells, unsigned long long *__restrict__ key,
+                            int32_t *__restrict__ idx) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t c = i / 6;
+  const int k = (int)(i - c * 6);
+  const int32_t va = cells[c * 4 + c_tet_edge[k][0]], vb = cells[c * 4 + c_tet_edge[k][1]];
+  key[i] = ((unsigned long long)(uint32_t)(va < vb ? va : vb) << 32) | (uint32_t)(va < vb ? vb : va);
+  idx[i] = (int32_t)i;
+}
+__global__ void k_edge_heads(int64_t n, const unsigned long long *__restrict__ key, uint8_t *__restrict__ head) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i < n) head[i] = (i == 0 || key[i] != key[i - 1]) ? 1 : 0;
+}
+__global__ void k_edge_fill(int64_t n, const uint8_t *__restrict__ head, const int32_t *__restrict__ rank,
+                            const int32_t *__restrict__ idx, int32_t *__restrict__ c2e) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i < n) c2e[idx[i]] = rank[i] + head[i] - 1;
+}
+
+static int build_edges_device(phx_mesh *m) {
+  hipStream_t st = m->stream;
+  const int64_t n = m->nc * 6;
+  PHX_REQUIRE(n < INT32_MAX, PHX_ERR_VALUE, "too many edges for 32-bit local ids");
+  unsigned long long *key = nullptr, *key2 = nullptr;
+  int32_t *idx = nullptr, *idx2 = nullptr, *rank = nullptr, *c2e = nullptr;
+  uint8_t *head = nullptr;
+  void *tmp = nullptr;
+  auto release = [&]() {
+    (void)phx_free(key); (void)phx_free(key2); (void)phx_free(idx); (void)phx_free(idx2); (void)phx_free(rank);
+    (void)phx_free(head); (void)phx_free(tmp); (void)phx_free(c2e);
+  };
+  auto run = [&]() -> int {
+    PHX_HIP(phx_malloc(&key, sizeof(unsigned long long) * (size_t)n));
+    PHX_HIP(phx_malloc(&key2, sizeof(unsigned long long) * (size_t)n));
+    PHX_HIP(phx_malloc(&idx, sizeof(int32_t) * (size_t)n));
+    PHX_HIP(phx_malloc(&idx2, sizeof(int32_t) * (size_t)n));
+    PHX_HIP(phx_malloc(&rank, sizeof(int32_t) * (size_t)n));
+    PHX_HIP(phx_malloc(&head, (size_t)n));
+    PHX_HIP(phx_malloc(&c2e, sizeof(int32_t) * (size_t)n));
+    const dim3 block(256), grid((unsigned)phx_div_up(n, 256));
+    k_edge_keys<<<grid, block, 0, st>>>(n, m->cells, key, idx);
+    size_t b1 = 0, b2 = 0;
+    PHX_HIP(phx_sort_pairs(nullptr, b1, key, key2, idx, idx2, (size_t)n, 0, 64, st));
+    PHX_HIP(phx_exclusive_sum(nullptr, b2, rocprim::make_transform_iterator(head, TopoU8ToI32()), rank, (size_t)n, st));
+    PHX_HIP(phx_malloc(&tmp, std::max(std::max(b1, b2), (size_t)16)));
+    PHX_HIP(phx_sort_pairs(tmp, b1, key, key2, idx, idx2, (size_t)n, 0, 64, st));
+    k_edge_heads<<<grid, block, 0, st>>>(n, key2, head);
+    PHX_HIP(phx_exclusive_sum(tmp, b2, rocprim::make_transform_iterator(head, TopoU8ToI32()), rank, (size_t)n, st));
+    k_edge_fill<<<grid, block, 0, st>>>(n, head, rank, idx2, c2e);
+    PHX_HIP(hipGetLastError());
+    int32_t last_rank = 0;
+    uint8_t last_head = 0;
+    const phx_rb_item items[2] = {{rank + (n - 1), (int)sizeof(int32_t), &last_rank}, {head + (n - 1), 1, &last_head}};
+    PHX_CHECK(phx_read_back(st, items, 2));
+    m->ne = (int64_t)last_rank + last_head;
+    return PHX_OK;
+  };
+  const int rc = run();
+  if (rc == PHX_OK) { m->c2e = c2e; c2e = nullptr; }
+  release();
+  return rc;
+}
+
 int phx_mesh_build_edges(phx_mesh *m) {
   if (m->edges) return PHX_OK;
   PHX_REQUIRE(m->cell_type == PHX_TRIANGLE || m->cell_type == PHX_TETRAHEDRON,
@@ -1045,29 +1117,9 @@ int phx_mesh_build_edges(phx_mesh *m) {
     PHX_HIP(phx_malloc(&m->c2e, sizeof(int32_t) * (size_t)m->nc * 6));
     k_box_c2e<<<grid, block, 0, m->stream>>>(E, m->nc, m->c2e);
   } else {
-    // unstructured tetrahedra: number the edges by the rank of their sorted vertex pair (host)
-    std::vector<int32_t> cells((size_t)m->nc * 4);
-    PHX_HIP(hipMemcpy(cells.data(), m->cells, cells.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    const int te[6][2] = {{2, 3}, {1, 3}, {1, 2}, {0, 3}, {0, 2}, {0, 1}};
-    struct Rec { int32_t a, b; int64_t slot; };
-    std::vector<Rec> recs((size_t)m->nc * 6);
-    for (int64_t c = 0; c < m->nc; ++c)
-      for (int k = 0; k < 6; ++k) {
-        const int32_t va = cells[c * 4 + te[k][0]], vb = cells[c * 4 + te[k][1]];
-        recs[c * 6 + k] = {std::min(va, vb), std::max(va, vb), c * 6 + k};
-      }
-    std::sort(recs.begin(), recs.end(), [](const Rec &x, const Rec &y) {
-      return x.a != y.a ? x.a < y.a : (x.b != y.b ? x.b < y.b : x.slot < y.slot);
-    });
-    std::vector<int32_t> c2e((size_t)m->nc * 6);
-    int64_t ne = 0;
-    for (size_t i = 0; i < recs.size(); ++i) {
-      if (i > 0 && (recs[i].a != recs[i - 1].a || recs[i].b != recs[i - 1].b)) ++ne;
-      c2e[recs[i].slot] = (int32_t)ne;
-    }
-    m->ne = recs.empty() ? 0 : ne + 1;
-    PHX_HIP(phx_malloc(&m->c2e, sizeof(int32_t) * c2e.size()));
-    PHX_HIP(hipMemcpy(m->c2e, c2e.data(), sizeof(int32_t) * c2e.size(), hipMemcpyHostToDevice));
+    // unstructured tetrahedra: number the edges by the rank of their sorted vertex pair -- one radix sort of the
+    // (cell, local edge) slots on the device, no mesh array leaves it (as phx_topology_build_device numbers the facets)
+    PHX_CHECK(build_edges_device(m));
   }
   PHX_HIP(phx_malloc(&m->edges, sizeof(int32_t) * 2 * (size_t)m->ne));
   k_edge_vertices<<<grid, block, 0, m->stream>>>(m->nc, m->ci.nvpc, m->cell_type == PHX_TETRAHEDRON ? 6 : 3,

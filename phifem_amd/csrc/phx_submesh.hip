@@ -4,6 +4,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
 #include <vector>
 
 #include "phx_common.h"
@@ -165,3 +166,4 @@ extern "C" int phx_submesh_maps(phx_mesh *sub, int32_t *c_map, int32_t *v_map) {
 }
 
 #include "phx_partition.inc.hip"
+#include "phx_refine.inc.hip"

@@ -235,6 +235,10 @@ class Mesh:
             parts.append(((x[fv[:, 0]] + x[fv[:, 1]]) + x[fv[:, 2]]) / 3.0)
         return np.ascontiguousarray(np.concatenate(parts, axis=0))
 
+    def refine(self):
+        """Uniform regular refinement (`phifem_amd.refine`)."""
+        return refine(self)
+
     def cell_tag_values(self):
         return self._get(L.ARR_CELL_TAGS, (self.nc,), np.int32)
 
@@ -248,7 +252,7 @@ class Mesh:
         t = (C.c_double * 8)()
         L.check(L.lib.phx_last_timings(self._h, t))
         return {"tag_cells": t[0], "tag_facets": t[1], "assemble": t[2], "solve": t[3],
-                "spmv_avg": t[4]}
+                "spmv_avg": t[4], "refine_kernels": t[6], "refine_create": t[7]}
 
 
 def create_box(lo, hi, n, device=0, offset=None, n_global=None):
@@ -285,3 +289,54 @@ def create_rectangle(bbox, n, device=0, cell_type="triangle"):
     v0 = (j * (nx + 1) + i).reshape(-1)
     cells = np.stack([v0, v0 + 1, v0 + nx + 1, v0 + nx + 2], axis=1).astype(np.int32)
     return Mesh.from_arrays("quadrilateral", x, cells, device=device)
+
+
+def refine(mesh):
+    """Uniform regular refinement on the device (dolfinx.mesh.refine(mesh)[0], demo/interface-elasticity/main.py:390):
+    every triangle into 4, every tetrahedron into 8 (Bey's rule on the stored vertex order), every quadrilateral
+    into 4.  The fine vertices are `mesh.lagrange_dof_points(2)` in that order, child k of cell c is fine cell
+    nchild * c + k (include/phifem_hip.h states the child tables).  The result is an ordinary untagged mesh --
+    `parent` stays None, it is no sub-mesh -- that carries `fine.coarse` (the mesh it came from, kept alive) and
+    `fine.nchild`."""
+    h = C.c_void_p()
+    L.check(L.lib.phx_mesh_refine(mesh._h, C.byref(h)))
+    fine = Mesh(h, device=mesh.device)
+    fine.coarse = mesh
+    fine.nchild = fine.nc // mesh.nc
+    return fine
+
+
+def prolongate(fine, values, degree=1):
+    """The Lagrange function of `degree` given by `values` on `fine.coarse`, expressed on `fine` (the spaces are nested:
+    the same function).  `values`: a NodalFunction (its degree is used), a numpy array or a tensor on the mesh's GPU,
+    of shape (ndofs,) or (ncomp, ndofs) in the layout `solve()` returns; the result is of the same kind and shape on
+    the fine mesh.  Degree 1 on all cell types, degree 2 on simplices."""
+    from .mesh_scripts import NodalFunction
+    coarse = getattr(fine, "coarse", None)
+    if coarse is None:
+        raise ValueError("prolongate: the mesh was not produced by refine()")
+    if isinstance(values, NodalFunction):
+        return NodalFunction(prolongate(fine, values.values, values.degree), values.degree)
+    if degree not in (1, 2) or (degree == 2 and coarse.cell_type == "quadrilateral"):
+        raise NotImplementedError("prolongation: degree 1 on every cell type, degree 2 on simplices")
+    nin, nout = coarse.lagrange_ndofs(degree), fine.lagrange_ndofs(degree)
+    is_tensor = hasattr(values, "data_ptr")
+    if is_tensor:
+        import torch
+        if not values.is_cuda or values.device.index != fine.device:
+            raise ValueError("prolongate: a tensor has to live on the mesh's GPU")
+        v = values.to(torch.float64).contiguous()
+    else:
+        v = np.ascontiguousarray(values, dtype=np.float64)
+    shape = tuple(v.shape)
+    if len(shape) not in (1, 2) or shape[-1] != nin:
+        raise ValueError(f"prolongate: expected {nin} values per component, got shape {shape}")
+    ncomp = 1 if len(shape) == 1 else shape[0]
+    oshape = shape[:-1] + (nout,)
+    if ncomp == 0:
+        raise ValueError("prolongate: no component")
+    out = torch.empty(oshape, dtype=torch.float64, device=v.device) if is_tensor else np.empty(oshape)
+    pi, li = L.ptr(v)
+    po, lo = L.ptr(out)
+    L.check(L.lib.phx_prolongate(coarse._h, fine._h, degree, ncomp, pi, li, po, lo))
+    return out

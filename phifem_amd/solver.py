@@ -64,7 +64,8 @@ class PhiFEMSolver:
         reported by a RuntimeWarning and `stats["coarse_reason"]`.
 
         deterministic=True (PHX_OPT_DETERMINISTIC): bit-reproducible assembly (degree 2, and degree 1 on meshes that
-        are not Kuhn boxes: the element kernels run twice and accumulate exactly) and Krylov dot products -- the same matrix bits, iteration count and solution
+        are not GENERATED Kuhn boxes -- a caller-supplied Kuhn box is then assembled in its own numbering instead of on
+        the generated box behind it: the element kernels run twice and accumulate exactly) and Krylov dot products -- the same matrix bits, iteration count and solution
         on every run; costs one more pass of the element kernels.
 
         mesh: a tagged `phifem_amd.Mesh` (box mode) or the sub-mesh returned by
