@@ -354,6 +354,53 @@ int phx_prolongate(phx_mesh *coarse, phx_mesh *fine, int degree, int ncomp, cons
                    double *out, int loc_out);
 int phx_refine_tables(int cell_type, int32_t *children, int *nchild, double *p2_weights);
 
+/* --- point location and evaluation of Lagrange functions at arbitrary points -----------------
+ * Stands in for dolfinx's Function.eval with a bounding-box tree and for interpolate_nonmatching;
+ * tests/locate_ref.py restates the rules in numpy.
+ *
+ * Reference coordinates of a point in a cell: simplices lambda_1 .. lambda_d of the STORED vertex order (lambda_0 =
+ * 1 - sum); axis-parallel rectangles (xi, eta) in tensor-product order.  A cell holds a point when every barycentric
+ * coordinate is >= -tol (rectangles: xi, eta in [-tol, 1 + tol]).
+ *
+ * phx_locate_points: pts[npts][gdim] at `loc` -> cells_out[npts] (-1: no cell holds the point) and
+ * xref_out[npts][tdim] (zeros where the cell is -1; callers must not rely on that) at loc_out.
+ *   Generated boxes (phx_mesh_create_box, slabs included) take a CLOSED FORM: cube = clamped floor((x - lo) / h)
+ *   corrected against the lattice planes, simplex = the ordering of the local coordinates, cell id = the generator's
+ *   numbering.  No search structure is built, no connectivity is read.  Tie rules: a point on a lattice plane belongs
+ *   to the cube above it, on the upper faces of the box to the last cube; among equal local coordinates the lower axis
+ *   goes first (the lowest-numbered simplex of that cube that holds the point).
+ *   Every other mesh (rectangles included) is searched through BINS: a uniform grid over the bounding box with about
+ *   one bin per cell, (bin, cell) pairs built as count -> scan -> fill with integer atomics and 64-bit offsets.  When the
+ *   pairs exceed 16 nc the bins per axis are halved and the count runs again (deterministic).  The structure belongs to
+ *   the mesh: built on first use on the mesh's stream (again when a call asks for a larger tol), freed with the mesh.
+ *   DETERMINISM RULE: of all cells that hold the point the one with the SMALLEST cell index wins; the result depends
+ *   neither on the fill order of the bins nor on the order of the points.
+ *   PHX_ERR_VALUE: tol < 0; PHX_ERR_NOT_IMPLEMENTED: a quadrilateral that is no axis-parallel rectangle in
+ *   tensor-product order.
+ *
+ * phx_eval_points: values[ncomp][ndofs(degree)] at loc_v (the layout phx_solve returns per field), cells[npts] and
+ * xref[npts][tdim] at loc_p as phx_locate_points wrote them -> out[ncomp][npts] and, with want_grad, the physical
+ * gradient in that cell grad_out[ncomp][npts][gdim], at loc_out; `fill` where the cell is -1 (or out of range).
+ *   degree 1: triangles, tetrahedra, rectangles (Q1); degree 2: simplices, vertices then the edges of PHX_ARR_C2E.
+ *   One lane per point; sums run in ascending local DoF order, so results repeat bit for bit.
+ *   PHX_ERR_NOT_IMPLEMENTED: degree 2 on quadrilaterals, degree 3, non-rectangular quadrilaterals.
+ *
+ * Both calls release every temporary on failure (phx_pool_stats live bytes return to where they were); what stays
+ * after a successful phx_locate_points is the locator, reported by phx_locator_info.
+ *
+ * [host] phx_locator_info: info[8] = {path: 1 closed form / 2 bins, bins along x, y, z, stored (bin, cell) pairs,
+ * device bytes held, halvings of the resolution, 1 when the bins are built}; a closed-form mesh reports zeros after
+ * the path.
+ * [host] phx_locate_timings: t[3] = wall seconds of the last locator build, of the last phx_locate_points without
+ * the build, and of the last phx_eval_points (each call ends with the stream synchronised). */
+int phx_locate_points(phx_mesh *m, int64_t npts, const double *pts, int loc, double tol, int32_t *cells_out,
+                      double *xref_out, int loc_out);
+int phx_eval_points(phx_mesh *m, int degree, int ncomp, const double *values, int loc_v, int64_t npts,
+                    const int32_t *cells, const double *xref, int loc_p, int want_grad, double fill, double *out,
+                    double *grad_out, int loc_out);
+int phx_locator_info(const phx_mesh *m, int64_t *info);
+int phx_locate_timings(const phx_mesh *m, double *t);
+
 /* ------------------------------------------------------------------ assembly --------- */
 /* Weak-Dirichlet phi-FEM Poisson, mixed (u,p) in P1 x P1: bilinear form
  * demo/weak-dirichlet/flower/main.py:112-135 + assemble_matrix :137-139, linear form :142-151 +

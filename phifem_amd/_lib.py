@@ -106,6 +106,10 @@ SIGNATURES = {
     "phx_mesh_refine": ([_vp, C.POINTER(_vp)], _i),
     "phx_prolongate": ([_vp, _vp, _i, _i, _vp, _i, _vp, _i], _i),
     "phx_refine_tables": ([_i, _vp, _pi, _vp], _i),
+    "phx_locate_points": ([_vp, _i64, _vp, _i, _d, _vp, _vp, _i], _i),
+    "phx_eval_points": ([_vp, _i, _i, _vp, _i, _i64, _vp, _vp, _i, _i, _d, _vp, _vp, _i], _i),
+    "phx_locator_info": ([_vp, _pi64], _i),
+    "phx_locate_timings": ([_vp, _pd], _i),
     "phx_assemble_poisson_wd": ([_vp, _d, _d, _vp, _vp, _vp, _i, C.POINTER(_vp)], _i),
     "phx_assemble_poisson_wd_p2": ([_vp, _d, _d, _vp, _i, _vp, _vp, _i, C.POINTER(_vp)], _i),
     "phx_assemble_poisson_sd": ([_vp, _d, _i, _vp, _i, _vp, _i, C.POINTER(_vp)], _i),

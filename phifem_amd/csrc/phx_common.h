@@ -109,6 +109,7 @@ struct phx_mesh {
   double box_h[3] = {0.0, 0.0, 0.0};  // exact lattice spacing (hi - lo) / n_global per axis
   int64_t box_off[3] = {0, 0, 0};     // cube offset of this (slab of a) box in the global box
   int64_t box_nglob[3] = {0, 0, 0};   // cubes per axis of the global box
+  double box_lo[3] = {0.0, 0.0, 0.0}, box_hi[3] = {0.0, 0.0, 0.0};   // corners of the GLOBAL box (generated boxes only)
   int64_t *v2c_ptr = nullptr;  // [nv+1]
   int32_t *v2c_idx = nullptr;  // [nc*nvpc]
   bool is_box = false;
@@ -144,6 +145,11 @@ struct phx_mesh {
   int32_t *v2lat = nullptr;   // [nv]          sub-mesh vertex -> parent lattice vertex
   int32_t *lat2v = nullptr;   // [parent nv]   parent lattice vertex -> sub-mesh vertex or -1
   double timings[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // point location (phx_locate.inc.hip): the bins of a mesh that is no generated box, built on first use on the mesh's
+  // stream and freed with the mesh; wall seconds of the last locator build / phx_locate_points / phx_eval_points
+  struct phx_locator *locator = nullptr;
+  int rect_checked = 0;            // quadrilaterals: 1 once every cell was seen to be an axis-parallel rectangle
+  double loc_timings[3] = {0, 0, 0};
   bool own_stream = true;
   int profile_spmv = 0;
   int spmv_xcd_group = 0;          // PHX_OPT_SPMV_XCD_GROUP
@@ -363,3 +369,5 @@ struct phx_blockjac;
 void phx_blockjac_destroy(phx_blockjac *b);         // phx_solve.hip
 struct phx_coarse;
 void phx_coarse_destroy(phx_coarse *c);             // phx_solve.hip
+struct phx_locator;
+void phx_locator_destroy(phx_locator *l);           // phx_submesh.hip (phx_locate.inc.hip)

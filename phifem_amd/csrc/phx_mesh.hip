@@ -916,6 +916,7 @@ extern "C" int phx_mesh_create_box(int gdim, const double *lo, const double *hi,
   for (int a = 0; a < 3; ++a) m->box_off[a] = a < gdim ? b.off[a] : 0;
   for (int a = 0; a < 3; ++a) m->box_nglob[a] = a < gdim ? b.nglob[a] : 1;
   for (int a = 0; a < gdim; ++a) m->box_h[a] = (b.hi[a] - b.lo[a]) / (double)b.nglob[a];
+  for (int a = 0; a < gdim; ++a) { m->box_lo[a] = b.lo[a]; m->box_hi[a] = b.hi[a]; }
   PHX_HIP(phx_malloc(&m->x, sizeof(double) * (size_t)nv * gdim));
   PHX_HIP(phx_malloc(&m->cells, sizeof(int32_t) * (size_t)nc * (gdim + 1)));
   PHX_HIP(phx_malloc(&m->c2f, sizeof(int32_t) * (size_t)nc * (gdim + 1)));
@@ -1149,6 +1150,7 @@ extern "C" int phx_mesh_destroy(phx_mesh *m) {
   (void)phx_free(m->v2lat); (void)phx_free(m->lat2v);
   (void)phx_free(m->in_cmap); (void)phx_free(m->in_fmap);
   if (m->inner) { phx_mesh_destroy(m->inner); m->inner = nullptr; }
+  phx_locator_destroy(m->locator);
   if (m->scal_h) (void)hipHostFree(m->scal_h);
   for (auto &pe : m->prof_ev) for (auto &e : pe) (void)hipEventDestroy(e);
   for (int w = 0; w < 2; ++w) (void)phx_free(m->sel_counts[w]);

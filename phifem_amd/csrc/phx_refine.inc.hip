@@ -177,6 +177,7 @@ struct DevTemps {
     if (e == hipSuccess) p.push_back((void *)*q);
     return e;
   }
+  template <typename T> hipError_t alloc(T **q, size_t bytes) { return get(q, bytes); }   // phx_q1rect.inc.hip's name
   ~DevTemps() { for (void *q : p) (void)phx_free(q); }
 };
 

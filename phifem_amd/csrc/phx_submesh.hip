@@ -1,6 +1,8 @@
 // Sub-mesh of Omega_h = cells tagged 1 or 2, with transferred tags.
 // Replaces dolfinx.mesh.create_submesh [3P] + _transfer_tags, src/phifem/mesh_scripts.py:217-281,
 // 636-645: device-resident since round 2.
+#include <math.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -167,3 +169,5 @@ extern "C" int phx_submesh_maps(phx_mesh *sub, int32_t *c_map, int32_t *v_map) {
 
 #include "phx_partition.inc.hip"
 #include "phx_refine.inc.hip"
+#include "phx_q1rect.inc.hip"   // rect_load and the rectangle flag, for phx_locate.inc.hip
+#include "phx_locate.inc.hip"

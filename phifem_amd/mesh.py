@@ -251,8 +251,11 @@ class Mesh:
     def timings(self):
         t = (C.c_double * 8)()
         L.check(L.lib.phx_last_timings(self._h, t))
+        tl = (C.c_double * 3)()      # point location and evaluation (phifem_amd.evaluate): wall seconds of the last calls
+        L.check(L.lib.phx_locate_timings(self._h, tl))
         return {"tag_cells": t[0], "tag_facets": t[1], "assemble": t[2], "solve": t[3],
-                "spmv_avg": t[4], "refine_kernels": t[6], "refine_create": t[7]}
+                "spmv_avg": t[4], "refine_kernels": t[6], "refine_create": t[7],
+                "locate_build": tl[0], "locate": tl[1], "evaluate": tl[2]}
 
 
 def create_box(lo, hi, n, device=0, offset=None, n_global=None):
