@@ -617,6 +617,40 @@ int phx_reference_nodes(int gdim, int degree, double *bary, int *n_nodes);
 int phx_cell_errors(phx_mesh *m, int ncomp, int degree_h, const double *u_h, const double *u_ref,
                     int64_t ncells, const int32_t *cell_list, int loc, double *l2_local,
                     double *h10_local, double *norms);
+/* --- a posteriori error indicators and Doerfler marking ----------------------------------------
+ * The reference has no counterpart (dolfinx users write the residual forms in UFL); tests/estimate_ref.py restates
+ * the definition in numpy.
+ *
+ * phx_estimate_poisson_wd: residual indicator of the weak-Dirichlet Poisson scheme (phx_assemble_poisson_wd*) on the
+ * cell tags currently held by the mesh.  u, p, phi, f, u_D: nodal arrays of ONE degree at loc_in, [nv] (degree 1) or
+ * [nv + ne] (degree 2, vertices then the edges of PHX_ARR_C2E), the layout phx_solve returns per field.  With h_T the
+ * cell diameter of the assemblers and Omega_h the cells tagged 1 or 2, for T in Omega_h
+ *   R_T = h_T^2 int_T (f_h + Laplace u_h)^2
+ *   J_T = 1/2 sum over the facets F of T whose other cell T' exists and lies in Omega_h of
+ *         h_F int_F [grad u_h . n]^2,   h_F = (h_T + h_T') / 2        (cell tags and f2c only, no facet tags)
+ *   B_T = h_T^-2 int_T (u_h - phi_h p_h / h_T - u_D)^2   if T is tagged 2, else 0
+ * -> eta2_parts[3][nc] at loc_out (rows R, J, B; cells outside Omega_h exactly 0) and sums3[3] on the host, the
+ * totals of the rows.  These are the residuals of the discrete scheme's own terms: an indicator for marking and for
+ * effectivity studies, not a proven two-sided bound.
+ *   degree 1: triangles, tetrahedra, rectangles (Q1); degree 2: simplices.  Every rule is exact for its integrand.
+ *   DETERMINISM RULE: J is a gather -- a cell evaluates the jumps over its own facets, so an interior facet is
+ *   evaluated twice and nothing is added atomically; the totals are per-block partial sums folded in a fixed order.
+ *   The same inputs give the same bits on every run.
+ *   PHX_ERR_VALUE: the mesh carries no cell tags (call compute_tags_measures first), a NULL array;
+ *   PHX_ERR_NOT_IMPLEMENTED: degree 2 on quadrilaterals, degree 3, non-rectangular quadrilaterals.
+ *
+ * phx_mark_dorfler: eta2[n] at loc_in -> marked[n] (0 / 1) at loc_out and *n_marked.  Order the entries by (eta2
+ * descending, index ascending), let S_k be the inclusive sums in that order: marked are the first k* entries, k* the
+ * smallest k with S_k >= theta S_n; nothing is marked when S_n = 0.  A stable radix sort, a scan with a fixed order of
+ * additions and one mask kernel on the mesh's device and stream; nothing but n_marked returns to the host.
+ *   PHX_ERR_VALUE: theta outside (0, 1]; a negative, NaN or infinite entry.
+ *
+ * Both calls release every temporary on failure (phx_pool_stats live bytes return to where they were). */
+int phx_estimate_poisson_wd(phx_mesh *m, int degree, const double *u, const double *p, const double *phi,
+                            const double *f, const double *u_D, int loc_in, double *eta2_parts, int loc_out,
+                            double *sums3);
+int phx_mark_dorfler(phx_mesh *m, int64_t n, const double *eta2, int loc_in, double theta, uint8_t *marked,
+                     int loc_out, int64_t *n_marked);
 
 /* Times `reps` launches of the SpMV kernel with HIP events on the mesh's stream.
  * out[3] = {avg ms per launch, algorithmic bytes per launch (12 nnz + 20 n), padded bytes}. */

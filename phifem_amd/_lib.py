@@ -117,6 +117,8 @@ SIGNATURES = {
     "phx_assemble_elasticity_if": ([_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, C.POINTER(_vp)], _i),
     "phx_reference_nodes": ([_i, _i, _vp, C.POINTER(C.c_int)], _i),
     "phx_cell_errors": ([_vp, _i, _i, _vp, _vp, _i64, _vp, _i, _vp, _vp, _pd], _i),
+    "phx_estimate_poisson_wd": ([_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _pd], _i),
+    "phx_mark_dorfler": ([_vp, _i64, _vp, _i, _d, _vp, _i, _pi64], _i),
     "phx_system_destroy": ([_vp], _i),
     "phx_system_info": ([_vp, _pi64], _i),
     "phx_system_export": ([_vp, _vp, _vp, _vp, _vp, _vp], _i),

@@ -2148,3 +2148,4 @@ extern "C" int phx_system_export(phx_system *s, int64_t *rowptr, int32_t *col, d
 #include "phx_assemble_el_quad.inc.hip"
 #include "phx_assemble_wd_quad.inc.hip"
 #include "phx_errors.inc.hip"
+#include "phx_estimate.inc.hip"

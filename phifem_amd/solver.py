@@ -274,6 +274,26 @@ class PhiFEMSolver:
         nd = self.ndofs
         return w[:nd], w[nd:]
 
+    def estimate(self, w, parts=False):
+        """Residual error indicator per cell (`phifem_amd.estimate`) of the mixed solution `w` = [u, p] that `solve()`
+        returned, with the phi_h, f_h, u_D handed to the last `assemble` and the tags the mesh holds now.  All five
+        nodal functions have the solver's degree, so a degree-2 solver needs levelset_degree = 2."""
+        if getattr(self, "_keep", None) is None:
+            raise RuntimeError("estimate: call assemble() first")
+        if self.levelset_degree != self.degree:
+            raise NotImplementedError("estimate: phi_h must have the degree of u_h (levelset_degree = degree)")
+        from .estimate import estimate
+        # the data of assemble() on the side of w: the indicator is of the kind of the solution
+        if hasattr(w, "data_ptr") and w.is_cuda:
+            import torch
+            data = [a if hasattr(a, "data_ptr") and a.is_cuda else torch.as_tensor(np.asarray(a), device=w.device)
+                    for a in self._keep]
+        else:
+            w = np.asarray(w)
+            data = [a.cpu().numpy() if hasattr(a, "data_ptr") else a for a in self._keep]
+        u, p = self.split(w)
+        return estimate(self.mesh, u, p, data[0], data[1], data[2], degree=self.degree, parts=parts)
+
     def precond_info(self):
         """State of the fictitious-domain preconditioner after a solve (phx_precond_info)."""
         o = (C.c_double * 8)()
@@ -316,6 +336,10 @@ class PhiFEMSolver:
         return {"ms": o[0], "algorithmic_bytes": o[1], "padded_bytes": o[2]}
 
 
+_OTHER_RESIDUALS = ("estimate: the residual indicator covers the weak-Dirichlet Poisson scheme of PhiFEMSolver; this "
+                    "formulation has other residuals")
+
+
 class StrongDirichletSolver(PhiFEMSolver):
     """Direct ("strong Dirichlet") phi-FEM: u_h = phi_h w_h with one scalar unknown w_h -- the
     assemble -> solve -> multiply sequence of demo/strong-dirichlet/flower/main.py:83-182 over the
@@ -351,6 +375,9 @@ class StrongDirichletSolver(PhiFEMSolver):
 
     def split(self, w):
         raise NotImplementedError("one scalar field: solve() returns w_h itself")
+
+    def estimate(self, w, parts=False):
+        raise NotImplementedError(_OTHER_RESIDUALS)
 
     def solution(self, w, solution_degree=None):
         """u_h = w_h phi_h at the nodes of the solution space (main.py:172-182: both factors are
@@ -403,6 +430,9 @@ class NeumannRobinSolver(PhiFEMSolver):
         m = self.mesh
         d, nv = m.gdim, m.nv
         return w[:nv], w[nv:(1 + d) * nv].reshape(d, nv).T, w[(1 + d) * nv:]
+
+    def estimate(self, w, parts=False):
+        raise NotImplementedError(_OTHER_RESIDUALS)
 
 
 class InterfaceElasticitySolver(PhiFEMSolver):
@@ -460,6 +490,9 @@ class InterfaceElasticitySolver(PhiFEMSolver):
                                                      vp(bcv), bcv.size, L.HOST, C.byref(h)))
         self._sys = h
         return self.info()
+
+    def estimate(self, w, parts=False):
+        raise NotImplementedError(_OTHER_RESIDUALS)
 
     def blocks(self, w):
         """Split the solution: dict of (nv, d) / (nv, d, d) arrays (solution_wh.split(), main.py:291)."""
