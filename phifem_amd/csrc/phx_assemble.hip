@@ -1059,7 +1059,9 @@ static int det_alloc(phx_mesh *m, Slots &sl, int64_t nslots, int64_t nrows, bool
   if (!m->deterministic) return PHX_OK;
   // default: a fifth of the device (57.6 GB of 288: the 256^3 elasticity system needs 52 GB, the 512^3 P2 system more)
   static const double limit_gb = [] {
-    if (const char *e = getenv("PHX_DET_LIMIT_GB")) return atof(e);
+    bool set = false;
+    const double gb = phx_sw_det_limit_gb(&set);
+    if (set) return gb;
     size_t fr = 0, tot = 0;
     if (hipMemGetInfo(&fr, &tot) != hipSuccess || tot == 0) { (void)hipGetLastError(); return 48.0; }
     return 0.2 * (double)tot / 1073741824.0;
@@ -1944,8 +1946,7 @@ static int p1_fill_slots(phx_mesh *m, phx_system *s, Slots &sl, DevTemps &tmp, b
   PHX_CHECK(rhs_alloc(m, s));
   A.du = s->dof_of_vertex_u; A.dp = s->dof_of_vertex_p; A.rhs = s->rhs;
   // box slots (BoxCodes) for the stored rows of structured systems; PHX_BOX_SLOTS=0: the hashed slots (A/B aid)
-  const char *bs_env = getenv("PHX_BOX_SLOTS");
-  w.box_slots = structured && !m->export_csr && !m->deterministic && !(bs_env && atoi(bs_env) == 0);
+  w.box_slots = structured && !m->export_csr && !m->deterministic && phx_sw_box_slots();
   if (w.box_slots) {
     const BoxCodes *codes = box_codes(m->device, m->gdim);
     PHX_REQUIRE(codes != nullptr && codes->ncode <= PHX_BOX_MAXCODE, PHX_ERR_HIP, "box slot code table");

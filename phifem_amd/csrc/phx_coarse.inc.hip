@@ -312,6 +312,8 @@ k_cc_restrict_axis_split(int64_t total, int64_t inner, int64_t nfa, int ma, int 
   out[2 * t + 1] = acc[1];
 }
 // row I of Ac from the eight parts of its node: X3s[((blk m2 + ck) (m1 m0 4) + (cj m0 + ci) 4 + px 2 + py) 2 + pz]
+// The buffer holds Ac transposed in column-major order, buf[J + nc * I] = Ac[I][J]: the inverse taken in place is
+// Ac^-1 in row-major order.
 __global__ void k_cc_store_parts(int nc, int bj, int col3, CcDims g, const int32_t *__restrict__ node_of,
                                  const int32_t *__restrict__ cmap, const double *__restrict__ X3s, double *__restrict__ buf) {
   const int I = blockIdx.x * blockDim.x + threadIdx.x;
@@ -328,30 +330,6 @@ __global__ void k_cc_store_parts(int nc, int bj, int col3, CcDims g, const int32
     const int32_t J = cmap[bj * g.M + tx + (int64_t)g.m[0] * (ty + (int64_t)g.m[1] * tz)];
     if (J >= 0) buf[(int64_t)J + (int64_t)nc * I] = X3s[b0 + q];
   }
-}
-
-// column of Ac found by the probe of (block bj, colour) -- the LUMPED variant (PHX_EL_COARSE_LUMPED=1, A/B aid): row I takes the entry of the one node of that colour within
-// one coarse cell of its own node.  The buffer holds Ac TRANSPOSED in column-major order = Ac row-major ... of the
-// transpose: buf[J + nc * I] = Ac[I][J], so that the column-major inverse rocSOLVER leaves is Ac^-1 in row-major order.
-__global__ void k_cc_store_column(int nc, int bj, int col3, CcDims g, const int32_t *__restrict__ node_of,
-                                  const int32_t *__restrict__ cmap, const double *__restrict__ gc, double *__restrict__ buf) {
-  const int I = blockIdx.x * blockDim.x + threadIdx.x;
-  if (I >= nc) return;
-  const int64_t node = node_of[I] % g.M;
-  const int ci[3] = {(int)(node % g.m[0]), (int)((node / g.m[0]) % g.m[1]), (int)(node / ((int64_t)g.m[0] * g.m[1]))};
-  const int cc[3] = {col3 % 3, (col3 / 3) % 3, col3 / 9};
-  int cj[3];
-  for (int a = 0; a < 3; ++a) {
-    int found = -1;
-    for (int dlt = -1; dlt <= 1; ++dlt) {
-      const int q = ci[a] + dlt;
-      if (q >= 0 && q < g.m[a] && q % 3 == cc[a]) found = q;
-    }
-    if (found < 0) return;
-    cj[a] = found;
-  }
-  const int32_t J = cmap[bj * g.M + cj[0] + (int64_t)g.m[0] * (cj[1] + (int64_t)g.m[1] * cj[2])];
-  if (J >= 0) buf[(int64_t)J + (int64_t)nc * I] = gc[I];
 }
 
 // zc = Ainv gc, one wavefront per row (fixed summation order)
@@ -657,8 +635,7 @@ static int coarse_build(phx_system *s, int nblk, phx_coarse **out, const CcReduc
   *out = nullptr;
   phx_mesh *m = s->mesh;
   hipStream_t st = m->stream;
-  static const int env_req = getenv("PHX_EL_COARSE") ? atoi(getenv("PHX_EL_COARSE")) : -2;   // A/B aid: overrides the option
-  const int req = env_req != -2 ? env_req : m->el_coarse;   // -1: automatic, 0: off, > 0: the ratio H / h
+  const int req = m->el_coarse;   // PHX_OPT_EL_COARSE: -1 automatic, 0 off, > 0 the ratio H / h
   // decided from numbers every rank shares
   if (req == 0 || !m->is_box || m->is_submesh) return PHX_OK;
   if (!reduce && (!s->rowptr || s->n == 0)) return PHX_OK;
@@ -715,7 +692,7 @@ static int coarse_build(phx_system *s, int nblk, phx_coarse **out, const CcReduc
   for (size_t q = 0; q < hused.size(); ++q)
     if (hused[q] > 0.0) { hmap[q] = (int32_t)hnode.size(); hnode.push_back((int32_t)q); }
   c->nc = (int)hnode.size();
-  static const int nc_max = getenv("PHX_EL_COARSE_MAX") ? atoi(getenv("PHX_EL_COARSE_MAX")) : 24000;
+  const int nc_max = 24000;   // coarse DoFs the dense inverse is asked to take
   if (c->nc == 0 || c->nc > nc_max) { coarse_free(c); return PHX_OK; }   // the same numbers on every rank
   const int nc = c->nc;
   c->nc_blk[0] = nc;
@@ -726,8 +703,6 @@ static int coarse_build(phx_system *s, int nblk, phx_coarse **out, const CcReduc
     (void)phx_free(wv); (void)phx_free(tv); (void)phx_free(X1s); (void)phx_free(X2s); (void)phx_free(X3s); (void)phx_free(T);
     (void)phx_free(f32); (void)phx_free(vflag);
   };
-  static const bool lumped = getenv("PHX_EL_COARSE_LUMPED") && atoi(getenv("PHX_EL_COARSE_LUMPED")) != 0;   // A/B aids, one rank
-  static const bool by_spmv = getenv("PHX_EL_COARSE_SPMV") && atoi(getenv("PHX_EL_COARSE_SPMV")) != 0;
   bool mem_ok = phx_malloc(&c->node_of, sizeof(int32_t) * (size_t)nc) == hipSuccess && phx_malloc(&c->Ainv, sizeof(double) * (size_t)nc * nc) == hipSuccess &&
                 phx_malloc(&c->X1, sizeof(double) * (size_t)t1) == hipSuccess && phx_malloc(&c->X2, sizeof(double) * (size_t)t2) == hipSuccess &&
                 phx_malloc(&c->X3, sizeof(double) * (size_t)t3) == hipSuccess && phx_malloc(&c->gc, sizeof(double) * (size_t)nc) == hipSuccess &&
@@ -736,7 +711,7 @@ static int coarse_build(phx_system *s, int nblk, phx_coarse **out, const CcReduc
                 phx_malloc(&X3s, sizeof(double) * (size_t)t3 * 8) == hipSuccess;
   // nine colours of a block from one pass over the CSR copy when their images fit (nine vectors in full lattice order:
   // 7 GB at 256^3), else -- one rank only -- one product with the solver's SpMV per (block, colour)
-  if (mem_ok && rows && !(lumped && !reduce) && !(by_spmv && !reduce) && (int64_t)c->nblk_u * nv < INT32_MAX && s->nent < INT32_MAX) {
+  if (mem_ok && rows && (int64_t)c->nblk_u * nv < INT32_MAX && s->nent < INT32_MAX) {
     size_t fr = 0, tot = 0;
     (void)hipMemGetInfo(&fr, &tot);
     const size_t need = sizeof(double) * 9 * (size_t)tf + sizeof(int32_t) * (size_t)n;
@@ -793,10 +768,7 @@ static int coarse_build(phx_system *s, int nblk, phx_coarse **out, const CcReduc
       k_cc_probe<<<cc_grid(nv), dim3(256), 0, st>>>(nv, bj, col, g, c->cpos, c->dpos, wv);
       rc = launch_spmv(s, s->sell_val, wv, tv, 0, nullptr, nullptr, nullptr, 0);
       ++c->probes;
-      if (rc == PHX_OK && lumped) {
-        rc = coarse_restrict(s, c, tv);
-        if (rc == PHX_OK) k_cc_store_column<<<cc_grid(nc), dim3(256), 0, st>>>(nc, bj, col, g, c->node_of, c->cmap, c->gc, c->Ainv);
-      } else if (rc == PHX_OK) {
+      if (rc == PHX_OK) {
         rc = coarse_restrict_split(s, c, col, tv, false, X1s, X2s, X3s);
         if (rc == PHX_OK) k_cc_store_parts<<<cc_grid(nc), dim3(256), 0, st>>>(nc, bj, col, g, c->node_of, c->cmap, X3s, c->Ainv);
       }

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/phifem_hip.h"
+#include "phx_switches.h"
 
 #define PHX_MAX_PTS 40   // detection points per cell (tet degree 4 has 34)
 #define PHX_MAX_VPC 4

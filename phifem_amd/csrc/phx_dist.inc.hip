@@ -31,7 +31,7 @@ static int nccl_bind() {
   void *h = nullptr;
   // PHX_RCCL_LIB: an explicit library path (the tests load a host-staged stand-in that lets several ranks share
   // the one GPU of the test box, which RCCL itself refuses)
-  const char *names[] = {getenv("PHX_RCCL_LIB"), "librccl.so.1", "librccl.so", "libnccl.so.2"};
+  const char *names[] = {phx_sw_rccl_lib(), "librccl.so.1", "librccl.so", "libnccl.so.2"};
   for (const char *n : names) { if (!n || !*n) continue; h = dlopen(n, RTLD_NOW | RTLD_GLOBAL); if (h) break; }
   PHX_REQUIRE(h != nullptr, PHX_ERR_HIP, "librccl not found: %s", dlerror());
 #define BIND(field, sym) \
@@ -53,7 +53,7 @@ static int nccl_bind() {
     // stderr when PHX_RCCL_LIB substituted the collective library, so that a stand-in is never bound silently.
     Dl_info di;
     if (dladdr((void *)g_nccl.AllReduce, &di) && di.dli_fname) snprintf(g_nccl_path, sizeof(g_nccl_path), "%s", di.dli_fname);
-    const char *e = getenv("PHX_RCCL_LIB");
+    const char *e = phx_sw_rccl_lib();
     if (e && *e) fprintf(stderr, "phifem_hip: collective library taken from PHX_RCCL_LIB: %s\n", g_nccl_path[0] ? g_nccl_path : e);
   }
   g_nccl.ok = true;
@@ -135,8 +135,7 @@ extern "C" int phx_comm_destroy(phx_comm *c) {
 // 1 when the halo exchanges of this communicator run overlapped with the SpMV (self-test passed and PHX_DIST_OVERLAP != 0)
 extern "C" int phx_comm_overlap(const phx_comm *c, int *out) {
   PHX_REQUIRE(c != nullptr && out != nullptr, PHX_ERR_VALUE, "phx_comm_overlap: null argument");
-  const bool env = !(getenv("PHX_DIST_OVERLAP") && atoi(getenv("PHX_DIST_OVERLAP")) == 0);
-  *out = (env && c->overlap_ok) ? 1 : 0;
+  *out = (phx_sw_dist_overlap() && c->overlap_ok) ? 1 : 0;
   return PHX_OK;
 }
 
@@ -197,8 +196,7 @@ static int halo_setup(HaloSpec &H, const phx_comm *c, int npeers, const int *pee
     H.send_idx.push_back(idx[2 * p]); H.recv_idx.push_back(idx[2 * p + 1]);
     H.tot_send += counts[2 * p]; H.tot_recv += counts[2 * p + 1];
   }
-  static const bool fused_env = !(getenv("PHX_DIST_FUSED_PACK") && atoi(getenv("PHX_DIST_FUSED_PACK")) == 0);
-  H.fused = npeers > 2 && fused_env;
+  H.fused = npeers > 2 && phx_sw_dist_fused_pack();
   // (+ one entry per peer: every slice has an address of its own, also an empty one)
   PHX_HIP(phx_malloc(&H.send_arena, sizeof(double) * (size_t)(H.tot_send + npeers + 1)));
   PHX_HIP(phx_malloc(&H.recv_arena, sizeof(double) * (size_t)(H.tot_recv + npeers + 1)));
@@ -294,12 +292,8 @@ static int allreduce_R(phx_system *s, phx_comm *c, int lo, int hi) {
 
 // Watchdog of the host synchronisations inside the distributed loop: a collective whose partner never arrives would
 // otherwise block in hipStreamSynchronize for ever.  PHX_DIST_TIMEOUT_S (default 300; 0 = wait without limit).
-static double dist_timeout_s() {
-  static const double t = getenv("PHX_DIST_TIMEOUT_S") ? atof(getenv("PHX_DIST_TIMEOUT_S")) : 300.0;   // (the Python side: dist_solver.dist_timeout_s)
-  return t;
-}
 static int stream_sync_watchdog(hipStream_t st, const char *what) {
-  const double limit = dist_timeout_s();
+  const double limit = phx_sw_dist_timeout_s();
   if (!(limit > 0.0)) { PHX_HIP(hipStreamSynchronize(st)); return PHX_OK; }
   struct timespec t0, t1;
   clock_gettime(CLOCK_MONOTONIC, &t0);
@@ -351,7 +345,7 @@ extern "C" int phx_solve_distributed(phx_system *s, phx_comm *c, int npeers, con
     const int rc = halo_setup(H, c, npeers, peers, counts, idx, st);
     if (rc != PHX_OK) { (void)hipStreamSynchronize(st); halo_free(H); return rc; }
   }
-  static const bool overlap_env = !(getenv("PHX_DIST_OVERLAP") && atoi(getenv("PHX_DIST_OVERLAP")) == 0);
+  static const bool overlap_env = phx_sw_dist_overlap();   // latched by the first distributed solve
   // a local matter: sends and receives pair up whatever stream each side issues them on
   const bool overlap = overlap_env && c->overlap_ok && c->nranks > 1 && npeers > 0 && c->cs != nullptr;
   auto body = [&]() -> int {

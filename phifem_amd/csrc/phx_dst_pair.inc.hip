@@ -1,5 +1,5 @@
 // Sine-transform passes for the LONG f64 lengths (384, 768, 1024): ONE WAVEFRONT PER PAIR of lines -- included by
-// phx_precond.inc.hip behind phx_dst_wave.inc.hip.  (PHX_DST_OLD=1: the generic kernels k_dst_x / k_dst_s, the A/B reference.)
+// phx_precond.inc.hip behind phx_dst_wave.inc.hip.  (The generic kernels k_dst_x / k_dst_s serve the shapes dst_pair_fast refuses.)
 //
 // Why: the kernels of round 3 (k_dst_xl / k_dst_yl, docs/HISTORY.md) spread a pair over L / 8 threads = 1.5 wavefronts (L = 768), so every Stockham stage and every
 // step of the prefix sum met at a BLOCK barrier: eleven barriers over twelve wavefronts per tile, 15 us of transform time per
@@ -216,12 +216,12 @@ k_dst_yp(BoxGrid g, DstPlan P, double *__restrict__ G, const int2 *__restrict__ 
       const int2 iv = row_any[outer];
       const int rlo = iv.y >= iv.x ? iv.x : (1 << 30);
       const uint32_t span = iv.y >= iv.x ? (uint32_t)(iv.y - iv.x) : 0u;
-      if ((dir & 3) == 1) { T.lrlo = rlo; T.lspan = span; } else { T.srlo = rlo; T.sspan = span; }
+      if (dir == 1) { T.lrlo = rlo; T.lspan = span; } else { T.srlo = rlo; T.sspan = span; }
     }
     return T;
   };
   auto issue_loads = [&](const Tile &T) {
-    const bool colok = tcol < T.ncols && !(dir & 0x200);
+    const bool colok = tcol < T.ncols;
     const uint32_t offa = colok ? (uint32_t)(tcol * 8 + row0 * pitch8) : PHX_BUF_OOB;
     const uint32_t offb = colok ? (uint32_t)(tcol * 8 + (LL - 2 - row0) * pitch8) : 0xc0000000u;
     const uint32_t da = (uint32_t)(row0 - T.lrlo), db = (uint32_t)(LL - 2 - row0 - T.lrlo);
@@ -255,7 +255,7 @@ k_dst_yp(BoxGrid g, DstPlan P, double *__restrict__ G, const int2 *__restrict__ 
     if (fold_in && row0 == 0) wcol[0] = 0.0;
   };
   auto issue_stores = [&](const Tile &T) {
-    const bool colok = tcol < T.ncols && !(dir & 0x200);
+    const bool colok = tcol < T.ncols;
     const uint32_t offa = colok ? (uint32_t)(tcol * 8 + row0 * pitch8) : PHX_BUF_OOB;
     const uint32_t offb = colok ? (uint32_t)(tcol * 8 + (LL - 2 - row0) * pitch8) : 0xc0000000u;
     const uint32_t da = (uint32_t)(row0 - T.srlo), db = (uint32_t)(LL - 2 - row0 - T.srlo);
@@ -283,7 +283,7 @@ k_dst_yp(BoxGrid g, DstPlan P, double *__restrict__ G, const int2 *__restrict__ 
   __syncthreads();
   for (;;) {
     // a wavefront whose pair(s) lie beyond the tile's columns transforms nothing (wave-uniform)
-    if (2 * (pr - (S::TP == 32 ? (pr & 1) : 0)) < cur.ncols && !(dir & 0x100)) {
+    if (2 * (pr - (S::TP == 32 ? (pr & 1) : 0)) < cur.ncols) {
       int tt = t;
       asm volatile("" : "+v"(tt));
       pair_core<LL, S::TP>(w, tt, tw);
@@ -470,8 +470,6 @@ static int dst_pair_grid(int64_t nwork) {
   return (int)std::min<int64_t>(nwork, (int64_t)per_cu * 256);
 }
 static bool dst_pair_fast(const BoxGrid &g, const DstPlan &p, int64_t nvec) {
-  static const bool off = getenv("PHX_DST_OLD") != nullptr || getenv("PHX_DST_GENERIC") != nullptr;
-  if (off) return false;
   const int64_t lat = g.plane * g.m[2];
   if (g.plane != g.pitch * g.m[1] || lat * 8 >= (int64_t)PHX_BUF_OOB || nvec * 8 >= (int64_t)PHX_BUF_OOB) return false;
   return p.L == 384 || p.L == 768 || p.L == 1024;

@@ -1,6 +1,6 @@
 // Sine-transform passes of the lattice preconditioner, f64, for the transform lengths whose pairs live inside one
 // wavefront (L = 192, 256, 512) -- included by phx_precond.inc.hip behind k_dst_x / k_dst_s, which stay for every
-// other length, for f32 and as the A/B reference (PHX_DST_OLD=1).
+// other length, for f32 and for the shapes dst_wave_fast refuses.
 //
 // Same algorithm and the same LDS layout as k_dst_x / k_dst_s (two real lines per complex FFT of length L, Stockham
 // stages in LDS, dst_core); what differs is everything around the transform.  The instruction stream of the old
@@ -147,7 +147,7 @@ k_dst_yw(BoxGrid g, DstPlan P, double *__restrict__ G, const int2 *__restrict__ 
   __syncthreads();
   {
     const int pr = tid / S::SLOT, t = tid % S::SLOT;
-    if (2 * pr < ncols && t < S::TP) dst_core<double, true, LL, false>(zs + pr * S::ZL, nullptr, P, t, true, tw, sn);
+    if (2 * pr < ncols && t < S::TP) dst_core<double, true, LL>(zs + pr * S::ZL, nullptr, P, t, true, tw);
   }
   __syncthreads();
   {
@@ -263,7 +263,7 @@ k_dst_xw(BoxGrid g, DstPlan P, double *__restrict__ G, const int32_t *__restrict
   tab.store(zs, &tw, &sn);
   __syncthreads();   // the tables; the pair's own elements are wave-local
   if (!live) return;
-  dst_core<double, true, LL, false>(w, nullptr, P, t, true, tw, sn);
+  dst_core<double, true, LL>(w, nullptr, P, t, true, tw);
   // k = 1 + t + i TP, i < 8: k = 1 .. L; the lattice holds k <= L - 1
   const int zk = ZP(1 + t);
   C2<double> F[8];
@@ -318,8 +318,6 @@ static bool dst_wave_shape_ok(const DstPlan &p) {
   return p.L == LL && p.wave && p.pairs == S::PAIRS && p.slot == S::SLOT && p.scr == 0 && p.tab_off == S::PAIRS * S::ZL;
 }
 static bool dst_wave_fast(const BoxGrid &g, const DstPlan &p, int64_t nvec) {
-  static const bool off = getenv("PHX_DST_OLD") != nullptr || getenv("PHX_DST_GENERIC") != nullptr;
-  if (off) return false;
   const int64_t lat = g.plane * g.m[2];
   if (g.plane != g.pitch * g.m[1] || lat * 8 >= (int64_t)PHX_BUF_OOB || nvec * 8 >= (int64_t)PHX_BUF_OOB) return false;
   bool ok = false;

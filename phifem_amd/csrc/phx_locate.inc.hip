@@ -197,15 +197,6 @@ k_loc_point_bins(int64_t npts, LocGrid G, const double *__restrict__ pts, uint32
   key[i] = (uint32_t)b;
   iota[i] = (int32_t)i;
 }
-__global__ void __launch_bounds__(256)
-k_loc_cell_keys(int64_t npts, int64_t nc, const int32_t *__restrict__ cells_of, uint32_t *__restrict__ key,
-                int32_t *__restrict__ iota) {
-  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i >= npts) return;
-  const int64_t c = cells_of[i];
-  key[i] = (uint32_t)(c < 0 || c >= nc ? nc : c);
-  iota[i] = (int32_t)i;
-}
 
 // one lane per point (order[t] = the point lane t serves, or t itself)
 template <int CT>
@@ -284,15 +275,14 @@ k_loc_box(int64_t npts, LocBox B, const double *__restrict__ pts, double tol, in
 // lambda_v (2 lambda_v - 1), then the edges of PHX_ARR_C2E 4 lambda_a lambda_b.  Sums in ascending local DoF order.
 template <int CT, int DEG, bool GRAD>
 __global__ void __launch_bounds__(256)
-k_loc_eval(int64_t npts, const int32_t *__restrict__ order, int64_t nc, int64_t nv, const int32_t *__restrict__ cells,
+k_loc_eval(int64_t npts, int64_t nc, int64_t nv, const int32_t *__restrict__ cells,
            const int32_t *__restrict__ c2e, const double *__restrict__ x, const int32_t *__restrict__ cell_of,
            const double *__restrict__ xref, int ncomp, const double *__restrict__ u, int64_t ld, double fill,
            double *__restrict__ out, double *__restrict__ gout) {
   constexpr int NV = LocCell<CT>::NV, D = LocCell<CT>::D;
   constexpr int NE = DEG == 2 ? (CT == 2 ? 6 : 3) : 0, ND = NV + NE;
-  const int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (t >= npts) return;
-  const int64_t i = order ? order[t] : t;
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= npts) return;
   const int64_t c = cell_of[i];
   if (c < 0 || c >= nc) {
     for (int q = 0; q < ncomp; ++q) {
@@ -370,15 +360,10 @@ k_loc_eval(int64_t npts, const int32_t *__restrict__ order, int64_t nc, int64_t 
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------
-// Serve the points in their own order or sorted (stable radix sort of 32-bit keys; the kernels then serve point
-// order[lane]).  Measured on the MI355X: sorting by BIN pays in the walk of the bins (10^7 points,
-// 129 k tetrahedra: 12.5 -> 4.0 ms with the sort included), sorting by CELL does not pay in the evaluation (0.21 -> 0.84 ms).
-// So the walk sorts and the evaluation does not; PHX_LOCATE_SORT = 0 / PHX_EVAL_SORT = 1 switch for A-B runs.
-bool loc_sort_points(bool walk) {
-  const char *e = getenv(walk ? "PHX_LOCATE_SORT" : "PHX_EVAL_SORT");
-  return e ? atoi(e) != 0 : walk;
-}
-
+// The walk of the bins serves its points sorted by bin (stable radix sort of 32-bit keys; k_loc_walk then serves point
+// order[lane]); the evaluation serves them in their own order.  Measured on the MI355X: sorting by
+// BIN pays in the walk (10^7 points, 129 k tetrahedra: 12.5 -> 4.0 ms with the sort included), sorting by CELL does not
+// pay in the evaluation (0.21 -> 0.84 ms).
 dim3 loc_grid(int64_t n) { return dim3((unsigned)phx_div_up(n > 0 ? n : 1, 256)); }
 
 int loc_cell_kind(const phx_mesh *m) {
@@ -515,7 +500,7 @@ int loc_locate_bins(phx_mesh *m, DevTemps &tmp, int64_t npts, const double *pts,
   for (int a = 0; a < 3; ++a) { G.n[a] = L->n[a]; G.lo[a] = L->lo[a]; G.inv[a] = L->inv[a]; }
   hipStream_t st = m->stream;
   int32_t *order = nullptr;
-  if (loc_sort_points(true) && npts > 1) {
+  if (npts > 1) {
     uint32_t *key = nullptr;
     int32_t *iota = nullptr;
     PHX_HIP(tmp.get(&key, sizeof(uint32_t) * (size_t)npts));
@@ -545,13 +530,13 @@ int loc_locate_box(phx_mesh *m, int64_t npts, const double *pts, double tol, int
 }
 
 template <int CT, int DEG>
-void loc_launch_eval(phx_mesh *m, bool grad, int64_t npts, const int32_t *order, const int32_t *cells_d,
+void loc_launch_eval(phx_mesh *m, bool grad, int64_t npts, const int32_t *cells_d,
                      const double *xref_d, int ncomp, const double *u, int64_t ld, double fill, double *out, double *gout) {
   if (grad)
-    k_loc_eval<CT, DEG, true><<<loc_grid(npts), dim3(256), 0, m->stream>>>(npts, order, m->nc, m->nv, m->cells, m->c2e, m->x,
+    k_loc_eval<CT, DEG, true><<<loc_grid(npts), dim3(256), 0, m->stream>>>(npts, m->nc, m->nv, m->cells, m->c2e, m->x,
                                                                           cells_d, xref_d, ncomp, u, ld, fill, out, gout);
   else
-    k_loc_eval<CT, DEG, false><<<loc_grid(npts), dim3(256), 0, m->stream>>>(npts, order, m->nc, m->nv, m->cells, m->c2e, m->x,
+    k_loc_eval<CT, DEG, false><<<loc_grid(npts), dim3(256), 0, m->stream>>>(npts, m->nc, m->nv, m->cells, m->c2e, m->x,
                                                                            cells_d, xref_d, ncomp, u, ld, fill, out, gout);
 }
 }  // namespace
@@ -646,23 +631,13 @@ extern "C" int phx_eval_points(phx_mesh *m, int degree, int ncomp, const double 
     PHX_HIP(tmp.get(&od, sizeof(double) * (size_t)npts * ncomp));
     if (want_grad) PHX_HIP(tmp.get(&gd, sizeof(double) * (size_t)npts * ncomp * D));
   }
-  int32_t *order = nullptr;
-  if (loc_sort_points(false) && npts > 1) {
-    uint32_t *key = nullptr;
-    int32_t *iota = nullptr;
-    PHX_HIP(tmp.get(&key, sizeof(uint32_t) * (size_t)npts));
-    PHX_HIP(tmp.get(&iota, sizeof(int32_t) * (size_t)npts));
-    k_loc_cell_keys<<<loc_grid(npts), dim3(256), 0, st>>>(npts, m->nc, cd, key, iota);
-    PHX_HIP(hipGetLastError());
-    PHX_CHECK(loc_sort_order(st, tmp, npts, key, iota, (uint64_t)m->nc + 1, &order));
-  }
   const bool grad = want_grad != 0;
   switch (loc_cell_kind(m) * 2 + (degree - 1)) {
-    case 0: loc_launch_eval<0, 1>(m, grad, npts, order, cd, xd, ncomp, ud, ld, fill, od, gd); break;
-    case 1: loc_launch_eval<0, 2>(m, grad, npts, order, cd, xd, ncomp, ud, ld, fill, od, gd); break;
-    case 2: loc_launch_eval<1, 1>(m, grad, npts, order, cd, xd, ncomp, ud, ld, fill, od, gd); break;
-    case 4: loc_launch_eval<2, 1>(m, grad, npts, order, cd, xd, ncomp, ud, ld, fill, od, gd); break;
-    default: loc_launch_eval<2, 2>(m, grad, npts, order, cd, xd, ncomp, ud, ld, fill, od, gd); break;
+    case 0: loc_launch_eval<0, 1>(m, grad, npts, cd, xd, ncomp, ud, ld, fill, od, gd); break;
+    case 1: loc_launch_eval<0, 2>(m, grad, npts, cd, xd, ncomp, ud, ld, fill, od, gd); break;
+    case 2: loc_launch_eval<1, 1>(m, grad, npts, cd, xd, ncomp, ud, ld, fill, od, gd); break;
+    case 4: loc_launch_eval<2, 1>(m, grad, npts, cd, xd, ncomp, ud, ld, fill, od, gd); break;
+    default: loc_launch_eval<2, 2>(m, grad, npts, cd, xd, ncomp, ud, ld, fill, od, gd); break;
   }
   PHX_HIP(hipGetLastError());
   if (loc_out != PHX_DEVICE) {

@@ -37,8 +37,9 @@ struct Pool {
 Pool &pool() { static Pool p; return p; }
 size_t pool_limit() {
   static size_t lim = [] {
-    const char *e = getenv("PHX_POOL_LIMIT_GB");
-    if (e) return (size_t)(atof(e) * (double)(1ull << 30));
+    bool set = false;
+    const double gb = phx_sw_pool_limit_gb(&set);
+    if (set) return (size_t)(gb * (double)(1ull << 30));
     // default: 60 % of the device (173 GB of 288) -- the transient buffers of one 256^3 elasticity pass add up to
     // ~110 GB, and with the former 96 GB every pass gave the largest ones back and paid hipMalloc for them again
     // (assembly 0.52 -> 2.5 s).  A failing allocation still empties the cache and retries.
@@ -367,10 +368,6 @@ static int mesh_init_device(phx_mesh *m, int device) {
   PHX_REQUIRE(device >= 0 && device < ndev, PHX_ERR_VALUE, "device %d out of range (%d)", device,
               ndev);
   m->device = device;
-  if (const char *e = getenv("PHX_PRECOND")) {   // default of PHX_OPT_PRECOND for this process (0 / 1 / 2)
-    const int v = atoi(e);
-    if (v >= 0 && v <= 2) m->precond = v;
-  }
   PHX_HIP(hipSetDevice(device));
   PHX_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
   PHX_HIP(hipEventCreate(&m->ev0));
@@ -646,8 +643,7 @@ static int mesh_attach_inner_lattice_copy(phx_mesh *m, const double *coords, con
 }
 
 // coords / cells at `loc` (host arrays from a caller, or device arrays of a parent mesh: phx_submesh.hip).  The facet
-// numbering and both connectivities are built on the device (phx_topology.inc.hip); PHX_TOPOLOGY_HOST=1 takes the
-// host sort of phx_topology_build_host instead (same numbering; A/B aid, host inputs only).
+// numbering and both connectivities are built on the device (phx_topology.inc.hip).
 int phx_mesh_create_from(int gdim, int cell_type, int64_t nv, const double *coords, int64_t nc,
                          const int32_t *cells, int loc, int device, phx_mesh **out) {
   phx_cell_info ci;
@@ -655,7 +651,6 @@ int phx_mesh_create_from(int gdim, int cell_type, int64_t nv, const double *coor
   PHX_REQUIRE(gdim == ci.tdim, PHX_ERR_VALUE, "gdim %d does not match the cell type", gdim);
   PHX_REQUIRE(nc > 0 && nv > 0, PHX_ERR_VALUE, "empty mesh");
   PHX_REQUIRE(nc * (int64_t)ci.nfpc < INT32_MAX, PHX_ERR_VALUE, "mesh too large for 32-bit local ids");
-  static const bool host_topo = getenv("PHX_TOPOLOGY_HOST") && atoi(getenv("PHX_TOPOLOGY_HOST")) != 0;
   phx_mesh *m = new phx_mesh();
   int rc = mesh_init_device(m, device);
   if (rc != PHX_OK) { delete m; return rc; }
@@ -673,23 +668,8 @@ int phx_mesh_create_from(int gdim, int cell_type, int64_t nv, const double *coor
     phx_set_error("mesh upload failed");
     return fail(PHX_ERR_HIP);
   }
-  if (host_topo && loc != PHX_DEVICE) {
-    std::vector<int32_t> c2f((size_t)nc * ci.nfpc), f2c((size_t)nc * ci.nfpc * 2);
-    int64_t nf = 0;
-    rc = phx_topology_build_host(cell_type, nv, nc, cells, c2f.data(), f2c.data(), &nf);
-    if (rc != PHX_OK) return fail(rc);
-    m->nf = nf;
-    if (phx_malloc(&m->c2f, sizeof(int32_t) * (size_t)nc * ci.nfpc) != hipSuccess ||
-        phx_malloc(&m->f2c, sizeof(int32_t) * (size_t)nf * 2) != hipSuccess ||
-        hipMemcpy(m->c2f, c2f.data(), sizeof(int32_t) * (size_t)nc * ci.nfpc, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(m->f2c, f2c.data(), sizeof(int32_t) * (size_t)nf * 2, hipMemcpyHostToDevice) != hipSuccess) {
-      phx_set_error("mesh upload failed");
-      return fail(PHX_ERR_HIP);
-    }
-  } else {
-    rc = phx_topology_build_device(m);
-    if (rc != PHX_OK) return fail(rc);
-  }
+  rc = phx_topology_build_device(m);
+  if (rc != PHX_OK) return fail(rc);
   rc = build_boundary_list(m);
   if (rc == PHX_OK) rc = phx_mesh_alloc_common(m);
   if (rc != PHX_OK) return fail(rc);
@@ -709,8 +689,7 @@ int phx_mesh_create_from(int gdim, int cell_type, int64_t nv, const double *coor
         phx_set_error("mesh upload failed");
         return fail(PHX_ERR_HIP);
       }
-      static const bool no_inner = getenv("PHX_INNER_BOX") && atoi(getenv("PHX_INNER_BOX")) == 0;   // A/B aid
-      if (!no_inner) {
+      if (phx_sw_inner_box()) {
         // simplices: leaves m->inner == nullptr when the cells are not the Kuhn split; quadrilaterals: a copy in lattice
         // vertex order, none when the vertices already are
         rc = cell_type == PHX_QUADRILATERAL ? mesh_attach_inner_lattice_copy(m, coords, cells, v2lat, lat2v)

@@ -86,16 +86,13 @@ static int dst_get_plan(int device, int L, bool f32, DstPlan *out) {
   // Only where no lane idles (L = 256, 512): at L = 192 / 384 / 128 the 25-50 % empty slot lanes cost as
   // much issue time as the barriers save (the transforms are VALU/LDS-issue bound).
   P.wave = (P.tp == 32 || P.tp == 64 || (!f32 && P.tp == 24)) ? 1 : 0;  // f64, L = 192: 190 -> 185 us per application
-  if (const char *e = getenv("PHX_DST_WAVE")) P.wave = (P.tp <= 64) && atoi(e) != 0;  // tuning aid
   P.slot = P.wave ? (P.tp <= 32 ? 32 : 64) : P.tp;
   const int el = f32 ? (int)sizeof(float2) : (int)sizeof(double2);
   // long f64 transforms take (almost) a whole CU's LDS per block to reach 128-byte tile rows
   // (768 x 768 x 192 lattice, y pass: 80 KB 1057 us, 156 KB 669 us)
-  int budget = (P.wave ? 64 : (L >= 768 ? (f32 ? 80 : 156) : (f32 ? 20 : 40))) * 1024;
-  int max_threads = P.wave ? 1024 : (L >= 768 ? 1024 : 512);
-  int max_pairs = P.wave ? (f32 ? 16 : 8) : 1024;
-  if (const char *e = getenv("PHX_DST_LDS_KB")) budget = atoi(e) > 0 ? atoi(e) * 1024 : budget;  // tuning aids
-  if (const char *e = getenv("PHX_DST_PAIRS")) max_pairs = atoi(e) > 0 ? atoi(e) : max_pairs;
+  const int budget = (P.wave ? 64 : (L >= 768 ? (f32 ? 80 : 156) : (f32 ? 20 : 40))) * 1024;
+  const int max_threads = P.wave ? 1024 : (L >= 768 ? 1024 : 512);
+  const int max_pairs = P.wave ? (f32 ? 16 : 8) : 1024;
   P.pairs = 1;
   while ((2 * P.pairs * ZLEN(L) + 2 * L) * el <= budget && 2 * P.pairs * P.slot <= max_threads &&
          2 * P.pairs <= max_pairs)
@@ -307,33 +304,16 @@ __device__ __forceinline__ C2<double> dpp_c2(C2<double> v) {
   return mk<double>(__hiloint2double(w[1], w[0]), __hiloint2double(w[3], w[2]));
 }
 
-// In:  w[ZP(j)] = (a_j, b_j), j = 1 .. L-1 (w[0] arbitrary).   Out: w[ZP(k)] = (F^a_k, F^b_k), k = 1 .. L-1,
+// In:  w[ZP(j)] = the folded sequence y_j = sin(pi j / L)(x_j + x_{L-j}) + (x_j - x_{L-j}) / 2 of the two lines x = a, b
+// (w[0] = 0, w[H] = 2 x_H) -- the loaders of the x and y passes fold in registers, which saves a read and a write of
+// every LDS element and one synchronisation per transform.   Out: w[ZP(k)] = (F^a_k, F^b_k), k = 1 .. L-1,
 // F_k = sum_j x_j sin(pi j k / L).  `scr`: tp + tp/8 + 1 complex values of scan scratch of this pair.
 // Block-wide barriers inside: every thread of the block calls it.
-// PRE = false: the caller has already written the folded sequence y_j = sin(pi j / L)(x_j + x_{L-j}) + (x_j - x_{L-j}) / 2
-// (w[0] = 0, w[H] = 2 x_H) -- the loaders of the x and y passes fold in registers, which saves a read and a write of
-// every LDS element and one synchronisation per transform.
-template <typename T, bool WAVE, int LL, bool PRE = true>
+template <typename T, bool WAVE, int LL>
 __device__ __forceinline__ void dst_core(C2<T> *w, C2<T> *scr, const DstPlan &P, int t, bool live,
-                                         const C2<T> *tw, const T *sn) {
-  const int L = plan_L<LL>(P), tp = plan_tp<LL>(P), H = L >> 1, slot = plan_slot<LL, WAVE>(P);
+                                         const C2<T> *tw) {
+  const int L = plan_L<LL>(P), tp = plan_tp<LL>(P), slot = plan_slot<LL, WAVE>(P);
   const T hf = T(0.5);
-  if (PRE && live) {
-    for (int j = 1 + t; j < H; j += tp) {
-      const C2<T> X = w[ZP(j)], Y = w[ZP(L - j)];
-      const T s = sn[j];
-      const C2<T> e = mk<T>(s * (X.x + Y.x), s * (X.y + Y.y));
-      const C2<T> o = mk<T>(hf * (X.x - Y.x), hf * (X.y - Y.y));
-      w[ZP(j)] = cadd(e, o);
-      w[ZP(L - j)] = csub(e, o);
-    }
-    if (t == 0) {
-      w[0] = mk<T>(T(0), T(0));
-      const C2<T> X = w[ZP(H)];
-      w[ZP(H)] = mk<T>(X.x + X.x, X.y + X.y);
-    }
-  }
-  if (PRE) psync<WAVE>();
   fft_pairs<T, WAVE, LL>(w, P, t, live, tw);
   // thread t owns k = 4 t .. 4 t + 3  (k < L / 2)
   // The running sums are kept in f64 whatever the transform precision: in f32 they are what turns the
@@ -477,7 +457,7 @@ k_dst_x(BoxGrid g, DstPlan P, T *__restrict__ G, const int32_t *__restrict__ gma
       base[c] = has[c] ? (l % g.m[1]) * g.pitch + (l / g.m[1]) * g.plane : 0;
     }
     // the thread takes the PAIRS (j, L - j), j = 1 + t + i tp (4 trips: j = 1 .. L / 2) of both lines and folds them in
-    // registers (dst_core<..., PRE = false>); all loads are issued before the first LDS write
+    // registers (see dst_core); all loads are issued before the first LDS write
     const int H = L >> 1;
     const T *sng = PlanTab<T>::sn(P);
     T va[4], vb[4], ua[4], ub[4], sj[4];   // line a / b at j (v) and at L - j (u)
@@ -525,7 +505,7 @@ k_dst_x(BoxGrid g, DstPlan P, T *__restrict__ G, const int32_t *__restrict__ gma
     if (t == 0) w[0] = mk<T>(T(0), T(0));
   }
   __syncthreads();
-  dst_core<T, WAVE, LL, false>(w, scr, P, t, live, tw, sn);
+  dst_core<T, WAVE, LL>(w, scr, P, t, live, tw);
   if (!live) return;
   if (IO == 2) {
     // k = t + 1 + i tp: all map loads, then all scale loads, then the stores
@@ -560,16 +540,15 @@ k_dst_x(BoxGrid g, DstPlan P, T *__restrict__ G, const int32_t *__restrict__ gma
   }
 }
 
-// ---- y / z lines (strided): a block takes W = 2 * pairs adjacent x columns of one `outer` index, so every
-// global access is a run of W consecutive values.  AXIS = 1: lines along y (outer = z), AXIS = 2: lines
-// along z (outer = y).  SOLVE (z only): forward transform, times scale / lambda, inverse transform, all in LDS.
-// row_any (AXIS = 1 only, nullable): row_any[z] = {first, last} row of plane z whose x line holds a mapped lattice
+// ---- y lines (strided): a block takes W = 2 * pairs adjacent x columns of one plane `outer` = z, so every
+// global access is a run of W consecutive values.  (The z direction is a tridiagonal solve, phx_tridiag.inc.hip.)
+// row_any (nullable): row_any[z] = {first, last} row of plane z whose x line holds a mapped lattice
 // point (one block-uniform pair: scalar loads and two compares per row; a flag load per row in front of every tile
 // load made the pass slower than the traffic it saved).  dir = 1
 // (forward, after the gathering x pass): such a row holds nothing -- it is not even written by the x pass -- and is taken
 // as zero; dir = 2 (backward, before the scattering x pass): nobody reads such a row, so it is not stored.  37 % of the
 // rows of the ball's box: that much less of the pass's traffic.
-template <typename T, int AXIS, bool SOLVE, bool WAVE, int LL = 0>
+template <typename T, bool WAVE, int LL = 0>
 __global__ void __launch_bounds__(1024)
 k_dst_s(BoxGrid g, DstPlan P, T *__restrict__ G, const int2 *__restrict__ row_any, int dir) {
   extern __shared__ double2 zs_raw[];
@@ -581,9 +560,9 @@ k_dst_s(BoxGrid g, DstPlan P, T *__restrict__ G, const int2 *__restrict__ row_an
   const int ncb = (mx + W - 1) / W;                 // column blocks
   const int col0 = (int)(blockIdx.x % ncb) * W;
   const int64_t outer = blockIdx.x / ncb;
-  const int len = g.m[AXIS];
-  const int64_t estride = AXIS == 1 ? g.pitch : g.plane;
-  const int64_t base = col0 + outer * (AXIS == 1 ? g.plane : g.pitch);
+  const int len = g.m[1];
+  const int64_t estride = g.pitch;
+  const int64_t base = col0 + outer * g.plane;
   const int ncols = min(W, mx - col0);
   const bool live = 2 * pr < ncols && t < Ptp;
   C2<T> *w = zs + (size_t)pr * ZLEN(L);
@@ -595,83 +574,46 @@ k_dst_s(BoxGrid g, DstPlan P, T *__restrict__ G, const int2 *__restrict__ row_an
   // rstep = L / 16: 16 trips, all loads in flight before the first LDS write)
   const int tcol = threadIdx.x % W, row0 = threadIdx.x / W, rstep = blockDim.x / W;
   T *wcol = reinterpret_cast<T *>(zs + (size_t)(tcol >> 1) * ZLEN(L)) + (tcol & 1);
-  if constexpr (!SOLVE) {
-    // plain transform: the thread takes the PAIRS (j, L - j), j = 1 + row0 + i rstep <= L / 2, and folds them in
-    // registers (dst_core<..., PRE = false>)
-    constexpr int NT = 8;
-    const int H = L >> 1;
-    T va[NT], vb[NT], sj[NT];
-    const T *sng = PlanTab<T>::sn(P);
-    int rlo = 0, rhi = len - 1;
-    if (AXIS == 1 && row_any && dir == 1) { const int2 iv = row_any[outer]; rlo = iv.x; rhi = iv.y; }
-    const bool colok = tcol < ncols;
-    const T *g0 = G + (base + tcol);
+  // plain transform: the thread takes the PAIRS (j, L - j), j = 1 + row0 + i rstep <= L / 2, and folds them in
+  // registers (see dst_core)
+  constexpr int NT = 8;
+  const int H = L >> 1;
+  T va[NT], vb[NT], sj[NT];
+  const T *sng = PlanTab<T>::sn(P);
+  int rlo = 0, rhi = len - 1;
+  if (row_any && dir == 1) { const int2 iv = row_any[outer]; rlo = iv.x; rhi = iv.y; }
+  const bool colok = tcol < ncols;
+  const T *g0 = G + (base + tcol);
 #pragma unroll
-    for (int i = 0; i < NT; ++i) {
-      const int j = 1 + row0 + i * rstep;
-      const int ra = j - 1, rb = L - 1 - j;
-      const bool ok = j <= H && colok;
-      va[i] = (ok && ra >= rlo && ra <= rhi) ? g0[(int64_t)ra * estride] : T(0);
-      vb[i] = (ok && j < H && rb >= rlo && rb <= rhi) ? g0[(int64_t)rb * estride] : T(0);
-      sj[i] = j <= H ? sng[j] : T(0);
-    }
+  for (int i = 0; i < NT; ++i) {
+    const int j = 1 + row0 + i * rstep;
+    const int ra = j - 1, rb = L - 1 - j;
+    const bool ok = j <= H && colok;
+    va[i] = (ok && ra >= rlo && ra <= rhi) ? g0[(int64_t)ra * estride] : T(0);
+    vb[i] = (ok && j < H && rb >= rlo && rb <= rhi) ? g0[(int64_t)rb * estride] : T(0);
+    sj[i] = j <= H ? sng[j] : T(0);
+  }
 #pragma unroll
-    for (int i = 0; i < NT; ++i) {
-      const int j = 1 + row0 + i * rstep;
-      if (j < H) {
-        const T e = sj[i] * (va[i] + vb[i]), o = T(0.5) * (va[i] - vb[i]);
-        wcol[2 * ZP(j)] = e + o;
-        wcol[2 * ZP(L - j)] = e - o;
-      } else if (j == H) {
-        wcol[2 * ZP(H)] = va[i] + va[i];
-      }
-    }
-    if (row0 == 0) wcol[0] = T(0);
-  } else {
-    T vv[16];
-    const T *gp = G + (base + (int64_t)row0 * estride + tcol);
-    const int64_t gstep = (int64_t)rstep * estride;
-    const bool colok = tcol < ncols;
-    int row = row0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      vv[i] = (row < len && colok) ? *gp : T(0);
-      gp += gstep;
-      row += rstep;
-    }
-    row = row0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      if (row < L - 1) wcol[2 * ZP(row + 1)] = vv[i];
-      row += rstep;
+  for (int i = 0; i < NT; ++i) {
+    const int j = 1 + row0 + i * rstep;
+    if (j < H) {
+      const T e = sj[i] * (va[i] + vb[i]), o = T(0.5) * (va[i] - vb[i]);
+      wcol[2 * ZP(j)] = e + o;
+      wcol[2 * ZP(L - j)] = e - o;
+    } else if (j == H) {
+      wcol[2 * ZP(H)] = va[i] + va[i];
     }
   }
+  if (row0 == 0) wcol[0] = T(0);
   __syncthreads();
-  dst_core<T, WAVE, LL, SOLVE>(w, scr, P, t, live, tw, sn);
-  if (SOLVE) {
-    if (live) {
-      const double *lx = g.lam[0], *ly = g.lam[1], *lz = g.lam[2];
-      const int kx = col0 + 2 * pr + 1;
-      const double lxy0 = lx[kx] + ly[outer + 1];
-      const double lxy1 = (kx + 1 < g.L[0] ? lx[kx + 1] : lx[kx]) + ly[outer + 1];
-      // the divide runs in the precision of the transform (an f64 division costs ~10x an f32 one)
-      const T sc = (T)g.scale, l0 = (T)lxy0, l1 = (T)lxy1;
-      for (int k = t + 1; k < L; k += Ptp) {
-        const C2<T> F = w[ZP(k)];
-        const T lzk = (T)lz[k];
-        w[ZP(k)] = mk<T>(F.x * sc / (l0 + lzk), F.y * sc / (l1 + lzk));
-      }
-    }
-    psync<WAVE>();
-    dst_core<T, WAVE, LL>(w, scr, P, t, live, tw, sn);
-  }
+  dst_core<T, WAVE, LL>(w, scr, P, t, live, tw);
   __syncthreads();
   if (tcol < ncols) {
     const T *wc = reinterpret_cast<const T *>(zs + (size_t)(tcol >> 1) * ZLEN(L)) + (tcol & 1);
     T *gp = G + (base + (int64_t)row0 * estride + tcol);
     const int64_t gstep = (int64_t)rstep * estride;
     int rlo = 0, rhi = len - 1;
-    if (AXIS == 1 && row_any && dir == 2) { const int2 iv = row_any[outer]; rlo = iv.x; rhi = iv.y; }
+    if (row_any && dir == 2) { const int2 iv = row_any[outer]; rlo = iv.x; rhi = iv.y; }
     for (int row = row0; row < len; row += rstep) {
       if (row >= rlo && row <= rhi) *gp = wc[2 * ZP(row + 1)];
       gp += gstep;
@@ -686,7 +628,7 @@ constexpr bool dst_wave_f64(int L) { return L / 8 == 32 || L / 8 == 64 || L / 8 
 // --------------------------------------------------------------------------------------------------
 struct phx_box_precond {
   BoxGrid g;
-  DstPlan plan[3];
+  DstPlan plan[2];           // x, y (z: tridiagonal solve, no transform)
   void *G = nullptr;         // lattice array, f32 or f64
   bool f32 = false;          // precision of the lattice array and the transforms
   int32_t *gmap = nullptr;   // [plane * m2] solver position of the u DoF, -1 none
@@ -708,7 +650,6 @@ struct phx_box_precond {
   uint8_t *line_any = nullptr;  // [m1 * m2] x line holds at least one mapped lattice point (nullptr: all do)
   int2 *line_iv = nullptr;      // [m2] {first, last} row of the plane with such a line ({1, 0}: none); line_any is widened to
                                 // the whole interval, so "outside the interval" and "line_any = 0" say the same
-  bool ztri = true;          // z direction: tridiagonal solve (default) or forward / inverse sine transform in LDS
   bool rowskip = false;      // an APPLICATION is running (gathering / scattering x passes around the middle passes): rows of
                              // x lines without a mapped point are neither written by the forward passes nor read back
   const int2 *line_iv_out = nullptr;   // set while the backward passes scatter through another map than the forward ones gather
@@ -736,8 +677,7 @@ static int dst_allow_lds_t() {
   PHX_HIP(hipFuncSetAttribute((const void *)k_dst_x<T, 0, WAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
   PHX_HIP(hipFuncSetAttribute((const void *)k_dst_x<T, 1, WAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
   PHX_HIP(hipFuncSetAttribute((const void *)k_dst_x<T, 2, WAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  PHX_HIP(hipFuncSetAttribute((const void *)k_dst_s<T, 1, false, WAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  PHX_HIP(hipFuncSetAttribute((const void *)k_dst_s<T, 2, true, WAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  PHX_HIP(hipFuncSetAttribute((const void *)k_dst_s<T, WAVE>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
   return PHX_OK;
 }
 // f64 kernels specialised for the transform length, in the synchronisation mode dst_get_plan picks for it
@@ -749,7 +689,7 @@ static int dst_allow_lds_len() {
   PHX_HIP(hipFuncSetAttribute((const void *)k_dst_x<double, 0, WV, LL>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
   PHX_HIP(hipFuncSetAttribute((const void *)k_dst_x<double, 1, WV, LL>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
   PHX_HIP(hipFuncSetAttribute((const void *)k_dst_x<double, 2, WV, LL>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-  PHX_HIP(hipFuncSetAttribute((const void *)k_dst_s<double, 1, false, WV, LL>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  PHX_HIP(hipFuncSetAttribute((const void *)k_dst_s<double, WV, LL>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
   return PHX_OK;
 }
 static int dst_allow_lds() {
@@ -777,13 +717,12 @@ static int box_grid_setup(phx_box_precond *bp, int device, const int L[3], const
   bp->f32 = f32;
   PHX_CHECK(dst_allow_lds());
   BoxGrid &g = bp->g;
-  if (const char *e = getenv("PHX_Z_TRIDIAG")) bp->ztri = atoi(e) != 0;  // A/B aid: 0 = sine transforms in z
   for (int a = 0; a < 3; ++a) {
     g.L[a] = L[a];
     g.m[a] = L[a] - 1;
     g.c[a] = c[a];
-    // no transform runs along a tridiagonal z axis: its length is free (L[2] >= 2)
-    if (a < 2 || !bp->ztri) PHX_CHECK(dst_get_plan(device, L[a], f32, &bp->plan[a]));
+    // no transform runs along z (tridiagonal solve): its length is free (L[2] >= 2)
+    if (a < 2) PHX_CHECK(dst_get_plan(device, L[a], f32, &bp->plan[a]));
   }
   g.pitch = L[0];
   g.plane = g.pitch * g.m[1];
@@ -832,20 +771,10 @@ static TriArgs box_tri_args(const phx_box_precond *bp) {
   return a;
 }
 
-// z pass on G: tridiagonal solve per (kx, ky) column, or forward sine transform, 1 / lambda, inverse in LDS
+// z pass on G: tridiagonal solve per (kx, ky) column
 template <typename T>
 static int box_pass_z_t(phx_box_precond *bp, hipStream_t st) {
-  const BoxGrid &g = bp->g;
-  T *G = static_cast<T *>(bp->G);
-  if (bp->ztri) return tri_launch<T, 0>(box_tri_args(bp), G, st);
-  const DstPlan &pz = bp->plan[2];
-  const int W = 2 * pz.pairs, ncb = (g.m[0] + W - 1) / W;
-  const dim3 grid((unsigned)((int64_t)ncb * g.m[1])), block((unsigned)(pz.pairs * pz.slot));
-  const size_t lds = (size_t)pz.lds_elems * sizeof(T) * 2;
-  if (pz.wave) k_dst_s<T, 2, true, true><<<grid, block, lds, st>>>(g, pz, G, nullptr, 0);
-  else k_dst_s<T, 2, true, false><<<grid, block, lds, st>>>(g, pz, G, nullptr, 0);
-  PHX_HIP(hipGetLastError());
-  return PHX_OK;
+  return tri_launch<T, 0>(box_tri_args(bp), static_cast<T *>(bp->G), st);
 }
 
 // dir: 0 plain transform of every row, 1 / 2 forward / backward pass of an application (rows of x lines without a
@@ -875,8 +804,6 @@ static int box_pass_y_t(phx_box_precond *bp, hipStream_t st, phx_system *prof, i
   }
   if constexpr (sizeof(T) == 8) {
     if (!done && dst_pair_fast(g, py, 0)) {
-      static const int ydbg = getenv("PHX_DST_YDBG") ? atoi(getenv("PHX_DST_YDBG")) : 0;   // experiment: 1 no transform, 2 no memory
-      dir |= ydbg << 8;
       switch (py.L) {
 #define X(L_) case L_: { \
           using S = PairShape<L_, 0>; \
@@ -890,10 +817,10 @@ static int box_pass_y_t(phx_box_precond *bp, hipStream_t st, phx_system *prof, i
     }
   }
   if constexpr (sizeof(T) == 8) {
-    if (!done && !getenv("PHX_DST_GENERIC")) {
+    if (!done) {
       switch (py.L) {
 #define X(L_) case L_: if ((py.wave != 0) == dst_wave_f64(L_)) { \
-          k_dst_s<double, 1, false, dst_wave_f64(L_), L_><<<grid, block, (size_t)py.lds_elems * el, st>>>(g, py, G, ra, dir); done = true; } break;
+          k_dst_s<double, dst_wave_f64(L_), L_><<<grid, block, (size_t)py.lds_elems * el, st>>>(g, py, G, ra, dir); done = true; } break;
         PHX_DST_LENGTHS(X)
 #undef X
         default: break;
@@ -901,8 +828,8 @@ static int box_pass_y_t(phx_box_precond *bp, hipStream_t st, phx_system *prof, i
     }
   }
   if (!done) {
-    if (py.wave) k_dst_s<T, 1, false, true><<<grid, block, (size_t)py.lds_elems * el, st>>>(g, py, G, ra, dir);
-    else k_dst_s<T, 1, false, false><<<grid, block, (size_t)py.lds_elems * el, st>>>(g, py, G, ra, dir);
+    if (py.wave) k_dst_s<T, true><<<grid, block, (size_t)py.lds_elems * el, st>>>(g, py, G, ra, dir);
+    else k_dst_s<T, false><<<grid, block, (size_t)py.lds_elems * el, st>>>(g, py, G, ra, dir);
   }
   if (prof) PHX_CHECK(prof_end(prof, 1));
   PHX_HIP(hipGetLastError());
@@ -990,7 +917,7 @@ static int box_pass_x_t(phx_box_precond *bp, hipStream_t st, const double *vin, 
     }
   }
   if constexpr (sizeof(T) == 8) {
-    if (!done && !getenv("PHX_DST_GENERIC")) {
+    if (!done) {
       switch (px.L) {
 #define X(L_) case L_: if ((px.wave != 0) == dst_wave_f64(L_)) { \
           k_dst_x<double, IO, dst_wave_f64(L_), L_><<<grid, block, lds, st>>>(g, px, static_cast<double *>(bp->G), bp->gmap, vin, vout, sc, bp->line_any); \
@@ -1290,12 +1217,10 @@ static int box_precond_setup(phx_system *s) {
   PHX_CHECK(box_local_bbox(s, p2, hbb));
   if (hbb[3] < 0) { s->precond_veto = false; return PHX_OK; }  // no (owned) active u DoF here: nothing to precondition
   int L[3], lo[3];
-  bool ztri = true;
-  if (const char *e = getenv("PHX_Z_TRIDIAG")) ztri = atoi(e) != 0;
   for (int a = 0; a < 3; ++a) {
     const int extent = hbb[3 + a] - hbb[a] + 1;
     // z (tridiagonal solve, no transform): exactly extent + margins planes; a 2-D lattice keeps its one real plane
-    const bool free_len = a == 2 && ztri;
+    const bool free_len = a == 2;
     if (free_len && m->gdim == 3) {
       // last vertex plane of the mesh box, in the coordinates of hbb (P2: the lattice of spacing h / 2)
       const int top = (m->is_box || m->on_box_lattice) ? (int)m->box_n[2] * (p2 ? 2 : 1) : -1;
@@ -1517,13 +1442,9 @@ static int box_precond_apply_red(phx_system *s, const double *vin, double *vout)
 // (x fastest, no padding in `f`) in f64 (f32 = 0) or f32 transforms; u overwrites f.
 extern "C" int phx_box_poisson_solve(int device, const int *L, const double *h, int f32, double *f_host) {
   PHX_HIP(hipSetDevice(device));
-  {
-    bool ztri = true;
-    if (const char *e = getenv("PHX_Z_TRIDIAG")) ztri = atoi(e) != 0;
-    for (int a = 0; a < 3; ++a)
-      PHX_REQUIRE(dst_pick_length(L[a]) == L[a] || (a == 2 && ztri && L[a] >= 2 && L[a] <= 1025), PHX_ERR_VALUE,
-                  "L[%d] = %d is not a supported transform length", a, L[a]);
-  }
+  for (int a = 0; a < 3; ++a)
+    PHX_REQUIRE(dst_pick_length(L[a]) == L[a] || (a == 2 && L[a] >= 2 && L[a] <= 1025), PHX_ERR_VALUE,
+                "L[%d] = %d is not a supported transform length", a, L[a]);
   phx_box_precond *bp = new phx_box_precond();
   const double c[3] = {h[1] * h[2] / h[0], h[0] * h[2] / h[1], h[0] * h[1] / h[2]};
   int rc = box_grid_setup(bp, device, L, c, f32 != 0);

@@ -25,8 +25,8 @@
 // Rows per length-sorting window.  Measured on the 256^3 system (2.9 M rows): no sort 180 us,
 // 512 -> 113 us, 4096 -> 184 us, 32768 -> 122 us, one global window -> 81 us per SpMV; the stable
 // global sort keeps the 7-point interior rows in natural order and only moves the few long
-// (cut-region) rows, so the x-gather locality survives.  PHX_SELL_WINDOW overrides (tuning aid).
-static int64_t g_sell_window = (int64_t)1 << 40;
+// (cut-region) rows, so the x-gather locality survives.
+static const int64_t SELL_WINDOW = (int64_t)1 << 40;
 // Dot products: every block adds its partial sum to one of NSLOT accumulators (one 64-byte line
 // each, so the memory-side atomics of different blocks do not queue on one address); a one-wave
 // kernel folds the slots into the scalar the next phase reads.
@@ -202,8 +202,7 @@ k_sell_index(int64_t nslices, const int64_t *__restrict__ slice_ptr, double *sva
 int phx_system_build_sell(phx_system *s) {
   phx_mesh *m = s->mesh;
   const int64_t n = s->n;
-  if (const char *e = getenv("PHX_SELL_WINDOW")) g_sell_window = atoll(e) > 0 ? atoll(e) : g_sell_window;
-  PHX_REQUIRE(n / g_sell_window < (1 << 21), PHX_ERR_VALUE, "system too large for the SELL sort key");
+  PHX_REQUIRE(n / SELL_WINDOW < (1 << 21), PHX_ERR_VALUE, "system too large for the SELL sort key");
   uint32_t *keys = nullptr, *keys2 = nullptr;
   int32_t *rows = nullptr;
   PHX_HIP(phx_malloc(&keys, sizeof(uint32_t) * (size_t)n));
@@ -215,7 +214,7 @@ int phx_system_build_sell(phx_system *s) {
   unsigned long long *dtotal = nullptr;
   PHX_HIP(phx_malloc(&dtotal, sizeof(unsigned long long)));
   PHX_HIP(hipMemsetAsync(dtotal, 0, sizeof(unsigned long long), m->stream));
-  k_row_lengths<<<grid, block, 0, m->stream>>>(n, s->rowptr, s->col, s->val, s->row_nz, keys, rows, dtotal, g_sell_window);
+  k_row_lengths<<<grid, block, 0, m->stream>>>(n, s->rowptr, s->col, s->val, s->row_nz, keys, rows, dtotal, SELL_WINDOW);
   unsigned long long htotal = 0;
   PHX_HIP(hipMemcpyAsync(&htotal, dtotal, sizeof(htotal), hipMemcpyDeviceToHost, m->stream));
   PHX_HIP(hipStreamSynchronize(m->stream));
@@ -223,7 +222,7 @@ int phx_system_build_sell(phx_system *s) {
   s->sell_true_nnz = (int64_t)htotal;
   // only the bits that can differ are sorted: 10 length bits (+ the window index if windowed)
   int end_bit = 10;
-  for (int64_t w = (n - 1) / g_sell_window; w > 0; w >>= 1) ++end_bit;
+  for (int64_t w = (n - 1) / SELL_WINDOW; w > 0; w >>= 1) ++end_bit;
   size_t bytes = 0;
   PHX_HIP(phx_sort_pairs(nullptr, bytes, keys, keys2, rows, s->perm, (size_t)n, 0, end_bit, m->stream));
   void *tmp = nullptr;
@@ -379,21 +378,9 @@ k_sum2_i32(int64_t n, const int32_t *__restrict__ a, const int32_t *__restrict__
 
 struct SelStored { const uint8_t *c0; __host__ __device__ bool operator()(const int32_t &i) const { return c0[i] == 0; } };
 
-// tile > 0: rows of one tile^3 block of lattice vertices (u and p rows alike) come first in the key: a slice then
-// gathers x entries of ONE (tile + 4)^3 neighbourhood, which the L1 of its CU holds
-__global__ void k_stored_keys(int64_t ns, const int32_t *__restrict__ list, const int32_t *__restrict__ len,
-                              uint32_t *__restrict__ keys, const int64_t *__restrict__ full, int64_t nv, int64_t n0,
-                              int64_t n01, int tile, int t0, int t1) {
+__global__ void k_stored_keys(int64_t ns, const int32_t *__restrict__ len, uint32_t *__restrict__ keys) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  if (i >= ns) return;
-  uint32_t key = (uint32_t)(1023 - min(len[i], 1023));   // ascending key = descending length
-  if (tile > 0) {
-    int64_t v = full[list[i]];
-    if (v >= nv) v -= nv;
-    const int x = (int)(v % n0) / tile, y = (int)((v % n01) / n0) / tile, z = (int)(v / n01) / tile;
-    key |= (uint32_t)((z * t1 + y) * t0 + x) << 10;
-  }
-  keys[i] = key;
+  if (i < ns) keys[i] = (uint32_t)(1023 - min(len[i], 1023));   // ascending key = descending length
 }
 
 // Stable counting sort of (key, value) pairs with keys < 1024 (the stored rows by length: half a million items, a few
@@ -886,28 +873,11 @@ int phx_system_build_structured(phx_system *s, const phx_slot_view &sv, int32_t 
     PHX_HIP(phx_malloc(&keys, sizeof(uint32_t) * (size_t)ns));
     PHX_HIP(phx_malloc(&keys2, sizeof(uint32_t) * (size_t)ns));
     const dim3 gs((unsigned)phx_div_up(ns, 256));
-    int tile = 0, tn[3] = {1, 1, 1}, key_bits = 10;
-    if (const char *e = getenv("PHX_SELL_TILE")) tile = atoi(e);
-    if (tile > 0) {
-      for (int a = 0; a < 3; ++a) tn[a] = (int)(m->box_n[a] / tile + 1);
-      const int64_t nt = (int64_t)tn[0] * tn[1] * tn[2];
-      if (nt >= (1 << 21)) tile = 0;
-      else while ((1ll << (key_bits - 10)) < nt) ++key_bits;
-    }
-    k_stored_keys<<<gs, block, 0, st>>>(ns, list, len, keys, s->full_of_active, m->nv, n0, n01, tile, tn[0], tn[1]);
+    k_stored_keys<<<gs, block, 0, st>>>(ns, len, keys);
     k_fill_i32<<<dim3((unsigned)phx_div_up(s->nslices * SELL_S, 256)), block, 0, st>>>(s->nslices * SELL_S, rows_active, -1, 0);
-    size_t bytes = 0;
-    void *tmp = nullptr;
-    static const bool sort_rocprim = getenv("PHX_SORT_ROCPRIM") && atoi(getenv("PHX_SORT_ROCPRIM")) != 0;   // A/B aid
-    if (key_bits <= 10 && !sort_rocprim) {
-      // keys = 1023 - row length, and a row holds at most slot-capacity entries
-      const int wmax = std::min(std::max(sv.W, 1), 1023);
-      PHX_CHECK(phx_counting_sort_pairs(st, keys, keys2, list, rows_active, ns, (uint32_t)(1023 - wmax), wmax + 1, &later));
-    } else {
-      PHX_HIP(phx_sort_pairs(nullptr, bytes, keys, keys2, list, rows_active, (size_t)ns, 0, key_bits, st));
-      PHX_HIP(phx_malloc(&tmp, bytes ? bytes : 16));
-      PHX_HIP(phx_sort_pairs(tmp, bytes, keys, keys2, list, rows_active, (size_t)ns, 0, key_bits, st));
-    }
+    // keys = 1023 - row length, and a row holds at most slot-capacity entries
+    const int wmax = std::min(std::max(sv.W, 1), 1023);
+    PHX_CHECK(phx_counting_sort_pairs(st, keys, keys2, list, rows_active, ns, (uint32_t)(1023 - wmax), wmax + 1, &later));
     PHX_HIP(hipMemcpyAsync(s->sell_rows, rows_active, sizeof(int32_t) * (size_t)(s->nslices * SELL_S), hipMemcpyDeviceToDevice, st));
     k_map_i32<<<dim3((unsigned)phx_div_up(s->nslices * SELL_S, 256)), block, 0, st>>>(s->nslices * SELL_S, s->iperm, s->sell_rows);
     int64_t *widths = nullptr;
@@ -920,7 +890,7 @@ int phx_system_build_structured(phx_system *s, const phx_slot_view &sv, int32_t 
     PHX_HIP(phx_exclusive_sum(t2, b2, widths, s->slice_ptr, (size_t)(s->nslices + 1), st));
     PHX_HIP(hipMemcpyAsync(&s->sell_nnz, s->slice_ptr + s->nslices, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     PHX_HIP(hipStreamSynchronize(st));
-    PHX_HIP(phx_free(tmp)); PHX_HIP(phx_free(t2)); PHX_HIP(phx_free(widths)); PHX_HIP(phx_free(keys)); PHX_HIP(phx_free(keys2));
+    PHX_HIP(phx_free(t2)); PHX_HIP(phx_free(widths)); PHX_HIP(phx_free(keys)); PHX_HIP(phx_free(keys2));
   } else {
     PHX_HIP(hipMemsetAsync(s->slice_ptr, 0, sizeof(int64_t), st));
     s->sell_nnz = 0;
@@ -1083,18 +1053,17 @@ k_spmv_sell(int64_t n, int64_t nslices, const int64_t *__restrict__ slice_ptr,
   // Optional XCD-aware block -> slice map (PHX_OPT_SPMV_XCD_GROUP): blocks b and b+8 share an XCD and
   // its L2; inside every run of 8*G consecutive block ids XCD k is handed G CONSECUTIVE slice groups,
   // so the x entries its rows gather stay in one L2.  Speed only: any placement is correct.
-  int64_t bid = blockIdx.x;
-  if (xcd_group < 0) {
-    // contiguous eighths (structured systems: nb_sell is a multiple of 8): XCD k walks the k-th eighth of the stored rows
-    if (bid < nb_sell) bid = (bid & 7) * (nb_sell >> 3) + (bid >> 3);
-  } else if (xcd_group > 0) {
-    const int64_t super = 8 * (int64_t)xcd_group, sg = bid / super;
-    if ((sg + 1) * super <= nb_sell) {
-      const int64_t rem = bid - sg * super;
-      bid = sg * super + (rem & 7) * xcd_group + (rem >> 3);
+  auto sell_slice = [&]() -> int64_t {   // slice of this wavefront (SELL blocks only)
+    int64_t bid = blockIdx.x;
+    if (xcd_group > 0) {   // 0 = none, G > 0 = group
+      const int64_t super = 8 * (int64_t)xcd_group, sg = bid / super;
+      if ((sg + 1) * super <= nb_sell) {
+        const int64_t rem = bid - sg * super;
+        bid = sg * super + (rem & 7) * xcd_group + (rem >> 3);
+      }
     }
-  }
-  const int64_t s = bid * (int64_t)(blockDim.x >> 6) + (threadIdx.x >> 6);
+    return bid * (int64_t)(blockDim.x >> 6) + (threadIdx.x >> 6);
+  };
   double acc = 0.0;
   int64_t row = -1;
   double p0 = 0.0, p1 = 0.0, p2 = 0.0;   // this lane's share of (y, d0), (y, y) and (y, d1)
@@ -1181,7 +1150,7 @@ k_spmv_sell(int64_t n, int64_t nslices, const int64_t *__restrict__ slice_ptr,
     // entries; the four partial sums of a row meet in two shuffles.  The stored rows are few and long (4.9e5 rows
     // of 24-60 entries at 256^3): one lane per row left 7600 wavefronts for the whole chip and the loop latency
     // bound (55 us); a quarter of the trip count and four times the waves.
-    if (s < nslices) {
+    if (const int64_t s = sell_slice(); s < nslices) {
       const int64_t base = slice_ptr[s];
       const int trips = (int)((slice_ptr[s + 1] - base) >> 6);   // width / 4
       const int32_t *c = scol + base + lane;
@@ -1213,7 +1182,7 @@ k_spmv_sell(int64_t n, int64_t nslices, const int64_t *__restrict__ slice_ptr,
         PHX_DOT_ACC(acc, yo);
       }
     }
-  } else if (s < nslices) {
+  } else if (const int64_t s = sell_slice(); s < nslices) {
     const int64_t base = slice_ptr[s];
     const int width = (int)((slice_ptr[s + 1] - base) >> 6);
     const int32_t *c = scol + base + lane;
@@ -1463,7 +1432,6 @@ enum { S_RHO = 0, S_ALPHA = 1, S_OMEGA = 2, S_BB = 3, S_RR = 4, S_RESTARTS = 5, 
        S_MODE = 7 };
 enum { R_RV = 0, R_TS = 1, R_TT = 2, R_SS = 3, R_RHO = 4, R_RR = 5 };
 #define R_OFF 8
-#define S_RR0 14   // S[14 + parity]: (r, r) at the last restart (kr_restart)
 // S_MODE = 1: every dot product is folded into R by k_reduce_slots (and all-reduced by a
 // multi-GPU driver) before its consumer runs.  S_MODE = 0 (native single-GPU loop): consumers
 // fold the 64 slots themselves -- no reduce / roll launches; the slot sets alternate with the
@@ -1561,7 +1529,6 @@ __global__ void k_kr_begin2(double *S, int mode) {
   S[S_RHO_NEXT] = S[R_OFF + R_RHO];
   S[S_BB] = S[R_OFF + R_RHO];
   S[S_RR] = S[R_OFF + R_RHO];
-  S[S_RR0] = S[S_RR0 + 1] = S[R_OFF + R_RHO];
 }
 
 // s = r - alpha v, alpha = rho/(rhat,v)
@@ -1608,14 +1575,8 @@ k_update_xr(int64_t n, int par, const uint8_t *__restrict__ own, const double *_
 // Breakdown guard: when (rhat, r) has collapsed relative to (r, r) (or a scalar went non-finite)
 // the iteration is RESTARTED from the current residual: rhat = p = r, rho = (r, r).  Every thread
 // evaluates the same predicate from the same device scalars.
-// drop2 > 0 (f32 lattice, native loop): ALSO restart whenever (r, r) has fallen by the factor drop2 since the last
-// restart.  With right preconditioning r = b - A x holds for whatever phat / shat were used, so a restart from r is
-// a step of iterative refinement in f64: the rounding noise of the f32 transforms (a slightly non-linear M^-1,
-// which BiCGStab's short recurrences do not tolerate over many iterations) only ever acts over one short cycle.
-// S[14 + par] holds (r, r) at the last restart for the iteration of parity par (read here, the other one written).
-__device__ __forceinline__ bool kr_restart(const double *S, double rho_new, double rr, double drop2 = 0.0, int par = 0) {
+__device__ __forceinline__ bool kr_restart(const double *S, double rho_new, double rr) {
   const double beta = (rho_new / S[S_RHO]) * (S[S_ALPHA] / S[S_OMEGA]);
-  if (drop2 > 0.0 && S[S_MODE] == 0.0 && rr <= drop2 * S[S_RR0 + par]) return true;
   return !(fabs(beta) <= 1.0e300) || !(fabs(rho_new) > 1.0e-14 * rr);
 }
 
@@ -1624,15 +1585,14 @@ __device__ __forceinline__ bool kr_restart(const double *S, double rho_new, doub
 __global__ void __launch_bounds__(256)
 k_update_p(int64_t n, int par, const uint8_t *__restrict__ own, const double *__restrict__ r,
            const double *__restrict__ v, double *__restrict__ p, double *__restrict__ rhat,
-           double *__restrict__ S, double drop2, RestOut ro) {
+           double *__restrict__ S, RestOut ro) {
   const double rho_new = dotv(S, par, R_RHO), rr = dotv(S, par, R_RR);
-  const bool restart = kr_restart(S, rho_new, rr, drop2, par);
+  const bool restart = kr_restart(S, rho_new, rr);
   if (blockIdx.x == 0) {
     if (threadIdx.x == 0) {
       S[S_RHO_NEXT] = restart ? rr : rho_new;
       S[S_RR] = rr;
       if (restart) S[S_RESTARTS] += 1.0;
-      if (S[S_MODE] == 0.0) S[S_RR0 + (par ^ 1)] = restart ? rr : S[S_RR0 + par];
     }
     double *nxt = S + P_OFF + ((par ^ 1) * 8 * NSLOT) * SLOT_STRIDE;
     for (int k = threadIdx.x; k < 8 * NSLOT; k += blockDim.x) nxt[k * SLOT_STRIDE] = 0.0;
@@ -1711,8 +1671,7 @@ static int launch_spmv(phx_system *s, const double *vals, const double *x, doubl
   if (s->n == 0) return PHX_OK;  // empty system (a slab outside the domain): the dot-product slots stay zero
   const dim3 block(256);
   const uint8_t *own = s->own;
-  static const int xg_env = getenv("PHX_SPMV_XCD_GROUP") ? atoi(getenv("PHX_SPMV_XCD_GROUP")) : -1;   // tuning aid
-  const int xg = xg_env >= 0 ? xg_env : s->mesh->spmv_xcd_group;
+  const int xg = s->mesh->spmv_xcd_group;
   const uint8_t *kinds = vals == s->sell_val ? s->sell_kind : s->sell_kind_raw;
   const int32_t *rows = s->structured ? s->sell_rows : nullptr;
   DotPart dp{nullptr, nullptr};
@@ -1733,36 +1692,30 @@ static int launch_spmv(phx_system *s, const double *vals, const double *x, doubl
   // the SELL blocks of the same launch
   StencilArgs sa{0, nullptr, 0, nullptr, nullptr, 0, nullptr};
   int64_t nb_sell = phx_div_up(s->nslices, 4);
-  static const int part = getenv("PHX_SPMV_PART") ? atoi(getenv("PHX_SPMV_PART")) : 0;  // timing aid: 1 SELL only, 2 stencil only
-  if (part == 2) nb_sell = 0;
-  int64_t nb = nb_sell;
-  static const int sell_xcd = getenv("PHX_SELL_XCD") ? atoi(getenv("PHX_SELL_XCD")) : 0;   // experiment: 1 = contiguous eighths
   // structured systems: a multiple of 8 SELL blocks (the surplus finds no slice), so that blockIdx % 8 is the XCD
   if (s->structured) nb_sell = (nb_sell + 7) & ~(int64_t)7;
-  nb = nb_sell;
-  if (s->structured && s->nseg > 0 && part != 1) {
+  int64_t nb = nb_sell;
+  if (s->structured && s->nseg > 0) {
     // the stencil blocks start at a multiple of 8 so that blockIdx % 8 (the XCD a block lands on) is theirs to
     // use: XCD k walks the k-th contiguous eighth of the rows, whose x entries then stay in ITS 4 MiB L2
     // (round-robin placement had every L2 fetch the whole vector: 3.5 x the bytes, 44 % hits)
-    nb_sell = (nb_sell + 7) & ~(int64_t)7;
     const int64_t nbst = phx_div_up(phx_div_up(s->nstencil_pos, 64), 16);   // four waves per block, four slices per wave
     sa = StencilArgs{s->nstencil_pos, s->seg, s->nseg, s->slice_seg, s->stencil, (nbst + 7) / 8, nullptr};
     if (s->st_map) { sa.chunk = s->st_chunk; sa.map = s->st_map; }
     nb = nb_sell + 8 * sa.chunk;
   }
-  const int xg2 = (sell_xcd == 1 && s->structured && nb_sell % 8 == 0 && nb_sell > 0) ? -1 : xg;
   if (nb == 0 && !s->p2s) return PHX_OK;
   const dim3 g2((unsigned)std::max<int64_t>(nb, 1));
   if (dots > 0 && nb > 0) PHX_CHECK(det_part(s, nb, &dp));
   if (nb == 0) {}
   else if (dots == 0)
-    k_spmv_sell<0><<<g2, block, 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, vals, x, y, own, d0, o0, o1, xg2, kinds, rows, nb_sell, sa, bnd, dp, nullptr, nullptr);
+    k_spmv_sell<0><<<g2, block, 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, vals, x, y, own, d0, o0, o1, xg, kinds, rows, nb_sell, sa, bnd, dp, nullptr, nullptr);
   else if (dots == 1)
-    k_spmv_sell<1><<<g2, block, 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, vals, x, y, own, d0, o0, o1, xg2, kinds, rows, nb_sell, sa, bnd, dp, nullptr, nullptr);
+    k_spmv_sell<1><<<g2, block, 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, vals, x, y, own, d0, o0, o1, xg, kinds, rows, nb_sell, sa, bnd, dp, nullptr, nullptr);
   else
-    k_spmv_sell<2><<<g2, block, 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, vals, x, y, own, d0, o0, o1, xg2, kinds, rows, nb_sell, sa, bnd, dp, nullptr, nullptr);
+    k_spmv_sell<2><<<g2, block, 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, vals, x, y, own, d0, o0, o1, xg, kinds, rows, nb_sell, sa, bnd, dp, nullptr, nullptr);
   PHX_HIP(hipGetLastError());
-  if (s->p2s && s->p2s->nrun > 0 && part_of == 0 && part != 1) {
+  if (s->p2s && s->p2s->nrun > 0 && part_of == 0) {
     // structured P2: the interior rows from the eight class stencils, one wavefront per run
     const phx_p2_struct *ps = s->p2s;
     const dim3 gp((unsigned)std::min<int64_t>(phx_div_up(ps->nrun, 4), 4096));
@@ -1917,17 +1870,6 @@ static int prof_collect(phx_system *s, double *avg_s, int *count, int c = 0) {
 #include "phx_coarse.inc.hip"
 void phx_blockjac_destroy(phx_blockjac *b) { blockjac_free(b); }
 
-// restart threshold of the native loop: ratio of |r| since the last restart below which BiCGStab restarts from r
-// (PHX_RESTART_DROP, e.g. 1e-4; default 0 = only on breakdown).  Measured with f32 transforms (round 2): the 3-D
-// problems converge as with f64 transforms with or without it; the 2-D flower problem stays erratic (100-600
-// iterations against 36-66) for every threshold tried -- refinement restarts are not what that problem lacks.
-static double kr_drop2(const phx_system *s) {
-  static const double env = getenv("PHX_RESTART_DROP") ? atof(getenv("PHX_RESTART_DROP")) : 0.0;
-  (void)s;
-  return env > 0.0 ? env * env : 0.0;
-}
-
-
 // Structured systems without the box preconditioner (configured out, vetoed, box too long): their u columns are
 // unscaled, so the Jacobi scaling of the u block is applied here: P = D_u^-1 on u rows, the identity elsewhere
 // (diag is stored in active order: through perm).
@@ -1965,7 +1907,7 @@ k_restart_from_r(int64_t n, const double *__restrict__ r, double *__restrict__ r
   if (cmask) block_atomic_sum(accc, slot_base(S, par, R_RV), part.p0);
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     const double rr = S[R_OFF + R_RR];
-    S[S_RHO] = rr; S[S_RHO_NEXT] = rr; S[S_RR] = rr; S[S_RR0] = rr; S[S_RR0 + 1] = rr;
+    S[S_RHO] = rr; S[S_RHO_NEXT] = rr; S[S_RR] = rr;
     S[S_ALPHA] = 1.0; S[S_OMEGA] = 1.0;
     S[S_RESTARTS] += 1.0;
   }
@@ -2048,7 +1990,6 @@ k_ident_xrp(int64_t n, int par, const uint32_t *__restrict__ cmask, const double
     S[S_RHO_NEXT] = restart ? rr : rho_new;
     S[S_RR] = rr;
     if (restart) S[S_RESTARTS] += 1.0;
-    S[S_RR0 + (par ^ 1)] = restart ? rr : S[S_RR0 + par];
   }
   double arr = 0.0, apc = 0.0;
   GRID_STRIDE(i, n) {
@@ -2118,7 +2059,7 @@ k_red_from(int64_t nb, const int32_t *__restrict__ rows, int64_t nu, const doubl
 // recurrences (re)started from r: rho = (r, r) = R[R_RR]
 __global__ void k_red_rho(double *S, int restart) {
   const double rr = S[R_OFF + R_RR];
-  S[S_RHO] = rr; S[S_RHO_NEXT] = rr; S[S_RR] = rr; S[S_RR0] = rr; S[S_RR0 + 1] = rr;
+  S[S_RHO] = rr; S[S_RHO_NEXT] = rr; S[S_RR] = rr;
   S[S_ALPHA] = 1.0; S[S_OMEGA] = 1.0;
   if (restart) S[S_RESTARTS] += 1.0;
 }
@@ -2180,7 +2121,6 @@ k_red_xrp(int64_t nb, int par, const int32_t *__restrict__ rows, int64_t nu, con
     S[S_RHO_NEXT] = restart ? rr : rho_new;
     S[S_RR] = rr;
     if (restart) S[S_RESTARTS] += 1.0;
-    S[S_RR0 + (par ^ 1)] = restart ? rr : S[S_RR0 + par];
   }
   double arr = 0.0;
   GRID_STRIDE(k, nb) {
@@ -2234,8 +2174,7 @@ static inline KrRed kr_red_vecs(phx_system *s) {
 // the stencil row equal to the lattice row {2 (cx + cy + cz), -cx, -cy, -cz} of K_box (read once per system).
 static int kr_identity(phx_system *s, bool *on) {
   *on = false;
-  static const int env = getenv("PHX_KR_IDENTITY") ? atoi(getenv("PHX_KR_IDENTITY")) : 1;
-  if (!env || !s->structured || !s->u_unscaled || s->u_weighted || s->p2s || s->precond_state != 1 || !s->precond ||
+  if (!phx_sw_kr_identity() || !s->structured || !s->u_unscaled || s->u_weighted || s->p2s || s->precond_state != 1 || !s->precond ||
       s->precond->f32 || s->precond->dist || s->own || s->kr_work || s->bnd || s->nseg <= 0 || s->n == 0)
     return PHX_OK;
   hipStream_t st = s->mesh->stream;
@@ -2265,9 +2204,8 @@ static int kr_identity(phx_system *s, bool *on) {
 // built on the first solve of the system.
 static int kr_reduced(phx_system *s, bool *on) {
   *on = false;
-  static const int env = getenv("PHX_KR_REDUCED") ? atoi(getenv("PHX_KR_REDUCED")) : 1;
   const phx_box_precond *bp = s->precond;
-  if (!env || s->n_sell_rows <= 0 || bp->dscale || bp->iscale || !bp->line_iv) return PHX_OK;
+  if (!phx_sw_kr_reduced() || s->n_sell_rows <= 0 || bp->dscale || bp->iscale || !bp->line_iv) return PHX_OK;
   if (!s->kr_red) PHX_HIP(phx_malloc(&s->kr_red, sizeof(double) * (size_t)(7 * s->nslices * SELL_S + s->n)));
   PHX_CHECK(box_red_maps(s));
   *on = true;
@@ -2284,8 +2222,7 @@ static int launch_spmv_stored_t(phx_system *s, const double *x, double *y, int d
   hipStream_t st = s->mesh->stream;
   const int64_t nb = (phx_div_up(s->nslices, 4) + 7) & ~(int64_t)7;   // a multiple of 8, as launch_spmv
   if (nb == 0) return PHX_OK;
-  static const int xg_env = getenv("PHX_SPMV_XCD_GROUP") ? atoi(getenv("PHX_SPMV_XCD_GROUP")) : -1;
-  const int xg = xg_env >= 0 ? xg_env : s->mesh->spmv_xcd_group;
+  const int xg = s->mesh->spmv_xcd_group;
   const StencilArgs sa{0, nullptr, 0, nullptr, nullptr, 0, nullptr};
   DotPart dp{nullptr, nullptr};
   if (dots > 0) PHX_CHECK(det_part(s, nb, &dp));
@@ -2454,7 +2391,7 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
       if (mode) k_reduce_slots<<<1, 64, 0, st>>>(S, par, R_RHO, 2, 1);
       break;
     case KR_UPDATE_P:
-      k_update_p<<<vec_grid(n), block, 0, st>>>(n, par, s->own, V.r, V.v, V.p, V.rhat, S, kr_drop2(s), rop);
+      k_update_p<<<vec_grid(n), block, 0, st>>>(n, par, s->own, V.r, V.v, V.p, V.rhat, S, rop);
       break;
     case KR_PRECOND_P:
       if (s->precond_state == 1) {
@@ -2955,8 +2892,6 @@ extern "C" int phx_spmv(phx_system *s, const double *x, double *y, int loc) {
   return PHX_OK;
 }
 
-#include "phx_spmv_exp.inc.hip"
-
 extern "C" int phx_spmv_bench(phx_system *s, int reps, double *out) {
   phx_mesh *m = s->mesh;
   PHX_HIP(hipSetDevice(m->device));
@@ -2964,28 +2899,6 @@ extern "C" int phx_spmv_bench(phx_system *s, int reps, double *out) {
   hipStream_t st = m->stream;
   double *xs = s->work + 6 * n, *ys = s->work + 7 * n;
   PHX_HIP(hipMemcpyAsync(xs, s->rhs, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
-  if (const char *e = getenv("PHX_SELL_EXP")) {
-    // load-schedule experiments on the stored rows alone (phx_spmv_exp.inc.hip); out[1] = max |y_exp - y| over them
-    PHX_REQUIRE(s->structured && s->n_sell_rows > 0, PHX_ERR_VALUE, "PHX_SELL_EXP needs a structured system");
-    const int var = atoi(e);
-    PHX_CHECK(launch_spmv(s, s->sell_val, xs, ys, 0, nullptr, nullptr, nullptr));
-    double *ye = s->work + 5 * n;
-    PHX_HIP(hipMemcpyAsync(ye, ys, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
-    for (int i = 0; i < 3; ++i) PHX_CHECK(launch_sell16_exp(s, var, s->sell_val, xs, ye));
-    PHX_HIP(hipEventRecord(m->ev0, st));
-    for (int i = 0; i < reps; ++i) PHX_CHECK(launch_sell16_exp(s, var, s->sell_val, xs, ye));
-    PHX_HIP(hipEventRecord(m->ev1, st));
-    PHX_HIP(hipEventSynchronize(m->ev1));
-    float ms = 0.f;
-    PHX_HIP(hipEventElapsedTime(&ms, m->ev0, m->ev1));
-    std::vector<double> a((size_t)n), b((size_t)n);
-    PHX_HIP(hipMemcpy(a.data(), ys, sizeof(double) * n, hipMemcpyDeviceToHost));
-    PHX_HIP(hipMemcpy(b.data(), ye, sizeof(double) * n, hipMemcpyDeviceToHost));
-    double d = 0.0;
-    for (int64_t i = 0; i < n; ++i) d = std::max(d, fabs(a[i] - b[i]));
-    out[0] = (double)ms / reps; out[1] = d; out[2] = 12.0 * (double)s->sell_nnz;
-    return PHX_OK;
-  }
   for (int i = 0; i < 3; ++i)
     PHX_CHECK(launch_spmv(s, s->sell_val, xs, ys, 0, nullptr, nullptr, nullptr));
   PHX_HIP(hipEventRecord(m->ev0, st));

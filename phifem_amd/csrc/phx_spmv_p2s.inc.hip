@@ -119,22 +119,21 @@ k_sell_fill_slots_wide(int64_t ns, const int32_t *__restrict__ rows, phx_slot_vi
 // x lines, and the gathers of the stored rows cost 530 of 911 us at 256^3 (the same stream without the gathers: 378 us).
 // With the tile on top a slice's rows are neighbours (u and p rows of one tile^3 block of fine points, longest first
 // inside the tile) and gather from one small neighbourhood.
+#define P2S_TILE 16   // fine points per tile edge (doubled while the tile index would not fit 22 key bits)
+#define P2S_LENQ 4    // length step of the key
 __global__ void k_p2s_stored_keys(int64_t ns, const int32_t *__restrict__ list, const int32_t *__restrict__ len,
                                   uint32_t *__restrict__ keys, const int64_t *__restrict__ full, int64_t nent,
-                                  phx_p2_lattice L, int tile, int t0, int t1, int lenq) {
+                                  phx_p2_lattice L, int tile, int t0, int t1) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= ns) return;
-  // ascending key = descending length, in steps of lenq entries (a slice is padded to a multiple of four anyway): rows
-  // of one step keep their lattice order
-  uint32_t key = (uint32_t)(1023 - min((len[i] + lenq - 1) / lenq * lenq, 1023));
-  if (tile > 0) {
-    int64_t e = full[list[i]];
-    if (e >= nent) e -= nent;
-    int64_t q[3];
-    phx_p2_fine_of_entity(L, e, q);
-    key |= (uint32_t)(((q[2] / tile) * t1 + q[1] / tile) * t0 + q[0] / tile) << 10;
-  }
-  keys[i] = key;
+  // ascending key = descending length, in steps of P2S_LENQ entries (a slice is padded to a multiple of four anyway):
+  // rows of one step keep their lattice order
+  const uint32_t key = (uint32_t)(1023 - min((len[i] + P2S_LENQ - 1) / P2S_LENQ * P2S_LENQ, 1023));
+  int64_t e = full[list[i]];
+  if (e >= nent) e -= nent;
+  int64_t q[3];
+  phx_p2_fine_of_entity(L, e, q);
+  keys[i] = key | (uint32_t)(((q[2] / tile) * t1 + q[1] / tile) * t0 + q[0] / tile) << 10;
 }
 
 int phx_system_build_structured_p2(phx_system *s, const phx_slot_view &sv, int32_t nent, const uint8_t *latc0,
@@ -210,18 +209,14 @@ int phx_system_build_structured_p2(phx_system *s, const phx_slot_view &sv, int32
     PHX_HIP(phx_malloc(&keys, sizeof(uint32_t) * (size_t)ns));
     PHX_HIP(phx_malloc(&keys2, sizeof(uint32_t) * (size_t)ns));
     const dim3 gs((unsigned)phx_div_up(ns, 256));
-    static const int tile_env = getenv("PHX_P2S_TILE") ? atoi(getenv("PHX_P2S_TILE")) : 16;   // 0: by length alone
-    int tile = tile_env, tn[3] = {1, 1, 1}, key_bits = 10;
-    if (tile > 0) {
+    int tile = P2S_TILE, tn[3], key_bits = 10;
+    for (int a = 0; a < 3; ++a) tn[a] = (int)(L.F[a] / tile + 1);
+    while ((int64_t)tn[0] * tn[1] * tn[2] > (1ll << 22)) {   // 22 + 10 key bits
+      tile *= 2;
       for (int a = 0; a < 3; ++a) tn[a] = (int)(L.F[a] / tile + 1);
-      while (tile > 0 && (int64_t)tn[0] * tn[1] * tn[2] > (1ll << 22)) {   // 22 + 10 key bits
-        tile *= 2;
-        for (int a = 0; a < 3; ++a) tn[a] = (int)(L.F[a] / tile + 1);
-      }
-      while ((1ll << (key_bits - 10)) < (int64_t)tn[0] * tn[1] * tn[2]) ++key_bits;
     }
-    static const int lenq = getenv("PHX_P2S_LENQ") ? std::max(1, atoi(getenv("PHX_P2S_LENQ"))) : 4;
-    k_p2s_stored_keys<<<gs, block, 0, st>>>(ns, list, len, keys, s->full_of_active, (int64_t)nent, L, tile, tn[0], tn[1], lenq);
+    while ((1ll << (key_bits - 10)) < (int64_t)tn[0] * tn[1] * tn[2]) ++key_bits;
+    k_p2s_stored_keys<<<gs, block, 0, st>>>(ns, list, len, keys, s->full_of_active, (int64_t)nent, L, tile, tn[0], tn[1]);
     k_fill_i32<<<dim3((unsigned)phx_div_up(s->nslices * SELL_S, 256)), block, 0, st>>>(s->nslices * SELL_S, rows_active, -1, 0);
     size_t bytes = 0;
     PHX_HIP(phx_sort_pairs(nullptr, bytes, keys, keys2, list, rows_active, (size_t)ns, 0, key_bits, st));

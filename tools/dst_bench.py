@@ -1,5 +1,5 @@
 """Times the sine-transform passes of the preconditioner lattice (development aid).
-usage: dst_bench.py L0 L1 L2 [f32=1] [reps=50]; tile sizes via PHX_DST_LDS_KB"""
+usage: dst_bench.py L0 L1 L2 [f32=1] [reps=50]"""
 import ctypes as C
 import os
 import sys
@@ -15,6 +15,6 @@ out = (C.c_double * 3)()
 L.check(L.lib.phx_box_dst_bench(0, (C.c_int * 3)(*Ls), f32, reps, out))
 pts = (Ls[0] - 1) * (Ls[1] - 1) * (Ls[2] - 1)
 b = 2 * (4 if f32 else 8) * pts
-print(f"L={Ls} f32={f32} LDS_KB={os.environ.get('PHX_DST_LDS_KB', 'default')}: "
+print(f"L={Ls} f32={f32}: "
       f"x {out[0]:.1f} us ({b / out[0] / 1e6:.2f} TB/s)  y {out[1]:.1f} us ({b / out[1] / 1e6:.2f} TB/s)  "
       f"z-solve {out[2]:.1f} us ({b / out[2] / 1e6:.2f} TB/s)", flush=True)

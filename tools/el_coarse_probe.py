@@ -4,8 +4,7 @@ import os, sys, subprocess, json
 if len(sys.argv) > 2 and sys.argv[1] != "--child":
     n = sys.argv[1]
     for ratio in sys.argv[2:]:
-        env = dict(os.environ, PHX_EL_COARSE=ratio)
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", n], env=env, capture_output=True, text=True)
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", n, ratio], capture_output=True, text=True)
         print(f"ratio {ratio}: {r.stdout.strip()} {r.stderr.strip()[-300:] if r.returncode else ''}", flush=True)
     sys.exit(0)
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -13,7 +12,7 @@ import warnings
 import torch
 from phifem_amd.distributed import ElasticitySlabProblem
 n = int(sys.argv[2])
-p = ElasticitySlabProblem(n, n, rtol=1e-8)
+p = ElasticitySlabProblem(n, n, rtol=1e-8, coarse=int(sys.argv[3]))   # PHX_OPT_EL_COARSE
 p.setup()
 warnings.simplefilter("ignore")
 p.step()
