@@ -223,6 +223,10 @@ enum phx_option {
                                h/2-lattice sine transform on u and Jacobi on p.  0 (default): off; -1: automatic (ratio
                                and on/off chosen by the library); >= 5: this ratio; 1..4: PHX_ERR_VALUE.
                                Built on the first solve of a system; phx_coarse_info reports it            */
+  PHX_OPT_BOX_TAGS = 13, /* 1 (default): generated 3-D Kuhn boxes are tagged by kernels that take one thread per cube
+                               and the connectivity in closed form (cells, single-layer passes); 0: the generic
+                               kernels that stream `cells` run on them too.  Same tags, bit for bit: 0 is the
+                               reference path of tests/test_box_closed_form_tags.py                          */
   PHX_OPT_ALLOW_EMPTY = 6, /* 1: phx_assemble_poisson_wd returns an EMPTY system (n_active = 0) when no cell
                                is tagged 1 / 2 instead of PHX_ERR_VALUE: a slab of a partitioned box that
                                does not touch the domain still joins every collective of the solve          */

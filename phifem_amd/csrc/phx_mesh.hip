@@ -1223,6 +1223,7 @@ extern "C" int phx_set_option(phx_mesh *m, int option, int64_t value) {
     case PHX_OPT_ALLOW_EMPTY: m->allow_empty = value != 0; return PHX_OK;
     case PHX_OPT_EXPORT_CSR: m->export_csr = value != 0; return PHX_OK;
     case PHX_OPT_STRUCTURED: m->structured = value != 0; return PHX_OK;
+    case PHX_OPT_BOX_TAGS: m->box_tags = value != 0; return PHX_OK;
     case PHX_OPT_DETERMINISTIC: m->deterministic = value != 0; return PHX_OK;
     case PHX_OPT_EL_COARSE:
       PHX_REQUIRE(value == -1 || value == 0 || (value >= 5 && value <= 4096), PHX_ERR_VALUE, "coarse ratio %lld: -1, 0 or >= 5", (long long)value);

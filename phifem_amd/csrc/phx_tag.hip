@@ -444,6 +444,8 @@ __global__ void k_entities(int64_t nlist, const int32_t *__restrict__ list,
   if (!FILL) { cnt0[i] = w == 0 ? n : 0; cnt1[i] = w == 1 ? n : 0; }
 }
 
+#include "phx_tag_box.inc.hip"
+
 // ------------------------------------------------------------------------------------------
 static int make_tab(const phx_mesh *m, int degree, int which, DetTab *tab) {
   std::vector<double> t;
@@ -530,7 +532,15 @@ extern "C" int phx_tag_cells(phx_mesh *m, int phi_kind, const double *phi, int l
   PHX_HIP(phx_malloc(&dwarn, sizeof(int)));
   PHX_HIP(hipMemsetAsync(dwarn, 0, sizeof(int), m->stream));
   PHX_CHECK(phx_begin_timing(m));
-  if (phi_kind == PHX_PHI_NODAL_P1) PHX_CHECK(launch_tag_cells<PHX_PHI_NODAL_P1>(m, tab, dphi, quad, dwarn));
+  // generated 3-D boxes: one thread per cube, connectivity in closed form (phx_tag_box.inc.hip)
+  const bool box = box_tags_apply(m);
+  BoxTagGeo bg;
+  dim3 bgrid, bblock;
+  if (box) box_tag_launch_dims(m, &bg, &bgrid, &bblock);
+  if (box && phi_kind == PHX_PHI_NODAL_P1) {
+    k_box_tag_cells<<<bgrid, bblock, 0, m->stream>>>(bg, tab, dphi, m->x, m->cell_tags, dwarn);
+    PHX_HIP(hipGetLastError());
+  } else if (phi_kind == PHX_PHI_NODAL_P1) PHX_CHECK(launch_tag_cells<PHX_PHI_NODAL_P1>(m, tab, dphi, quad, dwarn));
   else if (phi_kind == PHX_PHI_POINTS) PHX_CHECK(launch_tag_cells<PHX_PHI_POINTS>(m, tab, dphi, quad, dwarn));
   else PHX_CHECK(launch_tag_cells<PHX_PHI_QUADRIC>(m, tab, dphi, quad, dwarn));
   uint8_t *touched = nullptr, *vcut = nullptr;
@@ -544,7 +554,8 @@ extern "C" int phx_tag_cells(phx_mesh *m, int phi_kind, const double *phi, int l
     vcut = m->act_cut;
     PHX_HIP(hipMemsetAsync(vcut, 0, (size_t)m->nv, m->stream));
     PHX_HIP(hipMemsetAsync(touched, 0, (size_t)m->nv, m->stream));
-    if (m->ci.nvpc == 3) k_mark_inside_vertices<3><<<grid4, block4, 0, m->stream>>>(m->nc, m->cells, m->cell_tags, touched);
+    if (box) k_box_mark_inside<<<bgrid, bblock, 0, m->stream>>>(bg, m->cell_tags, touched);
+    else if (m->ci.nvpc == 3) k_mark_inside_vertices<3><<<grid4, block4, 0, m->stream>>>(m->nc, m->cells, m->cell_tags, touched);
     else k_mark_inside_vertices<4><<<grid4, block4, 0, m->stream>>>(m->nc, m->cells, m->cell_tags, touched);
   }
   // demotion of isolated cut cells (if asked for) + histogram + per-chunk counts of the cut cells, in one pass
@@ -552,15 +563,17 @@ extern "C" int phx_tag_cells(phx_mesh *m, int phi_kind, const double *phi, int l
   uint32_t *part = nullptr;
   const int64_t nchunks = phx_div_up(m->nc > 0 ? m->nc : 1, (int64_t)PHX_SEL_CHUNK);
   PHX_HIP(phx_malloc(&dres, sizeof(unsigned long long) * 4));
-  PHX_HIP(phx_malloc(&part, sizeof(uint32_t) * 4 * (size_t)grid4.x));
+  const int64_t npart = box ? (int64_t)bgrid.x * bgrid.y * bgrid.z : (int64_t)grid4.x;   // blocks of the counting kernel
+  PHX_HIP(phx_malloc(&part, sizeof(uint32_t) * 4 * (size_t)npart));
   PHX_HIP(hipMemsetAsync(dres, 0, sizeof(unsigned long long) * 4, m->stream));
   if (!m->sel_counts_cut) PHX_HIP(phx_malloc(&m->sel_counts_cut, sizeof(int32_t) * (size_t)(nchunks + 1)));
   PHX_HIP(hipMemsetAsync(m->sel_counts_cut, 0, sizeof(int32_t) * (size_t)(nchunks + 1), m->stream));
-  if (m->ci.nvpc == 3) k_demote_isolated_cut<3><<<grid4, block4, 0, m->stream>>>(m->nc, m->cells, m->cell_tags, touched, part, m->sel_counts_cut, vcut);
+  if (box) k_box_demote_count<<<bgrid, bblock, 0, m->stream>>>(bg, m->cell_tags, touched, part, m->sel_counts_cut, vcut);
+  else if (m->ci.nvpc == 3) k_demote_isolated_cut<3><<<grid4, block4, 0, m->stream>>>(m->nc, m->cells, m->cell_tags, touched, part, m->sel_counts_cut, vcut);
   else k_demote_isolated_cut<4><<<grid4, block4, 0, m->stream>>>(m->nc, m->cells, m->cell_tags, touched, part, m->sel_counts_cut, vcut);
   PHX_HIP(hipGetLastError());
   PHX_CHECK(phx_end_timing_mark(m));
-  k_hist_fold<<<dim3(64, 4), dim3(256), 0, m->stream>>>((int64_t)grid4.x, part, dres);
+  k_hist_fold<<<dim3(64, 4), dim3(256), 0, m->stream>>>(npart, part, dres);
   // one host round trip for the histogram, the warning flag and the timing events
   int hwarn = 0;
   unsigned long long hh[4] = {0, 0, 0, 0};
