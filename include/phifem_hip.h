@@ -73,7 +73,9 @@ enum phx_array {          /* phx_mesh_get_array selectors */
                              ascending facet index                        */
   PHX_ARR_C2E = 7,        /* i32 [nc*nepc] cell -> edges (P2 DoFs), local edge order of basix:
                              triangle (1,2),(0,2),(0,1); tetrahedron (2,3),(1,3),(1,2),(0,3),(0,2),(0,1) */
-  PHX_ARR_EDGES = 8       /* i32 [ne*2] vertex pair of every edge, ascending */
+  PHX_ARR_EDGES = 8,      /* i32 [ne*2] vertex pair of every edge, ascending */
+  PHX_ARR_PARENT_CELLS = 9, /* i32 [nc]     meshes made by phx_mesh_refine_marked: coarse cell of every cell      */
+  PHX_ARR_CHILD_NODES = 10  /* i8 [nc*nvpc] the same: local degree-2 nodes of the parent, the cell's leaf tuple  */
 };
 
 /* ------------------------------------------------------------------ misc ------------- */
@@ -357,6 +359,47 @@ int phx_mesh_refine(phx_mesh *m, phx_mesh **fine);
 int phx_prolongate(phx_mesh *coarse, phx_mesh *fine, int degree, int ncomp, const double *in, int loc_in,
                    double *out, int loc_out);
 int phx_refine_tables(int cell_type, int32_t *children, int *nchild, double *p2_weights);
+
+/* --- marked refinement of triangle and tetrahedron meshes ------------------------------------
+ * Stands in for dolfinx.mesh.refine with marked edges (longest-edge bisection with closure); tests/refine_marked_ref.py
+ * restates the rule in numpy, and the device result equals it bit for bit.
+ *
+ * cell_marks[nc], edge_marks[ne] (uint8, non-zero = marked, at `loc`; edge ids as PHX_ARR_EDGES / PHX_ARR_C2E, in 2-D
+ * the edges are the facets); either may be NULL.  Both NULL: a copy, one child per cell.
+ *
+ * EDGE ORDER, strict and total: the key of edge (p, q), p < q, is len2 = ((dx dx + dy dy) + dz dz), d = x[q] - x[p],
+ * evaluated without contraction.  The greater len2 wins; on equal len2 the lexicographically smaller (p, q) wins.  It
+ * depends on coordinates and vertex ids only.
+ *   1. Seed: a marked cell marks all its edges; the edge mask is OR-ed in.
+ *   2. Closure, the least fixed point of: every cell with a marked edge gets its greatest edge marked; in 3-D every
+ *      face with a marked edge gets its greatest edge marked.  (Monotone: independent of sweep order and races.  One
+ *      lane per cell and sweep, marks are byte stores of 1, the host reads one 4-byte flag per sweep.)
+ *   3. Subdivision: a sub-simplex is a tuple of nvpc local degree-2 nodes of the coarse cell (0 .. nvpc-1 its vertices,
+ *      nvpc + k the midpoint of local edge k), starting with (0, .., nvpc-1).  While it holds both end nodes of a
+ *      marked coarse edge: take the greatest such edge, at positions i < j, m its midpoint node; child 0 is the tuple
+ *      with position j replaced by m, child 1 with position i replaced by m.  Depth first, child 0 first; the leaves in
+ *      the order reached are the children: 1-4 per triangle, 1-8 per tetrahedron.  How a face is split depends only on
+ *      its own marked edges and the order, so neighbours agree: the result is conforming.  Orientation signs are not
+ *      kept.
+ *   4. Numbering: fine vertex v < nv is coarse vertex v; the midpoint 0.5 x_p + 0.5 x_q of marked edge e is nv + rank(e),
+ *      the rank among the marked edges by ascending id.  The children of cell c are the fine cells off[c] .. off[c+1]-1,
+ *      off the exclusive sum of the child counts.
+ *   5. *fine is an ordinary untagged mesh (never a lattice, whatever stood behind the coarse one) that remembers the
+ *      mesh it came from and carries PHX_ARR_PARENT_CELLS and PHX_ARR_CHILD_NODES (the leaf tuples).
+ * info (nullable) = {marked edges after the closure, closure sweeps run, fine cells}.
+ * PHX_ERR_NOT_IMPLEMENTED: quadrilaterals (hanging nodes); PHX_ERR_VALUE: slab with declared cut faces, counts of the
+ * all-marked case beyond the 32-bit id limits (checked before anything is allocated).  Temporaries are released on
+ * every exit (phx_pool_stats live bytes return to where they were).
+ *
+ * phx_prolongate accepts such a fine mesh (simplices, degree 1 and 2):
+ *   degree 1: copy at the coarse vertices, 0.5 u_p + 0.5 u_q at the new ones -- the coordinate arithmetic.
+ *   degree 2: the first nv values are copies, fine vertex nv + rank(e) copies the coarse edge DoF of e; a fine edge DoF
+ *     is the parent's P2 function at the fine edge's midpoint: lambda = mean of the barycentrics of its two child
+ *     nodes, weights lambda_i (2 lambda_i - 1), 4 lambda_i lambda_j (exact: all lambda are multiples of 1/4), summed
+ *     over the parent's local DoFs in ascending order with zero weights skipped.  The LOWEST-NUMBERED parent cell that
+ *     contains the fine edge writes it (integer min pass, then a write pass): the same bits on every run. */
+int phx_mesh_refine_marked(phx_mesh *m, const uint8_t *cell_marks, const uint8_t *edge_marks, int loc, phx_mesh **fine,
+                           int64_t *info);
 
 /* --- point location and evaluation of Lagrange functions at arbitrary points -----------------
  * Stands in for dolfinx's Function.eval with a bounding-box tree and for interpolate_nonmatching;

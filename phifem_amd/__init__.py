@@ -11,8 +11,8 @@ Host side (this package) mirrors the reference's interface for the path:
     demo/neumann/square/main.py:49-158 (quadrilaterals)
   * `phifem_amd.partition_cells`, `phifem_amd.distributed.PartitionedProblem`  <- no counterpart: unstructured
     background meshes partitioned over the ranks (the reference is serial, src/phifem/mesh_scripts.py:264)
-  * `phifem_amd.refine`, `phifem_amd.prolongate`     <- dolfinx.mesh.refine (demo/interface-elasticity/main.py:390)
-    and the nested coarse -> fine transfer of P1 / P2 nodal functions
+  * `phifem_amd.refine`, `phifem_amd.prolongate`     <- dolfinx.mesh.refine (demo/interface-elasticity/main.py:390),
+    uniform or marked by a cell / edge mask, and the nested coarse -> fine transfer of P1 / P2 nodal functions
   * `phifem_amd.locate`, `phifem_amd.evaluate`, `phifem_amd.interpolate_nonmatching`  <- dolfinx `Function.eval`
     with a bounding-box tree and `interpolate_nonmatching`: P1 / P2 / Q1 functions at arbitrary points
   * `phifem_amd.estimate`, `phifem_amd.mark_dorfler` <- no counterpart (dolfinx users write the residual forms in UFL):

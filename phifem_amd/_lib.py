@@ -32,7 +32,7 @@ PHI_NODAL_P1, PHI_POINTS, PHI_QUADRIC = 0, 1, 2
  OPT_BOX_TAGS) = (
     1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13)
 (ARR_COORDS, ARR_CELLS, ARR_C2F, ARR_F2C, ARR_CELL_TAGS, ARR_FACET_TAGS, ARR_BFACETS, ARR_C2E,
- ARR_EDGES) = range(9)
+ ARR_EDGES, ARR_PARENT_CELLS, ARR_CHILD_NODES) = range(11)
 
 OK, ERR_VALUE, ERR_NOT_IMPLEMENTED, ERR_HIP, ERR_PARTITION, ERR_CAPACITY, ERR_BREAKDOWN, ERR_TIMEOUT = (
     0, -1, -2, -3, -4, -5, -6, -7)
@@ -107,6 +107,7 @@ SIGNATURES = {
     "phx_mesh_refine": ([_vp, C.POINTER(_vp)], _i),
     "phx_prolongate": ([_vp, _vp, _i, _i, _vp, _i, _vp, _i], _i),
     "phx_refine_tables": ([_i, _vp, _pi, _vp], _i),
+    "phx_mesh_refine_marked": ([_vp, _vp, _vp, _i, C.POINTER(_vp), _pi64], _i),
     "phx_locate_points": ([_vp, _i64, _vp, _i, _d, _vp, _vp, _i], _i),
     "phx_eval_points": ([_vp, _i, _i, _vp, _i, _i64, _vp, _vp, _i, _i, _d, _vp, _vp, _i], _i),
     "phx_locator_info": ([_vp, _pi64], _i),

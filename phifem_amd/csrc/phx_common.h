@@ -82,6 +82,13 @@ struct phx_mesh {
   // uniform refinement (phx_refine.inc.hip): uid of the mesh this one was refined from (0: none), children per cell
   uint64_t refined_from = 0;
   int refine_nchild = 0;
+  // marked refinement (phx_refine_marked.inc.hip): the fine mesh keeps, on the device, the parent of every cell, the
+  // leaf tuples (local degree-2 nodes of the parent) and the coarse edge behind every new vertex nv + r
+  bool rm_marked = false;
+  int64_t rm_nmid = 0;
+  int32_t *rm_parent = nullptr;   // [nc]
+  int8_t *rm_child = nullptr;     // [nc*nvpc]
+  int32_t *rm_mid = nullptr;      // [rm_nmid] marked coarse edges, ascending
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -337,6 +344,9 @@ int phx_mesh_build_edges(phx_mesh *m);
 int phx_mesh_create_from(int gdim, int cell_type, int64_t nv, const double *coords, int64_t nc,
                          const int32_t *cells, int loc, int device, phx_mesh **out);
 int phx_mesh_pinned_scalars(phx_mesh *m, double **out);
+// phx_prolongate onto a mesh made by phx_mesh_refine_marked (phx_refine_marked.inc.hip)
+int phx_prolongate_marked(phx_mesh *coarse, phx_mesh *fine, int degree, int ncomp, const double *in, int loc_in,
+                          double *out, int loc_out);
 // Several small device values to the host with ONE round trip on `st`: a one-wave kernel packs them into a staging
 // block, one copy lands in pinned memory.  (Every hipMemcpyAsync into a pageable host variable is a round trip of its
 // own, ~20 us each: the totals of two scans cost four.)  At most 8 items of at most 64 bytes.

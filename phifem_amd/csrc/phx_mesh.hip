@@ -1128,6 +1128,7 @@ extern "C" int phx_mesh_destroy(phx_mesh *m) {
   free(m->c_map_h); free(m->v_map_h);
   (void)phx_free(m->v2lat); (void)phx_free(m->lat2v);
   (void)phx_free(m->in_cmap); (void)phx_free(m->in_fmap);
+  (void)phx_free(m->rm_parent); (void)phx_free(m->rm_child); (void)phx_free(m->rm_mid);
   if (m->inner) { phx_mesh_destroy(m->inner); m->inner = nullptr; }
   phx_locator_destroy(m->locator);
   if (m->scal_h) (void)hipHostFree(m->scal_h);
@@ -1283,6 +1284,12 @@ extern "C" int phx_mesh_get_array(phx_mesh *m, int which, void *out, int loc) {
     case PHX_ARR_EDGES:
       PHX_CHECK(phx_mesh_build_edges(m));
       src = m->edges; bytes = sizeof(int32_t) * m->ne * 2; break;
+    case PHX_ARR_PARENT_CELLS:
+    case PHX_ARR_CHILD_NODES:
+      PHX_REQUIRE(m->rm_marked, PHX_ERR_VALUE, "the mesh was not made by phx_mesh_refine_marked");
+      if (which == PHX_ARR_PARENT_CELLS) { src = m->rm_parent; bytes = sizeof(int32_t) * m->nc; }
+      else { src = m->rm_child; bytes = (size_t)m->nc * m->ci.nvpc; }
+      break;
     case PHX_ARR_CELL_TAGS:
     case PHX_ARR_FACET_TAGS: {
       const bool fac = which == PHX_ARR_FACET_TAGS;

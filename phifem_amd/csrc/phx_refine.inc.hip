@@ -254,6 +254,7 @@ extern "C" int phx_mesh_refine(phx_mesh *m, phx_mesh **fine_out) {
 
 extern "C" int phx_prolongate(phx_mesh *coarse, phx_mesh *fine, int degree, int ncomp, const double *in, int loc_in,
                               double *out, int loc_out) {
+  if (fine && fine->rm_marked) return phx_prolongate_marked(coarse, fine, degree, ncomp, in, loc_in, out, loc_out);
   RefineTables T;
   PHX_CHECK(refine_tables(coarse->cell_type, T));
   const bool quad = coarse->cell_type == PHX_QUADRILATERAL;

@@ -235,9 +235,20 @@ class Mesh:
             parts.append(((x[fv[:, 0]] + x[fv[:, 1]]) + x[fv[:, 2]]) / 3.0)
         return np.ascontiguousarray(np.concatenate(parts, axis=0))
 
-    def refine(self):
-        """Uniform regular refinement (`phifem_amd.refine`)."""
-        return refine(self)
+    def refine(self, marked=None, edges=None):
+        """Uniform regular refinement, or marked refinement with a cell / edge mask (`phifem_amd.refine`)."""
+        return refine(self, marked=marked, edges=edges)
+
+    @property
+    def parent_cells(self):
+        """Meshes made by `refine(mesh, marked=..)`: (nc,) int32, the coarse cell every cell lies in."""
+        return self._get(L.ARR_PARENT_CELLS, (self.nc,), np.int32)
+
+    @property
+    def child_nodes(self):
+        """Meshes made by `refine(mesh, marked=..)`: (nc, nvpc) int8, every cell as local degree-2 nodes of its
+        parent (0 .. nvpc-1 the parent's vertices, nvpc + k the midpoint of its local edge k)."""
+        return self._get(L.ARR_CHILD_NODES, (self.nc, self.nvpc), np.int8)
 
     def cell_tag_values(self):
         return self._get(L.ARR_CELL_TAGS, (self.nc,), np.int32)
@@ -294,13 +305,58 @@ def create_rectangle(bbox, n, device=0, cell_type="triangle"):
     return Mesh.from_arrays("quadrilateral", x, cells, device=device)
 
 
-def refine(mesh):
-    """Uniform regular refinement on the device (dolfinx.mesh.refine(mesh)[0], demo/interface-elasticity/main.py:390):
+def _mask_u8(mask, n, mesh, what):
+    """A cell / edge mask as contiguous uint8 of length n: numpy array or tensor on the mesh's GPU."""
+    if hasattr(mask, "data_ptr"):
+        import torch
+        if not mask.is_cuda or mask.device.index != mesh.device:
+            raise ValueError(f"refine: the {what} mask has to be a numpy array or a tensor on the mesh's GPU")
+        m = (mask != 0).to(torch.uint8).contiguous()
+    else:
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+    if tuple(m.shape) != (n,):
+        raise ValueError(f"refine: {what} mask of shape ({n},) expected, got {tuple(m.shape)}")
+    return m
+
+
+def _refine_marked(mesh, marked, edges):
+    if mesh.cell_type == "quadrilateral":
+        raise NotImplementedError("marked refinement of quadrilaterals is not implemented (it needs hanging nodes)")
+    cm = None if marked is None else _mask_u8(marked, mesh.nc, mesh, "cell")
+    em = None if edges is None else _mask_u8(edges, mesh.ne, mesh, "edge")
+    kinds = {hasattr(a, "data_ptr") for a in (cm, em) if a is not None}
+    if len(kinds) == 2:                         # one location flag crosses the C ABI: bring the numpy mask over
+        import torch
+        cm, em = (a if hasattr(a, "data_ptr") else torch.from_numpy(a).cuda(mesh.device) for a in (cm, em))
+    pc, loc = L.ptr(cm)
+    pe, loce = L.ptr(em)
+    h = C.c_void_p()
+    info = (C.c_int64 * 3)()
+    L.check(L.lib.phx_mesh_refine_marked(mesh._h, pc, pe, loc if cm is not None else loce, C.byref(h), info))
+    fine = Mesh(h, device=mesh.device)
+    fine.coarse = mesh
+    fine.nchild = None                          # the child count varies: see parent_cells
+    fine.refine_info = (int(info[0]), int(info[1]), int(info[2]))
+    return fine
+
+
+def refine(mesh, marked=None, edges=None):
+    """`refine(mesh)`: uniform regular refinement, as below.  `refine(mesh, marked=cell mask, edges=edge mask)`, either
+    or both: marked refinement of a triangle or tetrahedron mesh by longest-edge bisection with closure (the rule of
+    include/phifem_hip.h / DESIGN.md 7e; dolfinx.mesh.refine(mesh, edges)).  The masks are what `mark_dorfler` returns:
+    numpy arrays or tensors on the mesh's GPU, (nc,) over the cells and (ne,) over `mesh.edges`, non-zero = marked.
+    The result is an ordinary untagged mesh with `fine.coarse`, `fine.parent_cells`, `fine.child_nodes`,
+    `fine.refine_info` = (marked edges after the closure, closure sweeps, fine cells) and `fine.nchild = None`;
+    `prolongate` works on it.
+
+    Uniform regular refinement on the device (dolfinx.mesh.refine(mesh)[0], demo/interface-elasticity/main.py:390):
     every triangle into 4, every tetrahedron into 8 (Bey's rule on the stored vertex order), every quadrilateral
     into 4.  The fine vertices are `mesh.lagrange_dof_points(2)` in that order, child k of cell c is fine cell
     nchild * c + k (include/phifem_hip.h states the child tables).  The result is an ordinary untagged mesh --
     `parent` stays None, it is no sub-mesh -- that carries `fine.coarse` (the mesh it came from, kept alive) and
     `fine.nchild`."""
+    if marked is not None or edges is not None:
+        return _refine_marked(mesh, marked, edges)
     h = C.c_void_p()
     L.check(L.lib.phx_mesh_refine(mesh._h, C.byref(h)))
     fine = Mesh(h, device=mesh.device)
