@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The adaptive loop: tag -> solve -> estimate -> Doerfler marking -> marked refinement, all on the device.
 
-    python adapt.py [mesh.xdmf] [--levels 6] [--degree {1,2}] [--theta 0.5] [--compare-uniform]
+    python adapt.py [mesh.xdmf] [--levels 6] [--degree {1,2}] [--theta 0.5] [--compare-uniform] [--multilevel]
 
 Same mesh, circle and manufactured solution as estimate.py.  Per level the line shows the DoFs of u_h (the entities of
 the cells tagged 1 or 2; the cells of the whole background mesh are printed next to them), eta = sqrt(sum eta_T^2) of
@@ -10,7 +10,11 @@ the cells tagged 1 or 2; the cells of the whole background mesh are printed next
 splits them.  With --compare-uniform the same columns are
 printed for uniform refinement of the same start mesh, and then the background cells and DoFs either loop needs to
 reach the eta of each uniform level.  (The manufactured solution is smooth: the marked loop saves background cells, which
-it refines inside Omega_h only, not DoFs of Omega_h -- DESIGN.md 7e has the figures.)"""
+it refines inside Omega_h only, not DoFs of Omega_h -- DESIGN.md 7e has the figures.)
+
+With --multilevel (degree 1) every refined level is solved a second and a third time, with Jacobi and with the
+multilevel preconditioner over the hierarchy built so far: iterations and milliseconds of the warm second
+solve, timed with device events on the mesh's stream."""
 import argparse
 import os
 import sys
@@ -34,6 +38,7 @@ def main():
     ap.add_argument("--degree", type=int, default=1, choices=[1, 2])
     ap.add_argument("--theta", type=float, default=0.5)
     ap.add_argument("--compare-uniform", action="store_true")
+    ap.add_argument("--multilevel", action="store_true", help="per level: iterations and solve time with and without")
     args = ap.parse_args()
 
     m = P.io.read_xdmf(args.mesh)
@@ -71,6 +76,16 @@ def main():
         ndofs = sum(np.unique(e).size for e in ents)
         return ndofs, float(np.sqrt(eta2.sum())), float(h10), eta2
 
+    def timed(mesh, multilevel):
+        """(iterations, ms of the second, warm solve -- `stats["seconds"]` is the time between two events on the mesh's
+        stream around the Krylov loop --, preconditioner)"""
+        solver = P.PhiFEMSolver(mesh, multilevel=multilevel)
+        pts = mesh.x
+        solver.assemble(levelset(pts.T), source(pts.T), exact(pts.T))
+        for _ in range(2):
+            solver.solve(rtol=1e-8, max_iter=200000)
+        return solver.stats["iterations"], 1e3 * solver.stats["seconds"], solver.stats["precond"]
+
     def run(name, step):
         mesh = P.Mesh.from_arrays(m["cell_type"], x0, m["cells"])
         rows = []
@@ -78,6 +93,9 @@ def main():
             ndofs, eta, h10, eta2 = level(mesh)
             rows.append((ndofs, eta, h10, mesh.nc))
             line = f"{name} level {lv}: {mesh.nc} cells, dofs={ndofs}  eta={eta:.4e}  H10={h10:.4e}"
+            if args.multilevel and args.degree == 1 and getattr(mesh, "coarse", None) is not None:
+                (itj, msj, pj), (itm, msm, pm) = timed(mesh, False), timed(mesh, "auto")
+                line += f"  | {pj} {itj} it {msj:.2f} ms, {pm} {itm} it {msm:.2f} ms"
             if lv + 1 < args.levels:
                 mesh, note = step(mesh, eta2)
                 line += note

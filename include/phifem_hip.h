@@ -229,6 +229,14 @@ enum phx_option {
                                and the connectivity in closed form (cells, single-layer passes); 0: the generic
                                kernels that stream `cells` run on them too.  Same tags, bit for bit: 0 is the
                                reference path of tests/test_box_closed_form_tags.py                          */
+  PHX_OPT_MULTILEVEL = 14, /* 1: P1 weak-Dirichlet systems of this mesh (triangles, tetrahedra; one rank) are
+                               preconditioned with one geometric-multigrid V-cycle over the refinement hierarchy the
+                               mesh carries (phx_mesh_refine / phx_mesh_refine_marked, down to the first mesh without a
+                               living parent) on the u block and Jacobi on the p block: see phx_multilevel_setup.
+                               Systems of any other kind on this mesh (degree 2, strong Dirichlet, elasticity,
+                               quadrilaterals) are solved as without the option; a P1 weak-Dirichlet system that
+                               cannot be served (no living parent, Kuhn box, sub-mesh, slab, ...) fails its solve
+                               with the status phx_multilevel_setup reports.  0 (default): off, nothing changes  */
   PHX_OPT_ALLOW_EMPTY = 6, /* 1: phx_assemble_poisson_wd returns an EMPTY system (n_active = 0) when no cell
                                is tagged 1 / 2 instead of PHX_ERR_VALUE: a slab of a partitioned box that
                                does not touch the domain still joins every collective of the solve          */
@@ -400,6 +408,21 @@ int phx_refine_tables(int cell_type, int32_t *children, int *nchild, double *p2_
  *     contains the fine edge writes it (integer min pass, then a write pass): the same bits on every run. */
 int phx_mesh_refine_marked(phx_mesh *m, const uint8_t *cell_marks, const uint8_t *edge_marks, int loc, phx_mesh **fine,
                            int64_t *info);
+
+/* --- restriction: the transpose of the degree-1 phx_prolongate -------------------------------
+ * in[ncomp][fine nv] -> out[ncomp][coarse nv], component-major, at loc_in / loc_out: <phx_restrict(r), x> =
+ * <r, phx_prolongate(x)>.  Triangles and tetrahedra, `fine` the direct result of phx_mesh_refine(coarse) or of
+ * phx_mesh_refine_marked(coarse) (fine vertex v < nv is coarse vertex v in both; a uniformly refined lattice mesh is
+ * re-created through phx_mesh_create and keeps that numbering).
+ *   ORDER RULE: out[p] = ((in[p] + 0.5 in[m_1]) + 0.5 in[m_2]) + ..., m_1 < m_2 < ... the new fine vertices on the
+ *   bisected coarse edges that end in p, by ascending fine vertex id, added left to right without contraction.  It is a
+ *   gather through an integer CSR (coarse vertex -> dependent fine vertices) built once per fine mesh with the stable
+ *   radix sort and freed with the fine mesh; no floating-point atomics: the same bits on every run, and bit for bit
+ *   tests/multilevel_ref.py.
+ * PHX_ERR_NOT_IMPLEMENTED: degree 2, quadrilaterals; PHX_ERR_VALUE: `fine` is not the direct child of `coarse`.
+ * Temporaries are released on every exit. */
+int phx_restrict(phx_mesh *coarse, phx_mesh *fine, int degree, int ncomp, const double *in, int loc_in, double *out,
+                 int loc_out);
 
 /* --- point location and evaluation of Lagrange functions at arbitrary points -----------------
  * Stands in for dolfinx's Function.eval with a bounding-box tree and for interpolate_nonmatching;
@@ -573,6 +596,30 @@ int phx_krylov_precond_disable(phx_system *s);
  * the box, sampled average seconds of one y-pass launch of the sine transforms (PHX_OPT_PROFILE_SPMV),
  * launches sampled, bytes per lattice value (4: f32 transforms, 8: f64)}. */
 int phx_precond_info(phx_system *s, double *out);
+/* Multilevel preconditioner (PHX_OPT_MULTILEVEL; tests/multilevel_ref.py restates it in numpy).
+ * M^-1 = R V R^T on the u block, Jacobi on the p block: R^T places the u rows at their vertices of the system's mesh
+ * (level L, zeros elsewhere), V is ONE V-cycle for K_L, R reads the active vertices back.
+ *   Levels 0 .. L: the chain of phx_mesh_refine / phx_mesh_refine_marked parents of the system's mesh, down to the first
+ *   mesh that has no parent or whose parent has been destroyed.
+ *   Constrained vertices: on level L a vertex of a mesh-boundary facet that is no active u DoF of the system (active
+ *   boundary vertices stay free: phi-FEM imposes nothing there), and a vertex that belongs to no cell; on level l < L a
+ *   vertex is constrained when its image on level L (the same id) is.
+ *   K_l: the P1 stiffness matrix of ALL cells of level l, constrained rows and columns replaced by the identity, in
+ *   SELL-64 by vertex, built by a stable sort of one entry per (cell, local pair) and an in-order fold: no
+ *   floating-point atomics, the same bits on every run.
+ *   Smoother: damped Jacobi x <- x + w D^-1 (b - K x), w = 2/3, 2 sweeps before and after, zero initial guess (the first
+ *   sweep is x = w D^-1 b).  Transfers: phx_restrict's gather with constrained coarse entries set to zero, the degree-1
+ *   prolongation with constrained fine entries left alone.  V is symmetric and one fixed linear operator.
+ *   Coarsest level: n_0 <= 2048: the dense inverse of K_0 (kind 1); otherwise 2 * 2 + 8 sweeps from zero (kind 0).  (A
+ *   lattice solve on a Kuhn-box level 0, kind 2, is not built.)
+ * phx_multilevel_setup builds it for `s` now (phx_solve builds it on the first solve when the option is set) and reports:
+ *   PHX_ERR_VALUE: the system's mesh has no living parent; no constrained boundary vertex (K would be singular); slab or
+ *     partitioned rank;
+ *   PHX_ERR_NOT_IMPLEMENTED: degree 2, quadrilaterals, sub-meshes, systems other than P1 weak Dirichlet, systems that
+ *     the lattice preconditioner serves (Kuhn boxes and meshes recognised as such), P2 coarse-space correction asked for.
+ * It copies what it needs from the coarser meshes: they may be destroyed afterwards.  Everything is freed with the system.
+ * phx_precond_info then reports {5, levels, n_0, coarse kind, sum of the level sizes, 0, 0, 8}. */
+int phx_multilevel_setup(phx_system *s);
 /* After a solve, the coarse-space correction of the system (P2: PHX_OPT_P2_COARSE; elasticity: PHX_OPT_EL_COARSE):
  * out[6] = {ratio H / h, coarse DoFs of the first field (P2: u; elasticity: all), coarse DoFs of the second field (P2: p;
  * elasticity: 0), build seconds, operator products of the probing, bytes the dense apply streams (nc^2 * 8)}.  No

@@ -22,7 +22,7 @@ Everything numerical runs in `libphifem_hip.so` (hand-written HIP for gfx950) th
 declared in `include/phifem_hip.h`.  There is no CPU fallback.
 """
 from . import _lib  # noqa: F401  (fails loudly when the HIP library is missing)
-from .mesh import Mesh, MeshTags, create_box, create_rectangle, prolongate, refine  # noqa: F401
+from .mesh import Mesh, MeshTags, create_box, create_rectangle, prolongate, refine, restrict  # noqa: F401
 from .evaluate import evaluate, interpolate_nonmatching, locate, locator_info  # noqa: F401
 from .estimate import estimate, mark_dorfler  # noqa: F401
 from . import io  # noqa: F401

@@ -29,8 +29,8 @@ CELL_NAMES = {v: k for k, v in CELL_TYPES.items()}
 PHI_NODAL_P1, PHI_POINTS, PHI_QUADRIC = 0, 1, 2
 (OPT_PROFILE_SPMV, OPT_HAS_EXTERIOR, OPT_SPMV_XCD_GROUP, OPT_SPMV_VALUE_INDEX, OPT_PRECOND, OPT_ALLOW_EMPTY,
  OPT_EXPORT_CSR, OPT_STRUCTURED, OPT_DETERMINISTIC, OPT_EL_COARSE, OPT_STENCIL_PLANE_ROWS, OPT_P2_COARSE,
- OPT_BOX_TAGS) = (
-    1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13)
+ OPT_BOX_TAGS, OPT_MULTILEVEL) = (
+    1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14)
 (ARR_COORDS, ARR_CELLS, ARR_C2F, ARR_F2C, ARR_CELL_TAGS, ARR_FACET_TAGS, ARR_BFACETS, ARR_C2E,
  ARR_EDGES, ARR_PARENT_CELLS, ARR_CHILD_NODES) = range(11)
 
@@ -76,6 +76,7 @@ SIGNATURES = {
     "phx_krylov_precond_disable": ([_vp], _i),
     "phx_precond_info": ([_vp, _pd], _i),
     "phx_coarse_info": ([_vp, _pd], _i),
+    "phx_multilevel_setup": ([_vp], _i),
     "phx_coarse_export": ([_vp, _vp, _vp], _i),
     "phx_precond_local_bbox": ([_vp, _pi64], _i),
     "phx_precond_setup_global": ([_vp, _pi64, _i, _i, _pi64, _pi64], _i),
@@ -106,6 +107,7 @@ SIGNATURES = {
     "phx_submesh_create_from_flags": ([_vp, _vp, _i, C.POINTER(_vp)], _i),
     "phx_mesh_refine": ([_vp, C.POINTER(_vp)], _i),
     "phx_prolongate": ([_vp, _vp, _i, _i, _vp, _i, _vp, _i], _i),
+    "phx_restrict": ([_vp, _vp, _i, _i, _vp, _i, _vp, _i], _i),
     "phx_refine_tables": ([_i, _vp, _pi, _vp], _i),
     "phx_mesh_refine_marked": ([_vp, _vp, _vp, _i, C.POINTER(_vp), _pi64], _i),
     "phx_locate_points": ([_vp, _i64, _vp, _i, _d, _vp, _vp, _i], _i),

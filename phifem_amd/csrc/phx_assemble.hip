@@ -1374,6 +1374,7 @@ extern "C" int phx_system_destroy(phx_system *s) {
   phx_box_precond_destroy(s->precond);
   phx_blockjac_destroy(s->bj);
   phx_coarse_destroy(s->cc);
+  phx_multilevel_destroy(s->ml);
   delete s;
   return PHX_OK;
 }

@@ -76,8 +76,16 @@ struct phx_cell_info {
 int phx_get_cell_info(int cell_type, phx_cell_info *ci);
 
 uint64_t phx_next_mesh_uid(void);   // phx_mesh.hip: 1, 2, ... never reused within a process
+// the living meshes by uid (phx_mesh.hip): how a refined mesh finds the mesh it came from, or learns that it is gone
+void phx_mesh_register(struct phx_mesh *m);
+void phx_mesh_unregister(struct phx_mesh *m);
+struct phx_mesh *phx_mesh_lookup(uint64_t uid);   // nullptr: destroyed (or never there)
 
 struct phx_mesh {
+  phx_mesh() { phx_mesh_register(this); }
+  ~phx_mesh() { phx_mesh_unregister(this); }
+  phx_mesh(const phx_mesh &) = delete;
+  phx_mesh &operator=(const phx_mesh &) = delete;
   uint64_t uid = phx_next_mesh_uid();
   // uniform refinement (phx_refine.inc.hip): uid of the mesh this one was refined from (0: none), children per cell
   uint64_t refined_from = 0;
@@ -89,6 +97,9 @@ struct phx_mesh {
   int32_t *rm_parent = nullptr;   // [nc]
   int8_t *rm_child = nullptr;     // [nc*nvpc]
   int32_t *rm_mid = nullptr;      // [rm_nmid] marked coarse edges, ascending
+  // restriction (phx_restrict.inc.hip), built on first use: CSR coarse vertex -> the new fine vertices that depend on it
+  int32_t *rs_ptr = nullptr;      // [coarse nv + 1]
+  int32_t *rs_idx = nullptr;      // [2 * bisected edges] fine vertex ids, ascending within a row
   int device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -177,6 +188,7 @@ struct phx_mesh {
   int el_coarse = -1;              // PHX_OPT_EL_COARSE
   int p2_coarse = 0;               // PHX_OPT_P2_COARSE: 0 off, -1 automatic, >= 5 the ratio H / h
   int deterministic = 0;           // PHX_OPT_DETERMINISTIC: bit-reproducible P2 / elasticity assembly and Krylov dot products
+  int multilevel = 0;              // PHX_OPT_MULTILEVEL: V-cycle over the refinement hierarchy as the u preconditioner
   // A caller-supplied mesh that IS a Kuhn box in some vertex / cell order (what dolfinx's create_box / create_rectangle
   // hand over, demo/weak-dirichlet/flower/main.py:45-46): `inner` is the generated box with the same lattice, the maps
   // translate.  Tags are computed on THIS mesh (caller numbering, bit-exact as before); the P1 weak-Dirichlet assembly
@@ -314,6 +326,7 @@ struct phx_system {
   struct phx_blockjac *bj = nullptr;
   bool bj_tried = false;
   struct phx_coarse *cc = nullptr; // coarse correction on top of the vertex blocks (phx_coarse.inc.hip)
+  struct phx_multilevel *ml = nullptr;   // multilevel preconditioner of the u block (phx_multilevel.inc.hip)
   bool cc_tried = false;
   int cc_reason = 0;               // P2 coarse correction asked for but not built: PHX_CC_* reason (phx_coarse.inc.hip)
   // PHX_OPT_DETERMINISTIC: every block of a dot-product kernel leaves its partial sum in its own entry of `dpart`
@@ -347,6 +360,8 @@ int phx_mesh_pinned_scalars(phx_mesh *m, double **out);
 // phx_prolongate onto a mesh made by phx_mesh_refine_marked (phx_refine_marked.inc.hip)
 int phx_prolongate_marked(phx_mesh *coarse, phx_mesh *fine, int degree, int ncomp, const double *in, int loc_in,
                           double *out, int loc_out);
+// the restriction CSR of `fine` (rs_ptr / rs_idx), built once; coarse->edges must exist (phx_restrict.inc.hip)
+int phx_restrict_csr(phx_mesh *coarse, phx_mesh *fine);
 // Several small device values to the host with ONE round trip on `st`: a one-wave kernel packs them into a staging
 // block, one copy lands in pinned memory.  (Every hipMemcpyAsync into a pageable host variable is a round trip of its
 // own, ~20 us each: the totals of two scans cost four.)  At most 8 items of at most 64 bytes.
@@ -381,5 +396,7 @@ struct phx_blockjac;
 void phx_blockjac_destroy(phx_blockjac *b);         // phx_solve.hip
 struct phx_coarse;
 void phx_coarse_destroy(phx_coarse *c);             // phx_solve.hip
+struct phx_multilevel;
+void phx_multilevel_destroy(phx_multilevel *ml);    // phx_solve.hip (phx_multilevel.inc.hip)
 struct phx_locator;
 void phx_locator_destroy(phx_locator *l);           // phx_submesh.hip (phx_locate.inc.hip)

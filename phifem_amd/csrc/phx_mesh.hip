@@ -8,6 +8,8 @@
 
 #include <algorithm>
 #include <atomic>
+#include <mutex>
+#include <unordered_map>
 #include <vector>
 
 #include "phx_common.h"
@@ -136,6 +138,27 @@ extern "C" int phx_pool_stats(int64_t *live_bytes, int64_t *cached_bytes) {
 uint64_t phx_next_mesh_uid(void) {
   static std::atomic<uint64_t> next{0};
   return ++next;
+}
+
+namespace {
+struct MeshRegistry { std::mutex mu; std::unordered_map<uint64_t, phx_mesh *> by_uid; };
+MeshRegistry &mesh_registry() { static MeshRegistry *r = new MeshRegistry(); return *r; }   // outlives every mesh
+}  // namespace
+void phx_mesh_register(phx_mesh *m) {
+  MeshRegistry &r = mesh_registry();
+  std::lock_guard<std::mutex> lk(r.mu);
+  r.by_uid[m->uid] = m;
+}
+void phx_mesh_unregister(phx_mesh *m) {
+  MeshRegistry &r = mesh_registry();
+  std::lock_guard<std::mutex> lk(r.mu);
+  r.by_uid.erase(m->uid);
+}
+phx_mesh *phx_mesh_lookup(uint64_t uid) {
+  MeshRegistry &r = mesh_registry();
+  std::lock_guard<std::mutex> lk(r.mu);
+  auto it = r.by_uid.find(uid);
+  return it == r.by_uid.end() ? nullptr : it->second;
 }
 
 extern "C" int phx_version(void) { return 1; }
@@ -1129,6 +1152,7 @@ extern "C" int phx_mesh_destroy(phx_mesh *m) {
   (void)phx_free(m->v2lat); (void)phx_free(m->lat2v);
   (void)phx_free(m->in_cmap); (void)phx_free(m->in_fmap);
   (void)phx_free(m->rm_parent); (void)phx_free(m->rm_child); (void)phx_free(m->rm_mid);
+  (void)phx_free(m->rs_ptr); (void)phx_free(m->rs_idx);
   if (m->inner) { phx_mesh_destroy(m->inner); m->inner = nullptr; }
   phx_locator_destroy(m->locator);
   if (m->scal_h) (void)hipHostFree(m->scal_h);
@@ -1226,6 +1250,7 @@ extern "C" int phx_set_option(phx_mesh *m, int option, int64_t value) {
     case PHX_OPT_STRUCTURED: m->structured = value != 0; return PHX_OK;
     case PHX_OPT_BOX_TAGS: m->box_tags = value != 0; return PHX_OK;
     case PHX_OPT_DETERMINISTIC: m->deterministic = value != 0; return PHX_OK;
+    case PHX_OPT_MULTILEVEL: m->multilevel = value != 0; return PHX_OK;
     case PHX_OPT_EL_COARSE:
       PHX_REQUIRE(value == -1 || value == 0 || (value >= 5 && value <= 4096), PHX_ERR_VALUE, "coarse ratio %lld: -1, 0 or >= 5", (long long)value);
       m->el_coarse = (int)value;

@@ -1868,6 +1868,7 @@ static int prof_collect(phx_system *s, double *avg_s, int *count, int c = 0) {
 #include "phx_blockjac.inc.hip"
 #include "phx_dense.inc.hip"
 #include "phx_coarse.inc.hip"
+#include "phx_multilevel.inc.hip"
 void phx_blockjac_destroy(phx_blockjac *b) { blockjac_free(b); }
 
 // Structured systems without the box preconditioner (configured out, vetoed, box too long): their u columns are
@@ -2150,7 +2151,7 @@ static inline KrVecs kr_vecs(phx_system *s) {
   double *w = s->kr_work ? s->kr_work : s->work;
   const int64_t n = s->n;
   KrVecs V{w, w + n, w + 2 * n, w + 3 * n, w + 4 * n, w + 5 * n, w + 6 * n, w + 7 * n, w + 2 * n, w + 4 * n};
-  if (s->precond_state == 1 || s->u_unscaled || s->bj) {
+  if (s->precond_state == 1 || s->u_unscaled || s->bj || s->ml) {
     // attached workspaces (multi-GPU drivers, 10 n doubles) carry the two extra vectors themselves
     V.phat = s->kr_work ? w + 8 * n : s->pvec;
     V.shat = s->kr_work ? w + 9 * n : s->pvec + n;
@@ -2315,7 +2316,10 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
       s->cc_tried = true;
       PHX_CHECK(p2_coarse_build(s, &s->cc));
     }
-    if ((s->precond_state == 1 || s->u_unscaled || s->bj) && n > 0 && !s->kr_work) {
+    // multilevel preconditioner over the refinement hierarchy (PHX_OPT_MULTILEVEL), once per system.  The option speaks
+    // of P1 weak-Dirichlet systems on simplices: every other system of the mesh is solved as without it
+    if (m->multilevel != 0 && !s->ml && n > 0 && ml_kind_served(s)) PHX_CHECK(ml_setup(s));
+    if ((s->precond_state == 1 || s->u_unscaled || s->bj || s->ml) && n > 0 && !s->kr_work) {
       // phat / shat: rows the preconditioner never writes (u rows another rank owns) stay zero
       if (!s->pvec) PHX_HIP(phx_malloc(&s->pvec, sizeof(double) * (size_t)n * 2));
       PHX_HIP(hipMemsetAsync(s->pvec, 0, sizeof(double) * (size_t)n * 2, st));
@@ -2330,7 +2334,7 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
   double *S = kr_scal(s);
   const dim3 block(256);
   // identity part of the box preconditioner, written by the producers of p and s (RestOut)
-  const bool rest_out = s->precond_state == 1 && V.phat != V.p;
+  const bool rest_out = (s->precond_state == 1 || s->ml) && V.phat != V.p;
   const int32_t *rperm = s->structured ? nullptr : s->perm;
   const RestOut rop{rest_out ? V.phat : nullptr, rperm, s->nu}, ros{rest_out ? V.shat : nullptr, rperm, s->nu};
   const KrRed R = s->kr_red_used ? kr_red_vecs(s) : KrRed{};
@@ -2394,14 +2398,16 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
       k_update_p<<<vec_grid(n), block, 0, st>>>(n, par, s->own, V.r, V.v, V.p, V.rhat, S, rop);
       break;
     case KR_PRECOND_P:
-      if (s->precond_state == 1) {
+      if (s->ml) PHX_CHECK(ml_apply(s, V.p, V.phat));
+      else if (s->precond_state == 1) {
         PHX_CHECK(box_precond_apply(s, V.p, V.phat, s->precond->dist ? 1 : 0));
         if (s->cc && s->cc->p2) PHX_CHECK(coarse_apply_add(s, s->cc, V.p, V.phat));
       } else if (s->bj) { PHX_CHECK(blockjac_apply(s, s->bj, V.p, V.phat)); PHX_CHECK(coarse_apply_add(s, s->cc, V.p, V.phat)); }
       else if (s->u_unscaled && n > 0) k_jacobi_u<<<vec_grid(n), block, 0, st>>>(n, s->nu, s->perm, s->diag, V.p, V.phat);
       break;
     case KR_PRECOND_S:
-      if (s->precond_state == 1) {
+      if (s->ml) PHX_CHECK(ml_apply(s, V.sv, V.shat));
+      else if (s->precond_state == 1) {
         PHX_CHECK(box_precond_apply(s, V.sv, V.shat, s->precond->dist ? 1 : 0));
         if (s->cc && s->cc->p2) PHX_CHECK(coarse_apply_add(s, s->cc, V.sv, V.shat));
       } else if (s->bj) { PHX_CHECK(blockjac_apply(s, s->bj, V.sv, V.shat)); PHX_CHECK(coarse_apply_add(s, s->cc, V.sv, V.shat)); }
@@ -2578,7 +2584,7 @@ extern "C" int phx_krylov_finish(phx_system *s, double *x_out, int loc) {
 // the vectors a multi-GPU driver must halo-exchange instead of p / s)
 extern "C" int phx_krylov_precond_active(const phx_system *s, int *active) {
   // 1: the SpMV inputs are phat / shat (box preconditioner, or the u-block Jacobi of a structured system)
-  *active = (s->precond_state == 1 || s->u_unscaled || s->bj) ? 1 : 0;
+  *active = (s->precond_state == 1 || s->u_unscaled || s->bj || s->ml) ? 1 : 0;
   return PHX_OK;
 }
 
@@ -2652,6 +2658,11 @@ extern "C" int phx_precond_info(phx_system *s, double *out) {
   for (int i = 0; i < 8; ++i) out[i] = 0.0;
   if (s->bj) out[0] = s->cc ? 3.0 : 2.0;   // dense vertex blocks (interface elasticity), 3: with the coarse correction
   if (s->cc) { out[1] = (double)s->cc->ratio; out[4] = (double)s->cc->nc; }
+  if (s->ml) {   // 5: multilevel: {levels, n_0, coarse kind, sum of the level sizes}
+    out[0] = 5.0; out[1] = (double)s->ml->lv.size(); out[2] = (double)s->ml->lv[0].nv; out[3] = (double)s->ml->coarse_kind;
+    out[4] = (double)s->ml->points; out[7] = 8.0;
+    return PHX_OK;
+  }
   if (s->precond_state != 1) return PHX_OK;
   const BoxGrid &g = s->precond->g;
   out[0] = s->cc && s->cc->p2 ? 4.0 : 1.0;   // 4: with the P2 coarse correction
@@ -2718,7 +2729,7 @@ static int kr_drive(phx_system *s, const KrDist *d, double rtol, int64_t max_ite
   const KrVecs V = kr_vecs(s);
   const bool ident = s->kr_ident_used;   // decided by phase 0 (kr_identity; never in mode 1)
   const bool red = s->kr_red_used;       // kr_reduced (only with ident)
-  const bool pc = d ? d->pc_all : s->precond_state == 1;
+  const bool pc = d ? d->pc_all : (s->precond_state == 1 || s->ml);
   const double bb = s->scal_h[S_BB];
   auto read_head = [&](const char *what) -> int {
     PHX_HIP(hipMemcpyAsync(s->scal_h, S, sizeof(double) * 16, hipMemcpyDeviceToHost, st));

@@ -170,5 +170,6 @@ extern "C" int phx_submesh_maps(phx_mesh *sub, int32_t *c_map, int32_t *v_map) {
 #include "phx_partition.inc.hip"
 #include "phx_refine.inc.hip"
 #include "phx_refine_marked.inc.hip"
+#include "phx_restrict.inc.hip"
 #include "phx_q1rect.inc.hip"   // rect_load and the rectangle flag, for phx_locate.inc.hip
 #include "phx_locate.inc.hip"

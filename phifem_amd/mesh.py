@@ -399,3 +399,37 @@ def prolongate(fine, values, degree=1):
     po, lo = L.ptr(out)
     L.check(L.lib.phx_prolongate(coarse._h, fine._h, degree, ncomp, pi, li, po, lo))
     return out
+
+
+def restrict(fine, values, degree=1):
+    """The transpose of `prolongate`: `values` on `fine` -> values on `fine.coarse`, with <restrict(r), x> =
+    <r, prolongate(x)>.  It maps residuals (functionals), not functions.  `values`: a numpy array or a tensor on the
+    mesh's GPU, of shape (nv,) or (ncomp, nv) of the fine mesh; the result is of the same kind on the coarse mesh.
+    Degree 1 on triangles and tetrahedra, after uniform and after marked refinement.  The additions run in a stated
+    order (include/phifem_hip.h): the same bits on every run."""
+    coarse = getattr(fine, "coarse", None)
+    if coarse is None:
+        raise ValueError("restrict: the mesh was not produced by refine()")
+    if degree != 1 or coarse.cell_type == "quadrilateral":
+        raise NotImplementedError("restriction: degree 1 on triangles and tetrahedra")
+    nin, nout = fine.nv, coarse.nv
+    is_tensor = hasattr(values, "data_ptr")
+    if is_tensor:
+        import torch
+        if not values.is_cuda or values.device.index != fine.device:
+            raise ValueError("restrict: a tensor has to live on the mesh's GPU")
+        v = values.to(torch.float64).contiguous()
+    else:
+        v = np.ascontiguousarray(values, dtype=np.float64)
+    shape = tuple(v.shape)
+    if len(shape) not in (1, 2) or shape[-1] != nin:
+        raise ValueError(f"restrict: expected {nin} values per component, got shape {shape}")
+    ncomp = 1 if len(shape) == 1 else shape[0]
+    if ncomp == 0:
+        raise ValueError("restrict: no component")
+    oshape = shape[:-1] + (nout,)
+    out = torch.empty(oshape, dtype=torch.float64, device=v.device) if is_tensor else np.empty(oshape)
+    pi, li = L.ptr(v)
+    po, lo = L.ptr(out)
+    L.check(L.lib.phx_restrict(coarse._h, fine._h, degree, ncomp, pi, li, po, lo))
+    return out

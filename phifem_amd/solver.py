@@ -56,8 +56,18 @@ def _p2_coarse_option(coarse_space):
 
 class PhiFEMSolver:
     def __init__(self, mesh, pen_coef=1.0, stab_coef=1.0, degree=1, levelset_degree=1, deterministic=False,
-                 coarse_space=None):
-        """coarse_space (PHX_OPT_P2_COARSE, degree 2 on a generated Kuhn box, one rank): two-level preconditioner, the
+                 coarse_space=None, multilevel=False):
+        """multilevel (PHX_OPT_MULTILEVEL, degree 1 on triangle / tetrahedron meshes that `refine` produced, one
+        rank): the u block is preconditioned with one geometric-multigrid V-cycle over the refinement hierarchy the mesh
+        carries (`mesh.coarse`, down to the first mesh whose parent is gone), the p block keeps Jacobi.
+        False (default): nothing changes.  True: built by `assemble`; ValueError when the mesh has no living parent,
+        when every boundary vertex is active (the level matrices would be singular) or on a slab / partitioned rank;
+        NotImplementedError for degree 2, quadrilaterals, sub-meshes, `coarse_space`, and meshes the lattice
+        preconditioner serves (Kuhn boxes).  "auto": as True where it can be built, quietly Jacobi (or the lattice
+        preconditioner) elsewhere.  `stats["precond"]` reports "multilevel", `stats["precond_L"]` = [levels, vertices
+        of level 0, coarse kind: 1 dense inverse, 0 smoothing sweeps].
+
+        coarse_space (PHX_OPT_P2_COARSE, degree 2 on a generated Kuhn box, one rank): two-level preconditioner, the
         additive Galerkin correction R Ac^-1 R^T on multilinear functions of spacing H on top of the lattice sine
         transform.  None (default): off; "auto": the library picks H (and leaves it off where it does not pay);
         an int >= 5: H / h.  Built on the first solve; a correction that was asked for and could not be built is
@@ -98,6 +108,20 @@ class PhiFEMSolver:
         self.deterministic = bool(deterministic)
         self.coarse_space = coarse_space
         self._p2_coarse = _p2_coarse_option(coarse_space)
+        if multilevel not in (False, True, "auto"):
+            raise ValueError(f"multilevel={multilevel!r}: False, True or 'auto'")
+        self.multilevel = multilevel
+        if multilevel is True:
+            if degree != 1:
+                raise NotImplementedError("multilevel is implemented for degree = 1")
+            if getattr(mesh, "cell_type", None) == "quadrilateral":
+                raise NotImplementedError("multilevel is implemented on triangles and tetrahedra")
+            if getattr(mesh, "parent", None) is not None:
+                raise NotImplementedError("multilevel needs the refined mesh itself (box_mode=True), not a sub-mesh")
+            if coarse_space is not None:
+                raise NotImplementedError("multilevel is not combined with coarse_space")
+            if getattr(mesh, "coarse", None) is None:
+                raise ValueError("multilevel=True: the mesh was not produced by refine() (no parent to coarsen to)")
         if self._p2_coarse != 0:
             if degree != 2:
                 raise NotImplementedError("coarse_space is implemented for degree = 2")
@@ -107,6 +131,7 @@ class PhiFEMSolver:
     def _apply_options(self):
         L.check(L.lib.phx_set_option(self.mesh._h, L.OPT_DETERMINISTIC, int(getattr(self, "deterministic", False))))
         L.check(L.lib.phx_set_option(self.mesh._h, L.OPT_P2_COARSE, int(getattr(self, "_p2_coarse", 0))))
+        L.check(L.lib.phx_set_option(self.mesh._h, L.OPT_MULTILEVEL, int(getattr(self, "_ml_on", False))))
         if hasattr(self, "coarse"):
             L.check(L.lib.phx_set_option(self.mesh._h, L.OPT_EL_COARSE, self.coarse))
 
@@ -154,7 +179,30 @@ class PhiFEMSolver:
         self._keep = (phi_h, f_h, u_D)   # inputs stay alive as long as the system they were read for
         self._tag_generation = self.mesh._tag_generation
         self._sys = self._assemble_raw()
+        self._setup_multilevel()
         return self.info()
+
+    def _wants_multilevel(self):
+        ml = getattr(self, "multilevel", False)
+        if ml == "auto":
+            m = self.mesh
+            return (self.degree == 1 and getattr(m, "cell_type", None) in ("triangle", "tetrahedron")
+                    and getattr(m, "parent", None) is None and getattr(m, "coarse", None) is not None
+                    and getattr(self, "_p2_coarse", 0) == 0)
+        return ml is True
+
+    def _setup_multilevel(self):
+        """Builds the multilevel preconditioner of the system just assembled, so that its refusals surface here."""
+        self._ml_on = False
+        if not self._wants_multilevel():
+            return
+        try:
+            L.check(L.lib.phx_multilevel_setup(self._sys))
+            self._ml_on = True
+        except (ValueError, NotImplementedError):
+            if self.multilevel is True:
+                self._free()
+                raise
 
     def _assemble_raw(self):
         phi_h, f_h, u_D = self._keep
@@ -299,7 +347,7 @@ class PhiFEMSolver:
         o = (C.c_double * 8)()
         L.check(L.lib.phx_precond_info(self._sys, o))
         return {"precond": {1: "box-dst", 2: "vertex-block-jacobi", 3: "vertex-block-jacobi+coarse",
-                            4: "box-dst+coarse"}.get(int(o[0]), "jacobi"), "precond_L": [int(o[1]), int(o[2]), int(o[3])],
+                            4: "box-dst+coarse", 5: "multilevel"}.get(int(o[0]), "jacobi"), "precond_L": [int(o[1]), int(o[2]), int(o[3])],
                 "precond_points": int(o[4]), "dst_avg_s": o[5], "dst_timed": int(o[6]),
                 "precond_value_bytes": int(o[7])}
 
