@@ -1586,31 +1586,8 @@ static int csr_from_slots(phx_system *s, Slots &sl, int32_t nent) {
 // ---------------------------------------------------------------------------------------------
 // Host scaffold of the assemblers (weak Dirichlet P1 / P2 / Q1, strong Dirichlet, Neumann / Robin, interface
 // elasticity): each one reads numbering -> work lists -> slots -> launches -> finish; what it allocates on the way is
-// owned by the two objects below, so every return -- PHX_HIP / PHX_CHECK / PHX_REQUIRE included -- gives it back.
+// owned by a DevTemps (phx_common.h) or the object below, so every return -- PHX_HIP / PHX_CHECK / PHX_REQUIRE included -- gives it back.
 // ---------------------------------------------------------------------------------------------
-// Device temporaries of one call: the stream is synchronised once and the blocks are freed when the list goes out of
-// scope, so a kernel that is only enqueued may still read them.
-struct DevTemps {
-  hipStream_t stream;
-  std::vector<void *> blocks;
-  explicit DevTemps(hipStream_t st) : stream(st) {}
-  DevTemps(const DevTemps &) = delete;
-  DevTemps &operator=(const DevTemps &) = delete;
-  ~DevTemps() {
-    if (blocks.empty()) return;   // nothing to wait for (device-resident inputs, a call that failed at once)
-    (void)hipStreamSynchronize(stream);
-    for (void *p : blocks) (void)phx_free(p);
-  }
-  template <typename T>
-  hipError_t alloc(T **p, size_t bytes) {
-    const hipError_t e = phx_malloc(p, bytes);
-    if (e == hipSuccess) blocks.push_back(*p);
-    return e;
-  }
-  template <typename T>
-  void adopt(T *p) { if (p) blocks.push_back((void *)p); }   // a block some helper allocated (build_list)
-};
-
 // The system under construction and its slot table: destroyed unless a finish hands the system to the caller
 // (the finishing calls consume the slots on the way; free_slots leaves null pointers behind, so freeing twice is safe).
 struct SystemBuild {

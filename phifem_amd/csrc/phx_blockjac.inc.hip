@@ -148,18 +148,22 @@ static int blockjac_build(phx_system *s, int nblk, phx_blockjac **out) {
   const int64_t nvert = m->nv, n = s->n;
   PHX_REQUIRE(s->rowptr && s->nent == (int64_t)nblk * nvert && nblk <= BJ_MAXK, PHX_ERR_VALUE,
               "vertex-block Jacobi needs the CSR copy of a block-major system with at most %d blocks", BJ_MAXK);
-  phx_blockjac *b = new phx_blockjac();
+  // declared in this order: a failing return synchronises (tmp), then frees the temporaries, then b
+  std::unique_ptr<phx_blockjac, void (*)(phx_blockjac *)> own(new phx_blockjac(), blockjac_free);
+  DevTemps tmp(st);
+  phx_blockjac *b = own.get();
   b->nvert = nvert;
   int32_t *cnt = nullptr;
   int64_t *cnt2 = nullptr;
   int *sing = nullptr, hsing = 0;
   const dim3 block(256), gv((unsigned)phx_div_up(nvert, 256));
-  auto fail = [&](int code) { blockjac_free(b); (void)phx_free(cnt); (void)phx_free(cnt2); (void)phx_free(sing); return code; };
-  if (phx_malloc(&cnt, sizeof(int32_t) * (size_t)(nvert + 1)) != hipSuccess || phx_malloc(&cnt2, sizeof(int64_t) * (size_t)(nvert + 1)) != hipSuccess ||
-      phx_malloc(&b->vptr, sizeof(int32_t) * (size_t)(nvert + 1)) != hipSuccess || phx_malloc(&b->bptr, sizeof(int64_t) * (size_t)(nvert + 1)) != hipSuccess ||
-      phx_malloc(&b->vpos, sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1)) != hipSuccess ||
-      phx_malloc(&b->evert, sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1)) != hipSuccess || phx_malloc(&sing, sizeof(int)) != hipSuccess)
-    return fail(PHX_ERR_HIP);
+  PHX_HIP(tmp.alloc(&cnt, sizeof(int32_t) * (size_t)(nvert + 1)));
+  PHX_HIP(tmp.alloc(&cnt2, sizeof(int64_t) * (size_t)(nvert + 1)));
+  PHX_HIP(phx_malloc(&b->vptr, sizeof(int32_t) * (size_t)(nvert + 1)));
+  PHX_HIP(phx_malloc(&b->bptr, sizeof(int64_t) * (size_t)(nvert + 1)));
+  PHX_HIP(phx_malloc(&b->vpos, sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1)));
+  PHX_HIP(phx_malloc(&b->evert, sizeof(int32_t) * (size_t)std::max<int64_t>(n, 1)));
+  PHX_HIP(tmp.alloc(&sing, sizeof(int)));
   PHX_HIP(hipMemsetAsync(cnt + nvert, 0, sizeof(int32_t), st));
   PHX_HIP(hipMemsetAsync(cnt2 + nvert, 0, sizeof(int64_t), st));
   PHX_HIP(hipMemsetAsync(sing, 0, sizeof(int), st));
@@ -168,24 +172,20 @@ static int blockjac_build(phx_system *s, int nblk, phx_blockjac **out) {
     size_t b1 = 0, b2 = 0;
     PHX_HIP(phx_exclusive_sum(nullptr, b1, cnt, b->vptr, (size_t)(nvert + 1), st));
     PHX_HIP(phx_exclusive_sum(nullptr, b2, cnt2, b->bptr, (size_t)(nvert + 1), st));
-    void *tmp = nullptr;
-    PHX_HIP(phx_malloc(&tmp, std::max(b1, b2) ? std::max(b1, b2) : 16));
-    PHX_HIP(phx_exclusive_sum(tmp, b1, cnt, b->vptr, (size_t)(nvert + 1), st));
-    PHX_HIP(phx_exclusive_sum(tmp, b2, cnt2, b->bptr, (size_t)(nvert + 1), st));
+    void *work = nullptr;
+    PHX_HIP(tmp.alloc(&work, std::max(b1, b2)));
+    PHX_HIP(phx_exclusive_sum(work, b1, cnt, b->vptr, (size_t)(nvert + 1), st));
+    PHX_HIP(phx_exclusive_sum(work, b2, cnt2, b->bptr, (size_t)(nvert + 1), st));
     PHX_HIP(hipMemcpyAsync(&b->nvals, b->bptr + nvert, sizeof(int64_t), hipMemcpyDeviceToHost, st));
     PHX_HIP(hipStreamSynchronize(st));
-    PHX_HIP(phx_free(tmp));
   }
-  if (phx_malloc(&b->M, sizeof(double) * (size_t)std::max<int64_t>(b->nvals, 1)) != hipSuccess) return fail(PHX_ERR_HIP);
+  PHX_HIP(phx_malloc(&b->M, sizeof(double) * (size_t)std::max<int64_t>(b->nvals, 1)));
   k_bj_build<<<dim3((unsigned)phx_div_up(nvert, 4)), block, 0, st>>>(nvert, nblk, s->dof_of_vertex_u, s->full_of_active, s->rowptr, s->col,
                                                                      s->val, s->diag, s->iperm, b->vptr, b->bptr, b->vpos, b->evert, b->M, sing);
   PHX_HIP(hipGetLastError());
   PHX_HIP(hipMemcpyAsync(&hsing, sing, sizeof(int), hipMemcpyDeviceToHost, st));
   PHX_HIP(hipStreamSynchronize(st));
-  PHX_HIP(phx_free(cnt)); PHX_HIP(phx_free(cnt2)); PHX_HIP(phx_free(sing));
-  cnt = nullptr; cnt2 = nullptr; sing = nullptr;
-  if (hsing) { blockjac_free(b); *out = nullptr; return PHX_OK; }   // a singular vertex block: stay with scalar Jacobi
-  *out = b;
+  *out = hsing ? nullptr : own.release();   // a singular vertex block: stay with scalar Jacobi
   return PHX_OK;
 }
 

@@ -368,6 +368,29 @@ int phx_restrict_csr(phx_mesh *coarse, phx_mesh *fine);
 struct phx_rb_item { const void *dev; int bytes; void *host; };
 int phx_read_back(hipStream_t st, const phx_rb_item *items, int n);
 
+// Device temporaries of one call: the stream is synchronised once and the blocks are freed when the list goes out of
+// scope, so a kernel that is only enqueued may still read them.
+struct DevTemps {
+  hipStream_t stream;
+  std::vector<void *> blocks;
+  explicit DevTemps(hipStream_t st) : stream(st) {}
+  DevTemps(const DevTemps &) = delete;
+  DevTemps &operator=(const DevTemps &) = delete;
+  ~DevTemps() {
+    if (blocks.empty()) return;   // nothing to wait for (device-resident inputs, a call that failed at once)
+    (void)hipStreamSynchronize(stream);
+    for (void *p : blocks) (void)phx_free(p);
+  }
+  template <typename T>
+  hipError_t alloc(T **p, size_t bytes) {
+    const hipError_t e = phx_malloc(p, bytes);
+    if (e == hipSuccess) blocks.push_back(*p);
+    return e;
+  }
+  template <typename T>
+  void adopt(T *p) { if (p) blocks.push_back((void *)p); }   // a block some helper allocated (build_list)
+};
+
 int phx_system_build_empty(phx_system *s);  // phx_solve.hip
 // row slots of the assembly as the SELL builder of structured systems reads them (phx_assemble.hip: Slots)
 struct phx_slot_view {

@@ -236,14 +236,14 @@ static int dense_inverse_inplace(double *A, int n, hipStream_t st, int *singular
   double *W = nullptr, *R = nullptr, *Pinv = nullptr;
   int *piv = nullptr, *flag = nullptr, *win[2] = {nullptr, nullptr};
   const size_t nwin = (size_t)phx_div_up(n, 256) * B;
-  auto drop = [&]() { (void)phx_free(win[0]); (void)phx_free(win[1]); (void)phx_free(W); (void)phx_free(R); (void)phx_free(Pinv); (void)phx_free(piv); (void)phx_free(flag); };
-  if (phx_malloc(&win[0], sizeof(int) * nwin) != hipSuccess || phx_malloc(&win[1], sizeof(int) * nwin) != hipSuccess ||
-      phx_malloc(&W, sizeof(double) * (size_t)n * B) != hipSuccess ||
-      phx_malloc(&R, sizeof(double) * (size_t)n * B) != hipSuccess || phx_malloc(&Pinv, sizeof(double) * B * B) != hipSuccess ||
-      phx_malloc(&piv, sizeof(int) * (size_t)(n + B)) != hipSuccess || phx_malloc(&flag, sizeof(int)) != hipSuccess) {
-    drop();
-    return PHX_ERR_HIP;
-  }
+  DevTemps tmp(st);
+  PHX_HIP(tmp.alloc(&win[0], sizeof(int) * nwin));
+  PHX_HIP(tmp.alloc(&win[1], sizeof(int) * nwin));
+  PHX_HIP(tmp.alloc(&W, sizeof(double) * (size_t)n * B));
+  PHX_HIP(tmp.alloc(&R, sizeof(double) * (size_t)n * B));
+  PHX_HIP(tmp.alloc(&Pinv, sizeof(double) * B * B));
+  PHX_HIP(tmp.alloc(&piv, sizeof(int) * (size_t)(n + B)));
+  PHX_HIP(tmp.alloc(&flag, sizeof(int)));
   (void)hipMemsetAsync(flag, 0, sizeof(int), st);
   static bool lds_ok = false;
   if (!lds_ok) {
@@ -281,7 +281,7 @@ static int dense_inverse_inplace(double *A, int n, hipStream_t st, int *singular
   PHX_HIP(hipMemcpyAsync(hp.data(), piv, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st));
   PHX_HIP(hipMemcpyAsync(&hflag, flag, sizeof(int), hipMemcpyDeviceToHost, st));
   PHX_HIP(hipStreamSynchronize(st));
-  if (hflag) { drop(); *singular_out = 1; return PHX_OK; }
+  if (hflag) { *singular_out = 1; return PHX_OK; }
   // rows were swapped k <-> piv[k] for k = 0 .. n-1: the elimination ran on P A with (P A)[k] = A[pos[k]]; (P A)^-1 = A^-1 P^T,
   // so column j of the result is column pos^-1... of A^-1: A^-1[:, pos[k]] = result[:, k]
   for (int k = 0; k < n; ++k) pos[(size_t)k] = k;
@@ -291,7 +291,6 @@ static int dense_inverse_inplace(double *A, int n, hipStream_t st, int *singular
   k_dinv_permute_cols<<<dim3((unsigned)n), b256, sizeof(double) * (size_t)n, st>>>(n, A, piv);
   PHX_HIP(hipGetLastError());
   PHX_HIP(hipStreamSynchronize(st));
-  drop();
   return PHX_OK;
 }
 

@@ -373,7 +373,7 @@ int loc_cell_kind(const phx_mesh *m) {
 // quadrilaterals: every cell an axis-parallel rectangle in tensor-product order (checked once per mesh)
 int loc_require_rect(phx_mesh *m) {
   if (m->cell_type != PHX_QUADRILATERAL || m->rect_checked) return PHX_OK;
-  DevTemps tmp;
+  DevTemps tmp(m->stream);
   int *bad = nullptr;
   PHX_CHECK(rect_bad_alloc(m, tmp, &bad));
   k_loc_rect_check<<<loc_grid(m->nc), dim3(256), 0, m->stream>>>(m->nc, m->cells, m->x, bad);
@@ -387,14 +387,14 @@ int loc_require_rect(phx_mesh *m) {
 int loc_sort_order(hipStream_t st, DevTemps &tmp, int64_t npts, uint32_t *key, int32_t *iota, uint64_t nkeys,
                    int32_t **order) {
   uint32_t *key2 = nullptr;
-  PHX_HIP(tmp.get(&key2, sizeof(uint32_t) * (size_t)npts));
-  PHX_HIP(tmp.get(order, sizeof(int32_t) * (size_t)npts));
+  PHX_HIP(tmp.alloc(&key2, sizeof(uint32_t) * (size_t)npts));
+  PHX_HIP(tmp.alloc(order, sizeof(int32_t) * (size_t)npts));
   unsigned bits = 1;
   while (bits < 32 && ((uint64_t)1 << bits) < nkeys) ++bits;
   size_t bytes = 0;
   PHX_HIP(phx_sort_pairs((void *)nullptr, bytes, key, key2, iota, *order, (size_t)npts, 0u, bits, st));
   char *work = nullptr;
-  PHX_HIP(tmp.get(&work, bytes ? bytes : 16));
+  PHX_HIP(tmp.alloc(&work, bytes ? bytes : 16));
   PHX_HIP(phx_sort_pairs((void *)work, bytes, key, key2, iota, *order, (size_t)npts, 0u, bits, st));
   return PHX_OK;
 }
@@ -412,10 +412,10 @@ int loc_build_bins(phx_mesh *m, double tol) {
   phx_locator *L = g.l;
   L->tol = tol;
   {
-    DevTemps tmp;
+    DevTemps tmp(st);
     const int nblk = (int)std::min<int64_t>(256, phx_div_up(m->nv, 256));
     double *part = nullptr;
-    PHX_HIP(tmp.get(&part, sizeof(double) * 6 * (size_t)nblk));
+    PHX_HIP(tmp.alloc(&part, sizeof(double) * 6 * (size_t)nblk));
     k_loc_bbox<<<dim3(nblk), dim3(256), 0, st>>>(m->nv, D, m->x, part);
     PHX_HIP(hipGetLastError());
     std::vector<double> ph((size_t)nblk * 6);
@@ -445,10 +445,10 @@ int loc_build_bins(phx_mesh *m, double tol) {
     L->nbins = L->n[0] * L->n[1] * L->n[2];
     PHX_REQUIRE(L->nbins < ((int64_t)1 << 32), PHX_ERR_VALUE, "point location: %lld bins", (long long)L->nbins);
     for (int a = 0; a < 3; ++a) { G.n[a] = L->n[a]; G.lo[a] = L->lo[a]; G.inv[a] = L->inv[a]; }
-    DevTemps tmp;
+    DevTemps tmp(st);
     uint32_t *cnt = nullptr;
     int64_t *off = nullptr;
-    PHX_HIP(tmp.get(&cnt, sizeof(uint32_t) * (size_t)(L->nbins + 1)));
+    PHX_HIP(tmp.alloc(&cnt, sizeof(uint32_t) * (size_t)(L->nbins + 1)));
     PHX_HIP(phx_malloc(&off, sizeof(int64_t) * (size_t)(L->nbins + 1)));
     (void)phx_free(L->off);      // (the offsets of a resolution that was given up)
     L->off = off;
@@ -458,7 +458,7 @@ int loc_build_bins(phx_mesh *m, double tol) {
     size_t bytes = 0;
     PHX_HIP(phx_exclusive_sum((void *)nullptr, bytes, cnt, off, (size_t)(L->nbins + 1), st));
     char *work = nullptr;
-    PHX_HIP(tmp.get(&work, bytes ? bytes : 16));
+    PHX_HIP(tmp.alloc(&work, bytes ? bytes : 16));
     PHX_HIP(phx_exclusive_sum((void *)work, bytes, cnt, off, (size_t)(L->nbins + 1), st));
     int64_t total = 0;
     PHX_HIP(hipMemcpyAsync(&total, off + L->nbins, sizeof(int64_t), hipMemcpyDeviceToHost, st));
@@ -503,8 +503,8 @@ int loc_locate_bins(phx_mesh *m, DevTemps &tmp, int64_t npts, const double *pts,
   if (npts > 1) {
     uint32_t *key = nullptr;
     int32_t *iota = nullptr;
-    PHX_HIP(tmp.get(&key, sizeof(uint32_t) * (size_t)npts));
-    PHX_HIP(tmp.get(&iota, sizeof(int32_t) * (size_t)npts));
+    PHX_HIP(tmp.alloc(&key, sizeof(uint32_t) * (size_t)npts));
+    PHX_HIP(tmp.alloc(&iota, sizeof(int32_t) * (size_t)npts));
     k_loc_point_bins<D><<<loc_grid(npts), dim3(256), 0, st>>>(npts, G, pts, key, iota);
     PHX_HIP(hipGetLastError());
     PHX_CHECK(loc_sort_order(st, tmp, npts, key, iota, (uint64_t)L->nbins, &order));
@@ -550,7 +550,7 @@ extern "C" int phx_locate_points(phx_mesh *m, int64_t npts, const double *pts, i
   PHX_HIP(hipSetDevice(m->device));
   hipStream_t st = m->stream;
   const int D = m->gdim;
-  DevTemps tmp;
+  DevTemps tmp(st);
   if (npts == 0) return PHX_OK;
   const double t0 = wall_seconds();
   const double *pd = pts;
@@ -558,13 +558,13 @@ extern "C" int phx_locate_points(phx_mesh *m, int64_t npts, const double *pts, i
   double *xd = xref_out;
   if (loc != PHX_DEVICE) {
     double *b = nullptr;
-    PHX_HIP(tmp.get(&b, sizeof(double) * (size_t)npts * D));
+    PHX_HIP(tmp.alloc(&b, sizeof(double) * (size_t)npts * D));
     PHX_HIP(hipMemcpyAsync(b, pts, sizeof(double) * (size_t)npts * D, hipMemcpyHostToDevice, st));
     pd = b;
   }
   if (loc_out != PHX_DEVICE) {
-    PHX_HIP(tmp.get(&cd, sizeof(int32_t) * (size_t)npts));
-    PHX_HIP(tmp.get(&xd, sizeof(double) * (size_t)npts * D));
+    PHX_HIP(tmp.alloc(&cd, sizeof(int32_t) * (size_t)npts));
+    PHX_HIP(tmp.alloc(&xd, sizeof(double) * (size_t)npts * D));
   }
   double t_build = 0.0;
   if (m->is_box) {
@@ -608,28 +608,28 @@ extern "C" int phx_eval_points(phx_mesh *m, int degree, int ncomp, const double 
   if (npts == 0) return PHX_OK;
   const double t0 = wall_seconds();
   const int64_t ld = degree == 1 ? m->nv : m->nv + m->ne;
-  DevTemps tmp;
+  DevTemps tmp(st);
   const double *ud = values, *xd = xref;
   const int32_t *cd = cells;
   double *od = out, *gd = grad_out;
   if (loc_v != PHX_DEVICE) {
     double *b = nullptr;
-    PHX_HIP(tmp.get(&b, sizeof(double) * (size_t)ld * ncomp));
+    PHX_HIP(tmp.alloc(&b, sizeof(double) * (size_t)ld * ncomp));
     PHX_HIP(hipMemcpyAsync(b, values, sizeof(double) * (size_t)ld * ncomp, hipMemcpyHostToDevice, st));
     ud = b;
   }
   if (loc_p != PHX_DEVICE) {
     int32_t *b = nullptr;
     double *r = nullptr;
-    PHX_HIP(tmp.get(&b, sizeof(int32_t) * (size_t)npts));
-    PHX_HIP(tmp.get(&r, sizeof(double) * (size_t)npts * D));
+    PHX_HIP(tmp.alloc(&b, sizeof(int32_t) * (size_t)npts));
+    PHX_HIP(tmp.alloc(&r, sizeof(double) * (size_t)npts * D));
     PHX_HIP(hipMemcpyAsync(b, cells, sizeof(int32_t) * (size_t)npts, hipMemcpyHostToDevice, st));
     PHX_HIP(hipMemcpyAsync(r, xref, sizeof(double) * (size_t)npts * D, hipMemcpyHostToDevice, st));
     cd = b; xd = r;
   }
   if (loc_out != PHX_DEVICE) {
-    PHX_HIP(tmp.get(&od, sizeof(double) * (size_t)npts * ncomp));
-    if (want_grad) PHX_HIP(tmp.get(&gd, sizeof(double) * (size_t)npts * ncomp * D));
+    PHX_HIP(tmp.alloc(&od, sizeof(double) * (size_t)npts * ncomp));
+    if (want_grad) PHX_HIP(tmp.alloc(&gd, sizeof(double) * (size_t)npts * ncomp * D));
   }
   const bool grad = want_grad != 0;
   switch (loc_cell_kind(m) * 2 + (degree - 1)) {

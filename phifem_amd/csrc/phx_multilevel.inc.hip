@@ -56,25 +56,6 @@ void ml_free(phx_multilevel *ml) {
   delete ml;
 }
 
-// device temporaries of the setup: released on every exit, behind the last kernel queued on `stream`
-struct MlTemps {
-  hipStream_t stream;
-  std::vector<void *> p;
-  explicit MlTemps(hipStream_t st) : stream(st) {}
-  MlTemps(const MlTemps &) = delete;
-  MlTemps &operator=(const MlTemps &) = delete;
-  template <typename T> hipError_t get(T **q, size_t bytes) {
-    hipError_t e = phx_malloc(q, bytes ? bytes : 16);
-    if (e == hipSuccess) p.push_back((void *)*q);
-    return e;
-  }
-  ~MlTemps() {
-    if (p.empty()) return;
-    (void)hipStreamSynchronize(stream);
-    for (void *q : p) (void)phx_free(q);
-  }
-};
-
 dim3 ml_grid(int64_t n) { return dim3((unsigned)phx_div_up(n > 0 ? n : 1, 256)); }
 
 // ---- setup: constrained set and maps of level L
@@ -328,15 +309,14 @@ int ml_build_matrix(phx_mesh *m, const uint8_t *cons, hipStream_t st, MlLevel &l
   const int nvpc = m->ci.nvpc;
   const int64_t nv = m->nv, n = m->nc * (int64_t)nvpc * nvpc;
   PHX_REQUIRE_GRID(std::max(m->nc, nv) + 320, "phx_multilevel_setup");
-  MlTemps tmp(st);
+  DevTemps tmp(st);
   uint64_t *key = nullptr, *key2 = nullptr;
   double *val = nullptr, *val2 = nullptr;
   int32_t *len = nullptr;
-  int64_t *widths = nullptr;
-  PHX_HIP(tmp.get(&key, sizeof(uint64_t) * (size_t)n));
-  PHX_HIP(tmp.get(&key2, sizeof(uint64_t) * (size_t)n));
-  PHX_HIP(tmp.get(&val, sizeof(double) * (size_t)n));
-  PHX_HIP(tmp.get(&val2, sizeof(double) * (size_t)n));
+  PHX_HIP(tmp.alloc(&key, sizeof(uint64_t) * (size_t)n));
+  PHX_HIP(tmp.alloc(&key2, sizeof(uint64_t) * (size_t)n));
+  PHX_HIP(tmp.alloc(&val, sizeof(double) * (size_t)n));
+  PHX_HIP(tmp.alloc(&val2, sizeof(double) * (size_t)n));
   const dim3 block(256);
   if (m->nc > 0) {
     if (nvpc == 3) k_ml_entries<3><<<ml_grid(m->nc), block, 0, st>>>(m->nc, m->x, m->cells, key, val);
@@ -347,25 +327,19 @@ int ml_build_matrix(phx_mesh *m, const uint8_t *cons, hipStream_t st, MlLevel &l
     size_t bytes = 0;
     void *work = nullptr;
     PHX_HIP(phx_sort_pairs(nullptr, bytes, key, key2, val, val2, (size_t)n, 0u, 32u + bits, st));
-    PHX_HIP(tmp.get(&work, bytes));
+    PHX_HIP(tmp.alloc(&work, bytes));
     PHX_HIP(phx_sort_pairs(work, bytes, key, key2, val, val2, (size_t)n, 0u, 32u + bits, st));
   }
   l.nv = nv;
   l.nslices = phx_div_up(nv, 64);
-  PHX_HIP(tmp.get(&len, sizeof(int32_t) * (size_t)nv));
-  PHX_HIP(tmp.get(&widths, sizeof(int64_t) * (size_t)(l.nslices + 1)));
+  PHX_HIP(tmp.alloc(&len, sizeof(int32_t) * (size_t)nv));
   PHX_HIP(phx_malloc(&l.slice_ptr, sizeof(int64_t) * (size_t)(l.nslices + 1)));
   k_ml_rowlen<<<ml_grid(nv), block, 0, st>>>(nv, n, key2, len);
-  k_ml_widths<<<ml_grid(l.nslices + 1), block, 0, st>>>(l.nslices, nv, len, widths);
-  PHX_HIP(hipGetLastError());
-  size_t sbytes = 0;
-  void *swork = nullptr;
-  PHX_HIP(phx_exclusive_sum(nullptr, sbytes, widths, l.slice_ptr, (size_t)(l.nslices + 1), st));
-  PHX_HIP(tmp.get(&swork, sbytes));
-  PHX_HIP(phx_exclusive_sum(swork, sbytes, widths, l.slice_ptr, (size_t)(l.nslices + 1), st));
   int64_t total = 0;
-  PHX_HIP(hipMemcpyAsync(&total, l.slice_ptr + l.nslices, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  PHX_HIP(hipStreamSynchronize(st));
+  PHX_CHECK(slice_offsets(st, tmp, l.nslices, [&](int64_t *widths) {
+    k_ml_widths<<<ml_grid(l.nslices + 1), block, 0, st>>>(l.nslices, nv, len, widths);
+  }, l.slice_ptr, &total));
+  PHX_HIP(hipGetLastError());
   PHX_REQUIRE(total >= 64 * l.nslices && total < ((int64_t)1 << 40), PHX_ERR_HIP, "phx_multilevel_setup: bad SELL size %lld", (long long)total);
   l.sell_nnz = total;
   PHX_HIP(phx_malloc(&l.col, sizeof(int32_t) * (size_t)total));
@@ -419,12 +393,12 @@ int ml_build(phx_system *s, phx_multilevel *ml) {
   PHX_REQUIRE_GRID(std::max(std::max(nv, m->nbf), m->nc * (int64_t)m->ci.nvpc) + 256, "phx_multilevel_setup");
   // constrained set and the maps of level L
   {
-    MlTemps tmp(st);
+    DevTemps tmp(st);
     uint8_t *bnd = nullptr, *used = nullptr;
     int32_t *count = nullptr;
-    PHX_HIP(tmp.get(&bnd, (size_t)nv));
-    PHX_HIP(tmp.get(&used, (size_t)nv));
-    PHX_HIP(tmp.get(&count, sizeof(int32_t)));
+    PHX_HIP(tmp.alloc(&bnd, (size_t)nv));
+    PHX_HIP(tmp.alloc(&used, (size_t)nv));
+    PHX_HIP(tmp.alloc(&count, sizeof(int32_t)));
     PHX_HIP(phx_malloc(&ml->cons, (size_t)nv));
     PHX_HIP(phx_malloc(&ml->vpos, sizeof(int32_t) * (size_t)nv));
     if (!s->u_unscaled) PHX_HIP(phx_malloc(&ml->oscale, sizeof(double) * (size_t)nv));

@@ -1125,10 +1125,11 @@ static int box_local_bbox(phx_system *s, bool p2, int hbb[6]) {
   phx_mesh *m = s->mesh;
   hipStream_t st = m->stream;
   const int64_t n0 = m->box_n[0] + 1, n1 = m->box_n[1] + 1;
+  DevTemps tmp(st);
   int *dbb = nullptr;
   const int init[6] = {INT_MAX, INT_MAX, INT_MAX, -1, -1, -1};
   for (int i = 0; i < 6; ++i) hbb[i] = init[i];
-  PHX_HIP(phx_malloc(&dbb, sizeof(init)));
+  PHX_HIP(tmp.alloc(&dbb, sizeof(init)));
   k_bbox_init<<<1, 6, 0, st>>>(dbb);   // (an upload from a pageable host array is a host round trip)
   if (p2)
     k_active_bbox_p2<<<dim3((unsigned)std::min<int64_t>(phx_div_up(s->nent, 256), 1024)), dim3(256), 0, st>>>(
@@ -1138,7 +1139,6 @@ static int box_local_bbox(phx_system *s, bool p2, int hbb[6]) {
         m->nv, n0, n1, s->dof_of_vertex_u, s->iperm, s->own, m->v2lat, dbb);
   PHX_HIP(hipMemcpyAsync(hbb, dbb, sizeof(init), hipMemcpyDeviceToHost, st));
   PHX_HIP(hipStreamSynchronize(st));
-  PHX_HIP(phx_free(dbb));
   return PHX_OK;
 }
 
@@ -1388,10 +1388,11 @@ static int box_red_maps(phx_system *s) {
   hipStream_t st = s->mesh->stream;
   const int64_t n = s->n, tot = bp->g.plane * bp->g.m[2], nlines = (int64_t)bp->g.m[1] * bp->g.m[2];
   PHX_REQUIRE(tot > 0 && bp->line_iv, PHX_ERR_VALUE, "reduced loop: empty lattice");
+  DevTemps tmp(st);
   int32_t *bidx = nullptr;
   uint8_t *cols = nullptr;
-  PHX_HIP(phx_malloc(&bidx, sizeof(int32_t) * (size_t)n));
-  PHX_HIP(phx_malloc(&cols, (size_t)n));
+  PHX_HIP(tmp.alloc(&bidx, sizeof(int32_t) * (size_t)n));
+  PHX_HIP(tmp.alloc(&cols, (size_t)n));
   for (int k = 0; k < 2; ++k) {
     PHX_HIP(phx_malloc(&bp->red_map[k], sizeof(int32_t) * (size_t)tot));
     PHX_HIP(phx_malloc(&bp->red_any[k], (size_t)nlines));
@@ -1411,8 +1412,6 @@ static int box_red_maps(phx_system *s) {
   }
   PHX_HIP(hipGetLastError());
   PHX_HIP(hipStreamSynchronize(st));   // the temporaries are freed behind their last kernel
-  PHX_HIP(phx_free(bidx));
-  PHX_HIP(phx_free(cols));
   return PHX_OK;
 }
 

@@ -169,18 +169,6 @@ k_prol2_edges(int64_t ncf, int nvpc, int nchild, int nepc, const int32_t *__rest
   }
 }
 
-// frees what it was given when it goes out of scope (every exit of the two entry points below)
-struct DevTemps {
-  std::vector<void *> p;
-  template <typename T> hipError_t get(T **q, size_t bytes) {
-    hipError_t e = phx_malloc(q, bytes);
-    if (e == hipSuccess) p.push_back((void *)*q);
-    return e;
-  }
-  template <typename T> hipError_t alloc(T **q, size_t bytes) { return get(q, bytes); }   // phx_q1rect.inc.hip's name
-  ~DevTemps() { for (void *q : p) (void)phx_free(q); }
-};
-
 double wall_seconds() {
   return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -214,11 +202,11 @@ extern "C" int phx_mesh_refine(phx_mesh *m, phx_mesh **fine_out) {
   PHX_REQUIRE(nvf < INT32_MAX && ncf * (int64_t)m->ci.nfpc < INT32_MAX, PHX_ERR_VALUE,
               "refined mesh too large for 32-bit local ids (%lld vertices, %lld cells)", (long long)nvf, (long long)ncf);
   PHX_REQUIRE_GRID(ncf + 255, "phx_mesh_refine");
-  DevTemps tmp;
+  DevTemps tmp(m->stream);
   double *xf = nullptr;
   int32_t *cf = nullptr;
-  PHX_HIP(tmp.get(&xf, sizeof(double) * (size_t)nvf * m->gdim));
-  PHX_HIP(tmp.get(&cf, sizeof(int32_t) * (size_t)ncf * T.nvpc));
+  PHX_HIP(tmp.alloc(&xf, sizeof(double) * (size_t)nvf * m->gdim));
+  PHX_HIP(tmp.alloc(&cf, sizeof(int32_t) * (size_t)ncf * T.nvpc));
   const double t1 = wall_seconds();
   // fine vertices = the degree-2 Lagrange DoF points, by the kernel Mesh.lagrange_dof_points(2) runs
   PHX_CHECK(phx_lagrange_dof_points(m, 2, xf));
@@ -274,16 +262,16 @@ extern "C" int phx_prolongate(phx_mesh *coarse, phx_mesh *fine, int degree, int 
   PHX_REQUIRE(fine->nv == nv + nmidg + (quad ? coarse->nc : 0), PHX_ERR_VALUE,
               "the fine mesh is not the refinement of the given coarse mesh");
   PHX_REQUIRE_GRID(fine->nc * (int64_t)(T.nepc > 0 ? T.nepc : 1) + 255, "phx_prolongate");
-  DevTemps tmp;
+  DevTemps tmp(st);
   const double *din = in;
   double *dout = out;
   if (loc_in != PHX_DEVICE) {
     double *b = nullptr;
-    PHX_HIP(tmp.get(&b, sizeof(double) * (size_t)ldin * ncomp));
+    PHX_HIP(tmp.alloc(&b, sizeof(double) * (size_t)ldin * ncomp));
     PHX_HIP(hipMemcpyAsync(b, in, sizeof(double) * (size_t)ldin * ncomp, hipMemcpyHostToDevice, st));
     din = b;
   }
-  if (loc_out != PHX_DEVICE) PHX_HIP(tmp.get(&dout, sizeof(double) * (size_t)ldout * ncomp));
+  if (loc_out != PHX_DEVICE) PHX_HIP(tmp.alloc(&dout, sizeof(double) * (size_t)ldout * ncomp));
   const dim3 block(256);
   auto grid = [](int64_t n) { return dim3((unsigned)phx_div_up(n > 0 ? n : 1, 256)); };
   if (degree == 1) {
@@ -291,7 +279,7 @@ extern "C" int phx_prolongate(phx_mesh *coarse, phx_mesh *fine, int degree, int 
     const int32_t *pairs = coarse->edges;
     if (quad) {
       int32_t *fp = nullptr;
-      PHX_HIP(tmp.get(&fp, sizeof(int32_t) * 2 * (size_t)coarse->nf));
+      PHX_HIP(tmp.alloc(&fp, sizeof(int32_t) * 2 * (size_t)coarse->nf));
       k_refine_facet_pairs<<<grid(coarse->nf), block, 0, st>>>(coarse->nf, coarse->f2c, coarse->c2f, coarse->cells, fp);
       pairs = fp;
     }
@@ -305,8 +293,8 @@ extern "C" int phx_prolongate(phx_mesh *coarse, phx_mesh *fine, int degree, int 
     k_prol_copy<<<grid(ldin), block, 0, st>>>(ldin, ncomp, din, ldin, dout, ldout);
     int32_t *owner = nullptr;
     double *w = nullptr;
-    PHX_HIP(tmp.get(&owner, sizeof(int32_t) * (size_t)fine->ne));
-    PHX_HIP(tmp.get(&w, sizeof(T.w)));
+    PHX_HIP(tmp.alloc(&owner, sizeof(int32_t) * (size_t)fine->ne));
+    PHX_HIP(tmp.alloc(&w, sizeof(T.w)));
     std::vector<double> wh((size_t)T.nchild * T.nepc * T.ndof2);
     for (int k = 0; k < T.nchild; ++k)
       for (int j = 0; j < T.nepc; ++j)

@@ -347,18 +347,18 @@ extern "C" int phx_mesh_refine_marked(phx_mesh *m, const uint8_t *cell_marks, co
   hipStream_t st = m->stream;
   const dim3 block(256);
   const hipMemcpyKind up = loc == PHX_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-  DevTemps tmp;
+  DevTemps tmp(st);
   const double t1 = wall_seconds();
   // ---- 1. seed
   uint8_t *emark = nullptr;
-  PHX_HIP(tmp.get(&emark, (size_t)ne + 4));
+  PHX_HIP(tmp.alloc(&emark, (size_t)ne + 4));
   if (edge_marks) PHX_HIP(hipMemcpyAsync(emark, edge_marks, (size_t)ne, up, st));
   else PHX_HIP(hipMemsetAsync(emark, 0, (size_t)ne, st));
   if (cell_marks) {
     const uint8_t *cm = cell_marks;
     if (loc != PHX_DEVICE) {
       uint8_t *b = nullptr;
-      PHX_HIP(tmp.get(&b, (size_t)nc));
+      PHX_HIP(tmp.alloc(&b, (size_t)nc));
       PHX_HIP(hipMemcpyAsync(b, cell_marks, (size_t)nc, hipMemcpyHostToDevice, st));
       cm = b;
     }
@@ -367,8 +367,8 @@ extern "C" int phx_mesh_refine_marked(phx_mesh *m, const uint8_t *cell_marks, co
   // ---- 2. closure
   uint32_t *ordpk = nullptr;
   int32_t *changed = nullptr;
-  PHX_HIP(tmp.get(&ordpk, sizeof(uint32_t) * (size_t)nc));
-  PHX_HIP(tmp.get(&changed, sizeof(int32_t)));
+  PHX_HIP(tmp.alloc(&ordpk, sizeof(uint32_t) * (size_t)nc));
+  PHX_HIP(tmp.alloc(&changed, sizeof(int32_t)));
   if (tri) k_rm_order<3><<<rm_grid(nc), block, 0, st>>>(nc, m->x, m->cells, ordpk);
   else k_rm_order<4><<<rm_grid(nc), block, 0, st>>>(nc, m->x, m->cells, ordpk);
   PHX_HIP(hipGetLastError());
@@ -391,11 +391,11 @@ extern "C" int phx_mesh_refine_marked(phx_mesh *m, const uint8_t *cell_marks, co
   int32_t *list = nullptr;
   int64_t nm = 0;
   PHX_CHECK(phx_select_indices(st, ne, SelMarkedEdge{emark}, &list, &nm));
-  tmp.p.push_back(list);
+  tmp.adopt(list);
   int32_t *erank = nullptr, *cnt = nullptr, *off = nullptr;
-  PHX_HIP(tmp.get(&erank, sizeof(int32_t) * (size_t)ne));
-  PHX_HIP(tmp.get(&cnt, sizeof(int32_t) * (size_t)(nc + 1)));
-  PHX_HIP(tmp.get(&off, sizeof(int32_t) * (size_t)(nc + 1)));
+  PHX_HIP(tmp.alloc(&erank, sizeof(int32_t) * (size_t)ne));
+  PHX_HIP(tmp.alloc(&cnt, sizeof(int32_t) * (size_t)(nc + 1)));
+  PHX_HIP(tmp.alloc(&off, sizeof(int32_t) * (size_t)(nc + 1)));
   k_rm_rank<<<rm_grid(nm), block, 0, st>>>(nm, list, erank);
   if (tri) k_rm_count<3><<<rm_grid(nc + 1), block, 0, st>>>(nc, m->c2e, ordpk, emark, cnt);
   else k_rm_count<4><<<rm_grid(nc + 1), block, 0, st>>>(nc, m->c2e, ordpk, emark, cnt);
@@ -403,7 +403,7 @@ extern "C" int phx_mesh_refine_marked(phx_mesh *m, const uint8_t *cell_marks, co
   size_t sbytes = 0;
   void *stmp = nullptr;
   PHX_HIP(phx_exclusive_sum(nullptr, sbytes, cnt, off, (size_t)(nc + 1), st));
-  PHX_HIP(tmp.get(&stmp, sbytes ? sbytes : 16));
+  PHX_HIP(tmp.alloc(&stmp, sbytes ? sbytes : 16));
   PHX_HIP(phx_exclusive_sum(stmp, sbytes, cnt, off, (size_t)(nc + 1), st));
   int32_t total = 0;
   PHX_HIP(hipMemcpyAsync(&total, off + nc, sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -414,10 +414,10 @@ extern "C" int phx_mesh_refine_marked(phx_mesh *m, const uint8_t *cell_marks, co
   double *xf = nullptr;
   int32_t *cf = nullptr, *parent = nullptr;
   int8_t *child = nullptr;
-  PHX_HIP(tmp.get(&xf, sizeof(double) * (size_t)nvf * m->gdim));
-  PHX_HIP(tmp.get(&cf, sizeof(int32_t) * (size_t)ncf * nvpc));
-  PHX_HIP(tmp.get(&parent, sizeof(int32_t) * (size_t)ncf));
-  PHX_HIP(tmp.get(&child, (size_t)ncf * nvpc));
+  PHX_HIP(tmp.alloc(&xf, sizeof(double) * (size_t)nvf * m->gdim));
+  PHX_HIP(tmp.alloc(&cf, sizeof(int32_t) * (size_t)ncf * nvpc));
+  PHX_HIP(tmp.alloc(&parent, sizeof(int32_t) * (size_t)ncf));
+  PHX_HIP(tmp.alloc(&child, (size_t)ncf * nvpc));
   k_rm_coords<<<rm_grid(nvf), block, 0, st>>>(nvf, nv, m->gdim, m->x, list, m->edges, xf);
   if (tri) k_rm_write<3><<<rm_grid(nc), block, 0, st>>>(nc, m->cells, m->c2e, ordpk, emark, erank, off, nv, cf, parent, child);
   else k_rm_write<4><<<rm_grid(nc), block, 0, st>>>(nc, m->cells, m->c2e, ordpk, emark, erank, off, nv, cf, parent, child);
@@ -433,7 +433,7 @@ extern "C" int phx_mesh_refine_marked(phx_mesh *m, const uint8_t *cell_marks, co
   f->rm_marked = true;
   f->rm_nmid = nm;
   f->rm_parent = parent; f->rm_child = child; f->rm_mid = list;          // they leave the guard
-  for (void *q : {(void *)parent, (void *)child, (void *)list}) tmp.p.erase(std::find(tmp.p.begin(), tmp.p.end(), q));
+  for (void *q : {(void *)parent, (void *)child, (void *)list}) tmp.blocks.erase(std::find(tmp.blocks.begin(), tmp.blocks.end(), q));
   f->timings[5] = t1 - t0;                 // edge numbering of the coarse mesh (0 when it existed)
   f->timings[6] = t2 - t1;                 // seed, closure, numbering and write
   f->timings[7] = wall_seconds() - t2;     // creation of the fine mesh
@@ -461,16 +461,16 @@ int phx_prolongate_marked(phx_mesh *coarse, phx_mesh *fine, int degree, int ncom
   const int64_t ldin = degree == 1 ? nv : nv + coarse->ne;
   const int64_t ldout = degree == 1 ? fine->nv : fine->nv + fine->ne;
   PHX_REQUIRE_GRID(fine->nc * (int64_t)nepc + 255, "phx_prolongate");
-  DevTemps tmp;
+  DevTemps tmp(st);
   const double *din = in;
   double *dout = out;
   if (loc_in != PHX_DEVICE) {
     double *b = nullptr;
-    PHX_HIP(tmp.get(&b, sizeof(double) * (size_t)ldin * ncomp));
+    PHX_HIP(tmp.alloc(&b, sizeof(double) * (size_t)ldin * ncomp));
     PHX_HIP(hipMemcpyAsync(b, in, sizeof(double) * (size_t)ldin * ncomp, hipMemcpyHostToDevice, st));
     din = b;
   }
-  if (loc_out != PHX_DEVICE) PHX_HIP(tmp.get(&dout, sizeof(double) * (size_t)ldout * ncomp));
+  if (loc_out != PHX_DEVICE) PHX_HIP(tmp.alloc(&dout, sizeof(double) * (size_t)ldout * ncomp));
   const dim3 block(256);
   k_prol_copy<<<rm_grid(nv), block, 0, st>>>(nv, ncomp, din, ldin, dout, ldout);
   if (degree == 1) {
@@ -478,7 +478,7 @@ int phx_prolongate_marked(phx_mesh *coarse, phx_mesh *fine, int degree, int ncom
   } else {
     k_rm_prol_edge_dofs<<<rm_grid(nm), block, 0, st>>>(nm, fine->rm_mid, ncomp, din + nv, ldin, dout + nv, ldout);
     int32_t *owner = nullptr;
-    PHX_HIP(tmp.get(&owner, sizeof(int32_t) * (size_t)fine->ne));
+    PHX_HIP(tmp.alloc(&owner, sizeof(int32_t) * (size_t)fine->ne));
     PHX_HIP(hipMemsetAsync(owner, 0x7f, sizeof(int32_t) * (size_t)fine->ne, st));
     k_rm_prol2_owner<<<rm_grid(fine->nc * nepc), block, 0, st>>>(fine->nc * nepc, nepc, fine->c2e, fine->rm_parent, owner);
     if (tri)

@@ -59,14 +59,14 @@ int phx_restrict_csr(phx_mesh *coarse, phx_mesh *fine) {
   PHX_REQUIRE(n < INT32_MAX, PHX_ERR_VALUE, "phx_restrict: %lld entries exceed 32-bit offsets", (long long)n);
   PHX_REQUIRE_GRID(nv + nm + 256, "phx_restrict");
   hipStream_t st = coarse->stream;
-  DevTemps tmp;
+  DevTemps tmp(st);
   int32_t *ptr = nullptr, *idx = nullptr, *val = nullptr;
   uint32_t *key = nullptr, *key2 = nullptr;
-  PHX_HIP(tmp.get(&ptr, sizeof(int32_t) * (size_t)(nv + 1)));
-  PHX_HIP(tmp.get(&idx, sizeof(int32_t) * (size_t)(n + 1)));
-  PHX_HIP(tmp.get(&val, sizeof(int32_t) * (size_t)(n + 1)));
-  PHX_HIP(tmp.get(&key, sizeof(uint32_t) * (size_t)(n + 1)));
-  PHX_HIP(tmp.get(&key2, sizeof(uint32_t) * (size_t)(n + 1)));
+  PHX_HIP(tmp.alloc(&ptr, sizeof(int32_t) * (size_t)(nv + 1)));
+  PHX_HIP(tmp.alloc(&idx, sizeof(int32_t) * (size_t)(n + 1)));
+  PHX_HIP(tmp.alloc(&val, sizeof(int32_t) * (size_t)(n + 1)));
+  PHX_HIP(tmp.alloc(&key, sizeof(uint32_t) * (size_t)(n + 1)));
+  PHX_HIP(tmp.alloc(&key2, sizeof(uint32_t) * (size_t)(n + 1)));
   const dim3 block(256);
   if (nm > 0) {
     k_rs_entries<<<rm_grid(nm), block, 0, st>>>(nm, fine->rm_marked ? fine->rm_mid : nullptr, coarse->edges, nv, key, val);
@@ -76,14 +76,14 @@ int phx_restrict_csr(phx_mesh *coarse, phx_mesh *fine) {
     size_t bytes = 0;
     void *work = nullptr;
     PHX_HIP(phx_sort_pairs(nullptr, bytes, key, key2, val, idx, (size_t)n, 0u, bits, st));
-    PHX_HIP(tmp.get(&work, bytes ? bytes : 16));
+    PHX_HIP(tmp.alloc(&work, bytes ? bytes : 16));
     PHX_HIP(phx_sort_pairs(work, bytes, key, key2, val, idx, (size_t)n, 0u, bits, st));
   }
   k_rs_ptr<<<rm_grid(nv + 1), block, 0, st>>>(nv, n, key2, ptr);
   PHX_HIP(hipGetLastError());
   PHX_HIP(hipStreamSynchronize(st));
   fine->rs_ptr = ptr; fine->rs_idx = idx;                                  // they leave the guard
-  for (void *q : {(void *)ptr, (void *)idx}) tmp.p.erase(std::find(tmp.p.begin(), tmp.p.end(), q));
+  for (void *q : {(void *)ptr, (void *)idx}) tmp.blocks.erase(std::find(tmp.blocks.begin(), tmp.blocks.end(), q));
   return PHX_OK;
 }
 
@@ -104,16 +104,16 @@ extern "C" int phx_restrict(phx_mesh *coarse, phx_mesh *fine, int degree, int nc
   PHX_REQUIRE(fine->nv == nv + nm, PHX_ERR_VALUE, "the fine mesh is not the refinement of the given coarse mesh");
   PHX_CHECK(phx_restrict_csr(coarse, fine));
   const int64_t ldin = fine->nv, ldout = nv;
-  DevTemps tmp;
+  DevTemps tmp(st);
   const double *din = in;
   double *dout = out;
   if (loc_in != PHX_DEVICE) {
     double *b = nullptr;
-    PHX_HIP(tmp.get(&b, sizeof(double) * (size_t)ldin * ncomp));
+    PHX_HIP(tmp.alloc(&b, sizeof(double) * (size_t)ldin * ncomp));
     PHX_HIP(hipMemcpyAsync(b, in, sizeof(double) * (size_t)ldin * ncomp, hipMemcpyHostToDevice, st));
     din = b;
   }
-  if (loc_out != PHX_DEVICE) PHX_HIP(tmp.get(&dout, sizeof(double) * (size_t)ldout * ncomp));
+  if (loc_out != PHX_DEVICE) PHX_HIP(tmp.alloc(&dout, sizeof(double) * (size_t)ldout * ncomp));
   k_restrict<<<rm_grid(nv), dim3(256), 0, st>>>(nv, fine->rs_ptr, fine->rs_idx, ncomp, din, ldin, dout, ldout);
   PHX_HIP(hipGetLastError());
   if (loc_out != PHX_DEVICE)

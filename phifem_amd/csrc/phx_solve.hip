@@ -15,6 +15,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <vector>
 
 #include "phx_common.h"
@@ -199,64 +200,79 @@ k_sell_index(int64_t nslices, const int64_t *__restrict__ slice_ptr, double *sva
   }
 }
 
+// ---- host steps shared by the builds of the solver formats ("Host side of the solver formats")
+// solver workspace: 9 vectors + scalars, on the device and pinned
+static int system_workspace(phx_system *s) {
+  PHX_HIP(phx_malloc(&s->work, sizeof(double) * (s->n > 0 ? (size_t)s->n * 9 : 16)));
+  PHX_HIP(phx_malloc(&s->scal, sizeof(double) * PHX_SCAL_DOUBLES));
+  PHX_CHECK(phx_mesh_pinned_scalars(s->mesh, &s->scal_h));
+  return PHX_OK;
+}
+
+// slice_ptr [nslices + 1] = exclusive sum of the widths `launch_widths` writes (the last one 0); *total = its last entry,
+// on the host: one round trip.  The widths and the scan's scratch belong to `tmp`.
+template <typename Widths>
+static int slice_offsets(hipStream_t st, DevTemps &tmp, int64_t nslices, Widths launch_widths, int64_t *slice_ptr,
+                         int64_t *total) {
+  int64_t *widths = nullptr;
+  PHX_HIP(tmp.alloc(&widths, sizeof(int64_t) * (size_t)(nslices + 1)));
+  launch_widths(widths);
+  size_t bytes = 0;
+  void *work = nullptr;
+  PHX_HIP(phx_exclusive_sum(nullptr, bytes, widths, slice_ptr, (size_t)(nslices + 1), st));
+  PHX_HIP(tmp.alloc(&work, bytes));
+  PHX_HIP(phx_exclusive_sum(work, bytes, widths, slice_ptr, (size_t)(nslices + 1), st));
+  PHX_HIP(hipMemcpyAsync(total, slice_ptr + nslices, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  PHX_HIP(hipStreamSynchronize(st));
+  return PHX_OK;
+}
+
 int phx_system_build_sell(phx_system *s) {
   phx_mesh *m = s->mesh;
   const int64_t n = s->n;
   PHX_REQUIRE(n / SELL_WINDOW < (1 << 21), PHX_ERR_VALUE, "system too large for the SELL sort key");
-  uint32_t *keys = nullptr, *keys2 = nullptr;
-  int32_t *rows = nullptr;
-  PHX_HIP(phx_malloc(&keys, sizeof(uint32_t) * (size_t)n));
-  PHX_HIP(phx_malloc(&keys2, sizeof(uint32_t) * (size_t)n));
-  PHX_HIP(phx_malloc(&rows, sizeof(int32_t) * (size_t)n));
-  PHX_HIP(phx_malloc(&s->perm, sizeof(int32_t) * (size_t)n));
-  PHX_HIP(phx_malloc(&s->iperm, sizeof(int32_t) * (size_t)n));
-  const dim3 block(256), grid((unsigned)phx_div_up(n, 256));
-  unsigned long long *dtotal = nullptr;
-  PHX_HIP(phx_malloc(&dtotal, sizeof(unsigned long long)));
-  PHX_HIP(hipMemsetAsync(dtotal, 0, sizeof(unsigned long long), m->stream));
-  k_row_lengths<<<grid, block, 0, m->stream>>>(n, s->rowptr, s->col, s->val, s->row_nz, keys, rows, dtotal, SELL_WINDOW);
-  unsigned long long htotal = 0;
-  PHX_HIP(hipMemcpyAsync(&htotal, dtotal, sizeof(htotal), hipMemcpyDeviceToHost, m->stream));
-  PHX_HIP(hipStreamSynchronize(m->stream));
-  PHX_HIP(phx_free(dtotal));
-  s->sell_true_nnz = (int64_t)htotal;
-  // only the bits that can differ are sorted: 10 length bits (+ the window index if windowed)
-  int end_bit = 10;
-  for (int64_t w = (n - 1) / SELL_WINDOW; w > 0; w >>= 1) ++end_bit;
-  size_t bytes = 0;
-  PHX_HIP(phx_sort_pairs(nullptr, bytes, keys, keys2, rows, s->perm, (size_t)n, 0, end_bit, m->stream));
-  void *tmp = nullptr;
-  PHX_HIP(phx_malloc(&tmp, bytes ? bytes : 16));
-  PHX_HIP(phx_sort_pairs(tmp, bytes, keys, keys2, rows, s->perm, (size_t)n, 0, end_bit, m->stream));
-  k_invert_perm<<<grid, block, 0, m->stream>>>(n, s->perm, s->iperm);
-  s->nslices = phx_div_up(n, SELL_C);
-  int64_t *widths = nullptr;
-  PHX_HIP(phx_malloc(&widths, sizeof(int64_t) * (size_t)(s->nslices + 1)));
-  PHX_HIP(phx_malloc(&s->slice_ptr, sizeof(int64_t) * (size_t)(s->nslices + 1)));
-  k_slice_widths<<<dim3((unsigned)phx_div_up(s->nslices + 1, 256)), block, 0, m->stream>>>(
-      s->nslices, n, keys2, widths);
   {
-    size_t b2 = 0;
-    PHX_HIP(phx_exclusive_sum(nullptr, b2, widths, s->slice_ptr, (size_t)(s->nslices + 1), m->stream));
-    void *t2 = nullptr;
-    PHX_HIP(phx_malloc(&t2, b2 ? b2 : 16));
-    PHX_HIP(phx_exclusive_sum(t2, b2, widths, s->slice_ptr, (size_t)(s->nslices + 1), m->stream));
+    DevTemps tmp(m->stream);   // back behind the last synchronisation, before the workspace is allocated
+    uint32_t *keys = nullptr, *keys2 = nullptr;
+    int32_t *rows = nullptr;
+    PHX_HIP(tmp.alloc(&keys, sizeof(uint32_t) * (size_t)n));
+    PHX_HIP(tmp.alloc(&keys2, sizeof(uint32_t) * (size_t)n));
+    PHX_HIP(tmp.alloc(&rows, sizeof(int32_t) * (size_t)n));
+    PHX_HIP(phx_malloc(&s->perm, sizeof(int32_t) * (size_t)n));
+    PHX_HIP(phx_malloc(&s->iperm, sizeof(int32_t) * (size_t)n));
+    const dim3 block(256), grid((unsigned)phx_div_up(n, 256));
+    unsigned long long *dtotal = nullptr, htotal = 0;
+    PHX_HIP(tmp.alloc(&dtotal, sizeof(unsigned long long)));
+    PHX_HIP(hipMemsetAsync(dtotal, 0, sizeof(unsigned long long), m->stream));
+    k_row_lengths<<<grid, block, 0, m->stream>>>(n, s->rowptr, s->col, s->val, s->row_nz, keys, rows, dtotal, SELL_WINDOW);
+    PHX_HIP(hipMemcpyAsync(&htotal, dtotal, sizeof(htotal), hipMemcpyDeviceToHost, m->stream));
     PHX_HIP(hipStreamSynchronize(m->stream));
-    PHX_HIP(phx_free(t2));
-  }
-  PHX_HIP(hipMemcpy(&s->sell_nnz, s->slice_ptr + s->nslices, sizeof(int64_t), hipMemcpyDeviceToHost));
-  PHX_HIP(phx_malloc(&s->sell_col, sizeof(int32_t) * (size_t)s->sell_nnz));
-  PHX_HIP(phx_malloc(&s->sell_val, sizeof(double) * (size_t)s->sell_nnz));
-  PHX_HIP(phx_malloc(&s->sell_val_raw, sizeof(double) * (size_t)s->sell_nnz));
-  k_sell_fill<<<dim3((unsigned)phx_div_up(s->nslices * SELL_C, 256)), block, 0, m->stream>>>(
-      n, s->rowptr, s->col, s->val, s->diag, s->perm, s->iperm, s->slice_ptr, s->sell_col,
-      s->sell_val, s->sell_val_raw);
-  PHX_HIP(hipGetLastError());
-  {
+    s->sell_true_nnz = (int64_t)htotal;
+    // only the bits that can differ are sorted: 10 length bits (+ the window index if windowed)
+    int end_bit = 10;
+    for (int64_t w = (n - 1) / SELL_WINDOW; w > 0; w >>= 1) ++end_bit;
+    size_t bytes = 0;
+    PHX_HIP(phx_sort_pairs(nullptr, bytes, keys, keys2, rows, s->perm, (size_t)n, 0, end_bit, m->stream));
+    void *work = nullptr;
+    PHX_HIP(tmp.alloc(&work, bytes));
+    PHX_HIP(phx_sort_pairs(work, bytes, keys, keys2, rows, s->perm, (size_t)n, 0, end_bit, m->stream));
+    k_invert_perm<<<grid, block, 0, m->stream>>>(n, s->perm, s->iperm);
+    s->nslices = phx_div_up(n, SELL_C);
+    PHX_HIP(phx_malloc(&s->slice_ptr, sizeof(int64_t) * (size_t)(s->nslices + 1)));
+    PHX_CHECK(slice_offsets(m->stream, tmp, s->nslices, [&](int64_t *widths) {
+      k_slice_widths<<<dim3((unsigned)phx_div_up(s->nslices + 1, 256)), block, 0, m->stream>>>(s->nslices, n, keys2, widths);
+    }, s->slice_ptr, &s->sell_nnz));
+    PHX_HIP(phx_malloc(&s->sell_col, sizeof(int32_t) * (size_t)s->sell_nnz));
+    PHX_HIP(phx_malloc(&s->sell_val, sizeof(double) * (size_t)s->sell_nnz));
+    PHX_HIP(phx_malloc(&s->sell_val_raw, sizeof(double) * (size_t)s->sell_nnz));
+    k_sell_fill<<<dim3((unsigned)phx_div_up(s->nslices * SELL_C, 256)), block, 0, m->stream>>>(
+        n, s->rowptr, s->col, s->val, s->diag, s->perm, s->iperm, s->slice_ptr, s->sell_col,
+        s->sell_val, s->sell_val_raw);
+    PHX_HIP(hipGetLastError());
     PHX_HIP(phx_malloc(&s->sell_kind, (size_t)s->nslices * 2));
     s->sell_kind_raw = s->sell_kind + s->nslices;
     unsigned long long *tot = nullptr, htot[8];
-    PHX_HIP(phx_malloc(&tot, sizeof(htot)));
+    PHX_HIP(tmp.alloc(&tot, sizeof(htot)));
     PHX_HIP(hipMemsetAsync(tot, 0, sizeof(htot), m->stream));
     const dim3 gi((unsigned)phx_div_up(s->nslices, 4));
     k_sell_index<<<gi, block, 0, m->stream>>>(s->nslices, s->slice_ptr, s->sell_val, s->sell_kind, tot, m->spmv_value_index);
@@ -265,20 +281,12 @@ int phx_system_build_sell(phx_system *s) {
     PHX_HIP(hipGetLastError());
     PHX_HIP(hipMemcpyAsync(htot, tot, sizeof(htot), hipMemcpyDeviceToHost, m->stream));
     PHX_HIP(hipStreamSynchronize(m->stream));
-    PHX_HIP(phx_free(tot));
     s->sell_indexed_slices = (int64_t)htot[0];
     s->sell_indexed_large = (int64_t)htot[2];
     // what one SpMV of the solve streams from the matrix: columns + value stream + slice table
     s->sell_stream_bytes = 4 * s->sell_nnz + (int64_t)htot[1] + 9 * s->nslices;
   }
-  PHX_HIP(hipStreamSynchronize(m->stream));
-  PHX_HIP(phx_free(tmp)); PHX_HIP(phx_free(keys)); PHX_HIP(phx_free(keys2)); PHX_HIP(phx_free(rows));
-  PHX_HIP(phx_free(widths));
-  // solver workspace: 9 vectors + scalars
-  PHX_HIP(phx_malloc(&s->work, sizeof(double) * (size_t)n * 9));
-  PHX_HIP(phx_malloc(&s->scal, sizeof(double) * PHX_SCAL_DOUBLES));
-  PHX_CHECK(phx_mesh_pinned_scalars(s->mesh, &s->scal_h));
-  return PHX_OK;
+  return system_workspace(s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -433,27 +441,26 @@ k_csort(int64_t n, const uint32_t *__restrict__ keys, const int32_t *__restrict_
     for (int i = lane; i < nk; i += 64) H[(int64_t)i * nseg + seg] = c[i];
 }
 
-// keys_out / vals_out = the pairs sorted by key (< 1024), stable.  `later`: temporaries, freed by the caller behind its
-// next synchronisation.
+// keys_out / vals_out = the pairs sorted by key (< 1024), stable.  The temporaries belong to `tmp`: its end lies behind
+// the caller's next synchronisation.
 static int phx_counting_sort_pairs(hipStream_t st, const uint32_t *keys, uint32_t *keys_out, const int32_t *vals,
-                                   int32_t *vals_out, int64_t n, uint32_t klo, int nk, std::vector<void *> *later) {
+                                   int32_t *vals_out, int64_t n, uint32_t klo, int nk, DevTemps &tmp) {
   if (n <= 0) return PHX_OK;
   PHX_REQUIRE(nk >= 1 && nk <= PHX_CSORT_KEYS, PHX_ERR_VALUE, "counting sort over %d keys", nk);
   const int64_t nseg = phx_div_up(n, (int64_t)PHX_CSORT_SEG);
   const size_t nh = (size_t)nk * (size_t)nseg;
   int32_t *H = nullptr, *H2 = nullptr;
-  PHX_HIP(phx_malloc(&H, sizeof(int32_t) * nh));
-  PHX_HIP(phx_malloc(&H2, sizeof(int32_t) * nh));
+  PHX_HIP(tmp.alloc(&H, sizeof(int32_t) * nh));
+  PHX_HIP(tmp.alloc(&H2, sizeof(int32_t) * nh));
   const dim3 grid((unsigned)phx_div_up(nseg, 4)), block(256);
   k_csort<false><<<grid, block, 0, st>>>(n, keys, vals, nseg, klo, nk, H, nullptr, nullptr);
   size_t bytes = 0;
   PHX_HIP(phx_exclusive_sum(nullptr, bytes, H, H2, nh, st));
-  void *tmp = nullptr;
-  PHX_HIP(phx_malloc(&tmp, bytes ? bytes : 16));
-  PHX_HIP(phx_exclusive_sum(tmp, bytes, H, H2, nh, st));
+  void *work = nullptr;
+  PHX_HIP(tmp.alloc(&work, bytes));
+  PHX_HIP(phx_exclusive_sum(work, bytes, H, H2, nh, st));
   k_csort<true><<<grid, block, 0, st>>>(n, keys, vals, nseg, klo, nk, H2, keys_out, vals_out);
   PHX_HIP(hipGetLastError());
-  later->push_back(H); later->push_back(H2); later->push_back(tmp);
   return PHX_OK;
 }
 
@@ -773,40 +780,122 @@ __global__ void k_map_i32(int64_t n, const int32_t *__restrict__ map, int32_t *_
 }
 
 struct U8AsI32 { __host__ __device__ int32_t operator()(const uint8_t &a) const { return (int32_t)a; } };
-static int scan_u8(hipStream_t st, const uint8_t *flags, int32_t *out, int64_t n, int32_t *total) {
+// out = exclusive sum of the flags, *total = their sum on the host (one round trip); the scratch belongs to `tmp`
+static int scan_u8(hipStream_t st, const uint8_t *flags, int32_t *out, int64_t n, int32_t *total, DevTemps &tmp) {
   auto it = rocprim::make_transform_iterator(flags, U8AsI32());
   size_t bytes = 0;
   PHX_HIP(phx_exclusive_sum(nullptr, bytes, it, out, (size_t)(n), st));
-  void *tmp = nullptr;
-  PHX_HIP(phx_malloc(&tmp, bytes ? bytes : 16));
-  PHX_HIP(phx_exclusive_sum(tmp, bytes, it, out, (size_t)(n), st));
+  void *work = nullptr;
+  PHX_HIP(tmp.alloc(&work, bytes));
+  PHX_HIP(phx_exclusive_sum(work, bytes, it, out, (size_t)(n), st));
   int32_t last = 0;
   uint8_t lastf = 0;
   const phx_rb_item rb[2] = {{out + (n - 1), 4, &last}, {flags + (n - 1), 1, &lastf}};
   PHX_CHECK(phx_read_back(st, rb, 2));
-  PHX_HIP(phx_free(tmp));
   *total = last + (int32_t)lastf;
   return PHX_OK;
 }
 
 static int scan_u8_pair(hipStream_t st, const uint8_t *fa, int32_t *oa, int32_t *ta, const uint8_t *fb, int32_t *ob,
-                        int32_t *tb, int64_t n) {
+                        int32_t *tb, int64_t n, DevTemps &tmp) {
   auto ia = rocprim::make_transform_iterator(fa, U8AsI32());
   auto ib = rocprim::make_transform_iterator(fb, U8AsI32());
   size_t bytes = 0;
   PHX_HIP(phx_exclusive_sum(nullptr, bytes, ia, oa, (size_t)(n), st));
-  void *tmp = nullptr;
-  PHX_HIP(phx_malloc(&tmp, bytes ? bytes : 16));
-  PHX_HIP(phx_exclusive_sum(tmp, bytes, ia, oa, (size_t)(n), st));
-  PHX_HIP(phx_exclusive_sum(tmp, bytes, ib, ob, (size_t)(n), st));
+  void *work = nullptr;
+  PHX_HIP(tmp.alloc(&work, bytes));
+  PHX_HIP(phx_exclusive_sum(work, bytes, ia, oa, (size_t)(n), st));
+  PHX_HIP(phx_exclusive_sum(work, bytes, ib, ob, (size_t)(n), st));
   int32_t last[2] = {0, 0};
   uint8_t lastf[2] = {0, 0};
   const phx_rb_item rb[4] = {{oa + (n - 1), 4, &last[0]}, {fa + (n - 1), 1, &lastf[0]}, {ob + (n - 1), 4, &last[1]},
                              {fb + (n - 1), 1, &lastf[1]}};
   PHX_CHECK(phx_read_back(st, rb, 4));
-  PHX_HIP(phx_free(tmp));
   *ta = last[0] + (int32_t)lastf[0];
   *tb = last[1] + (int32_t)lastf[1];
+  return PHX_OK;
+}
+
+// len[i] = entries the SELL copy keeps of stored row list[i] (`len` belongs to `tmp`), their diagonals in s->diag,
+// htot = {structural, kept} entries summed over the list: one host round trip.  c0 (nullable): rows flagged there are
+// stencil rows without slots.
+static int stored_row_meta(phx_system *s, const phx_slot_view &sv, int32_t nent, const uint8_t *c0, int64_t ns,
+                           const int32_t *list, DevTemps &tmp, int32_t **len_out, unsigned long long htot[2]) {
+  phx_mesh *m = s->mesh;
+  hipStream_t st = m->stream;
+  const dim3 block(256);
+  DevTemps now(st);   // released behind the read-back below
+  int32_t *len = nullptr, *nstruct = nullptr;
+  unsigned long long *dtot = nullptr;
+  PHX_HIP(tmp.alloc(&len, sizeof(int32_t) * (size_t)std::max<int64_t>(ns, 1)));
+  PHX_HIP(now.alloc(&nstruct, sizeof(int32_t) * (size_t)std::max<int64_t>(ns, 1)));
+  PHX_HIP(now.alloc(&dtot, 2 * sizeof(unsigned long long)));
+  PHX_HIP(hipMemsetAsync(dtot, 0, 2 * sizeof(unsigned long long), st));
+  if (ns > 0) {
+    PHX_REQUIRE_GRID(ns * 64, "stored-row scan");
+    if (sv.occ)
+      k_slot_row_meta_box<<<dim3((unsigned)phx_div_up(ns * 64, 256)), block, 0, st>>>(
+          ns, list, sv, c0, s->nu, m->gdim, len, nstruct, s->diag);
+    else
+      k_slot_row_meta<<<dim3((unsigned)phx_div_up(ns * 64, 256)), block, 0, st>>>(
+          ns, list, sv, c0, nent, s->dof_of_vertex_u, s->dof_of_vertex_p, m->gdim, len, nstruct, s->diag);
+    k_sum2_i32<<<dim3((unsigned)std::min<int64_t>(phx_div_up(ns, 256), 512)), block, 0, st>>>(ns, nstruct, len, dtot);
+  }
+  PHX_HIP(hipMemcpyAsync(htot, dtot, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  PHX_HIP(hipStreamSynchronize(st));
+  *len_out = len;
+  return PHX_OK;
+}
+
+// SELL over the ns stored rows of a structured system, in slices of 16 rows with four lanes per row (k_spmv_sell):
+// slice_ptr, sell_rows, the three entry arrays, the kind bytes, sell_nnz and sell_stream_bytes of `s`.  The caller
+// supplies write_keys(keys) -- ascending key = order of the rows, low ten bits 1023 - length --, sort_rows(keys, keys2,
+// rows_active, now) -- the list sorted into rows_active (active numbering; it belongs to `tmp`), the sorted keys in keys2,
+// scratch in `now`, which ends behind the read-back of sell_nnz -- and launch_fill(rows_active).  One host round trip.
+template <typename Keys, typename Sort, typename Fill>
+static int sell_over_stored_rows(phx_system *s, int64_t ns, DevTemps &tmp, Keys write_keys, Sort sort_rows,
+                                 Fill launch_fill) {
+  hipStream_t st = s->mesh->stream;
+  const dim3 block(256);
+  s->nslices = phx_div_up(ns, SELL_S);
+  const int64_t nrows = s->nslices * SELL_S;
+  PHX_HIP(phx_malloc(&s->slice_ptr, sizeof(int64_t) * (size_t)(s->nslices + 1)));
+  PHX_HIP(phx_malloc(&s->sell_rows, sizeof(int32_t) * (size_t)std::max<int64_t>(nrows, 1)));
+  int32_t *rows_active = nullptr;
+  PHX_HIP(tmp.alloc(&rows_active, sizeof(int32_t) * (size_t)std::max<int64_t>(nrows, 1)));
+  if (ns > 0) {
+    DevTemps now(st);   // back before the SELL arrays are allocated
+    uint32_t *keys = nullptr, *keys2 = nullptr;
+    PHX_HIP(now.alloc(&keys, sizeof(uint32_t) * (size_t)ns));
+    PHX_HIP(now.alloc(&keys2, sizeof(uint32_t) * (size_t)ns));
+    write_keys(keys);
+    k_fill_i32<<<dim3((unsigned)phx_div_up(nrows, 256)), block, 0, st>>>(nrows, rows_active, -1, 0);
+    PHX_CHECK(sort_rows(keys, keys2, rows_active, now));
+    PHX_HIP(hipMemcpyAsync(s->sell_rows, rows_active, sizeof(int32_t) * (size_t)nrows, hipMemcpyDeviceToDevice, st));
+    k_map_i32<<<dim3((unsigned)phx_div_up(nrows, 256)), block, 0, st>>>(nrows, s->iperm, s->sell_rows);
+    PHX_CHECK(slice_offsets(st, now, s->nslices, [&](int64_t *widths) {
+      k_slice_widths16<<<dim3((unsigned)phx_div_up(s->nslices + 1, 256)), block, 0, st>>>(s->nslices, ns, keys2, widths);
+    }, s->slice_ptr, &s->sell_nnz));
+  } else {
+    PHX_HIP(hipMemsetAsync(s->slice_ptr, 0, sizeof(int64_t), st));
+    s->sell_nnz = 0;
+  }
+  const size_t ne = (size_t)std::max<int64_t>(s->sell_nnz, 1), nk = (size_t)std::max<int64_t>(s->nslices, 1);
+  PHX_HIP(phx_malloc(&s->sell_col, sizeof(int32_t) * ne));
+  PHX_HIP(phx_malloc(&s->sell_val, sizeof(double) * ne));
+  PHX_HIP(phx_malloc(&s->sell_val_raw, sizeof(double) * ne));
+  PHX_HIP(phx_malloc(&s->sell_kind, nk * 2));
+  s->sell_kind_raw = s->sell_kind + nk;
+  PHX_HIP(hipMemsetAsync(s->sell_kind, 0, nk * 2, st));
+  s->sell_stream_bytes = 0;
+  if (ns > 0) {
+    PHX_CHECK(launch_fill(rows_active));
+    if (ns < nrows)
+      k_sell_pad_tail<<<1, 64, 0, st>>>(ns, s->nslices, s->slice_ptr, s->sell_col, s->sell_val, s->sell_val_raw);
+    PHX_HIP(hipGetLastError());
+    // the stored rows (near Gamma_h) hold few repeated values: no dictionary coding here
+    s->sell_stream_bytes = 12 * s->sell_nnz + 8 * s->nslices + 4 * nrows;
+  }
   return PHX_OK;
 }
 
@@ -817,156 +906,96 @@ int phx_system_build_structured(phx_system *s, const phx_slot_view &sv, int32_t 
   const dim3 block(256), gn((unsigned)phx_div_up(n, 256)), gu((unsigned)phx_div_up(std::max<int64_t>(nu, 1), 256));
   const int64_t n0 = m->box_n[0] + 1, n01 = n0 * (m->box_n[1] + 1);
   const int has_z = m->gdim == 3 ? 1 : 0;
-  // ---- solver order: C0 rows (lattice order), other u rows, p rows
-  int32_t *rank = nullptr, nc0all = 0;
-  uint8_t *c0i = nullptr;   // [n] rows the stencil applies: C0 rows whose axis neighbours are C0 rows too
-  PHX_HIP(phx_malloc(&rank, sizeof(int32_t) * (size_t)std::max<int64_t>(nu, 1)));
-  PHX_HIP(phx_malloc(&c0i, (size_t)n));
-  PHX_HIP(hipMemsetAsync(c0i, 0, (size_t)n, st));
-  if (nu > 0) {
-    PHX_CHECK(scan_u8(st, s->c0, rank, nu, &nc0all));
-    k_c0_interior<<<gu, block, 0, st>>>(nu, s->c0, s->full_of_active, s->dof_of_vertex_u, n0, n01, has_z, c0i);
-  }
-  PHX_HIP(phx_malloc(&s->perm, sizeof(int32_t) * (size_t)n));
-  PHX_HIP(phx_malloc(&s->iperm, sizeof(int32_t) * (size_t)n));
-  k_build_perm<<<gn, block, 0, st>>>(n, nu, s->c0, rank, nc0all, s->perm, s->iperm);
-  // ---- stored rows (everything the stencil does not apply): kept entries, diagonal
-  int32_t *list = nullptr;
-  int64_t ns = 0;
-  std::vector<void *> later;   // temporaries whose last kernel is only enqueued: freed behind the last synchronisation
-  PHX_CHECK(phx_select_indices(st, n, SelStored{c0i}, &list, &ns, &later));   // one host round trip (the count)
-  later.push_back(rank);
-  int32_t *len = nullptr, *nstruct = nullptr;
-  unsigned long long *dtot = nullptr, htot[2] = {0, 0};
-  PHX_HIP(phx_malloc(&len, sizeof(int32_t) * (size_t)std::max<int64_t>(ns, 1)));
-  PHX_HIP(phx_malloc(&nstruct, sizeof(int32_t) * (size_t)std::max<int64_t>(ns, 1)));
-  PHX_HIP(phx_malloc(&dtot, sizeof(htot)));
-  PHX_HIP(hipMemsetAsync(dtot, 0, sizeof(htot), st));
-  if (ns > 0) {
-    PHX_REQUIRE_GRID(ns * 64, "stored-row scan");
-    if (sv.occ)
-      k_slot_row_meta_box<<<dim3((unsigned)phx_div_up(ns * 64, 256)), block, 0, st>>>(
-          ns, list, sv, s->c0, nu, m->gdim, len, nstruct, s->diag);
-    else
-      k_slot_row_meta<<<dim3((unsigned)phx_div_up(ns * 64, 256)), block, 0, st>>>(
-          ns, list, sv, s->c0, nent, s->dof_of_vertex_u, s->dof_of_vertex_p, m->gdim, len, nstruct, s->diag);
-    k_sum2_i32<<<dim3((unsigned)std::min<int64_t>(phx_div_up(ns, 256), 512)), block, 0, st>>>(ns, nstruct, len, dtot);
-  }
-  PHX_HIP(hipMemcpyAsync(htot, dtot, sizeof(htot), hipMemcpyDeviceToHost, st));
-  PHX_HIP(hipStreamSynchronize(st));
-  PHX_HIP(phx_free(dtot)); PHX_HIP(phx_free(nstruct));
-  s->n_sell_rows = ns;
-  s->nc0 = n - ns;
-  const int per_c0 = m->gdim == 3 ? 7 : 5, struct_c0 = m->gdim == 3 ? 15 : 7;
-  if (!s->rowptr) s->nnz = (int64_t)htot[0] + (int64_t)struct_c0 * s->nc0;     // structural entries (dolfinx pattern)
-  s->sell_true_nnz = (int64_t)htot[1] + (int64_t)per_c0 * s->nc0;              // non-zeros one SpMV applies
-  PHX_HIP(phx_malloc(&s->cscale, sizeof(double) * (size_t)n));
-  k_cscale<<<gn, block, 0, st>>>(n, nu, s->perm, s->diag, s->cscale);
-  // ---- SELL over the stored rows, longest first (stable: equal lengths keep their lattice order)
-  s->nslices = phx_div_up(ns, SELL_S);   // slices of 16 rows, four lanes per row (k_spmv_sell)
-  PHX_HIP(phx_malloc(&s->slice_ptr, sizeof(int64_t) * (size_t)(s->nslices + 1)));
-  PHX_HIP(phx_malloc(&s->sell_rows, sizeof(int32_t) * (size_t)std::max<int64_t>(s->nslices * SELL_S, 1)));
-  int32_t *rows_active = nullptr;   // the same list in active numbering (the slots are indexed by it)
-  PHX_HIP(phx_malloc(&rows_active, sizeof(int32_t) * (size_t)std::max<int64_t>(s->nslices * SELL_S, 1)));
-  if (ns > 0) {
-    uint32_t *keys = nullptr, *keys2 = nullptr;
-    PHX_HIP(phx_malloc(&keys, sizeof(uint32_t) * (size_t)ns));
-    PHX_HIP(phx_malloc(&keys2, sizeof(uint32_t) * (size_t)ns));
-    const dim3 gs((unsigned)phx_div_up(ns, 256));
-    k_stored_keys<<<gs, block, 0, st>>>(ns, len, keys);
-    k_fill_i32<<<dim3((unsigned)phx_div_up(s->nslices * SELL_S, 256)), block, 0, st>>>(s->nslices * SELL_S, rows_active, -1, 0);
-    // keys = 1023 - row length, and a row holds at most slot-capacity entries
-    const int wmax = std::min(std::max(sv.W, 1), 1023);
-    PHX_CHECK(phx_counting_sort_pairs(st, keys, keys2, list, rows_active, ns, (uint32_t)(1023 - wmax), wmax + 1, &later));
-    PHX_HIP(hipMemcpyAsync(s->sell_rows, rows_active, sizeof(int32_t) * (size_t)(s->nslices * SELL_S), hipMemcpyDeviceToDevice, st));
-    k_map_i32<<<dim3((unsigned)phx_div_up(s->nslices * SELL_S, 256)), block, 0, st>>>(s->nslices * SELL_S, s->iperm, s->sell_rows);
-    int64_t *widths = nullptr;
-    PHX_HIP(phx_malloc(&widths, sizeof(int64_t) * (size_t)(s->nslices + 1)));
-    k_slice_widths16<<<dim3((unsigned)phx_div_up(s->nslices + 1, 256)), block, 0, st>>>(s->nslices, ns, keys2, widths);
-    size_t b2 = 0;
-    PHX_HIP(phx_exclusive_sum(nullptr, b2, widths, s->slice_ptr, (size_t)(s->nslices + 1), st));
-    void *t2 = nullptr;
-    PHX_HIP(phx_malloc(&t2, b2 ? b2 : 16));
-    PHX_HIP(phx_exclusive_sum(t2, b2, widths, s->slice_ptr, (size_t)(s->nslices + 1), st));
-    PHX_HIP(hipMemcpyAsync(&s->sell_nnz, s->slice_ptr + s->nslices, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    PHX_HIP(hipStreamSynchronize(st));
-    PHX_HIP(phx_free(t2)); PHX_HIP(phx_free(widths)); PHX_HIP(phx_free(keys)); PHX_HIP(phx_free(keys2));
-  } else {
-    PHX_HIP(hipMemsetAsync(s->slice_ptr, 0, sizeof(int64_t), st));
-    s->sell_nnz = 0;
-  }
-  const size_t ne = (size_t)std::max<int64_t>(s->sell_nnz, 1);
-  PHX_HIP(phx_malloc(&s->sell_col, sizeof(int32_t) * ne));
-  PHX_HIP(phx_malloc(&s->sell_val, sizeof(double) * ne));
-  PHX_HIP(phx_malloc(&s->sell_val_raw, sizeof(double) * ne));
-  PHX_HIP(phx_malloc(&s->sell_kind, (size_t)std::max<int64_t>(s->nslices, 1) * 2));
-  s->sell_kind_raw = s->sell_kind + std::max<int64_t>(s->nslices, 1);
-  PHX_HIP(hipMemsetAsync(s->sell_kind, 0, (size_t)std::max<int64_t>(s->nslices, 1) * 2, st));
-  s->sell_stream_bytes = 0;
-  if (ns > 0) {
-    const dim3 gf((unsigned)phx_div_up(ns * 64, 256));
-    if (sv.occ)
-      k_sell_fill_slots_box<<<gf, block, 0, st>>>(ns, rows_active, sv, s->c0, nent, s->dof_of_vertex_u, s->dof_of_vertex_p,
-                                                  nu, m->gdim, s->stencil, s->diag, s->iperm, s->slice_ptr, s->sell_col,
-                                                  s->sell_val, s->sell_val_raw, s->full_of_active, n0, n01);
-    else
-      k_sell_fill_slots<<<gf, block, 0, st>>>(ns, rows_active, sv, s->c0, nent, s->dof_of_vertex_u, s->dof_of_vertex_p, nu,
-                                              m->gdim, s->stencil, s->diag, s->iperm, s->slice_ptr, s->sell_col, s->sell_val,
-                                              s->sell_val_raw, s->full_of_active, n0, n01);
-    if (ns < s->nslices * SELL_S)
-      k_sell_pad_tail<<<1, 64, 0, st>>>(ns, s->nslices, s->slice_ptr, s->sell_col, s->sell_val, s->sell_val_raw);
-    PHX_HIP(hipGetLastError());
-    // the stored rows (near Gamma_h) hold few repeated values: no dictionary coding here
-    s->sell_stream_bytes = 12 * s->sell_nnz + 8 * s->nslices + 4 * s->nslices * SELL_S;
-  }
-  later.push_back(len); later.push_back(list); later.push_back(rows_active);
-  // ---- stencil runs over the positions of the C0 rows
-  s->nseg = 0;
-  s->nstencil_pos = nc0all;
-  if (s->nc0 > 0 && nc0all > 0) {
-    const int64_t nq = nc0all;
-    uint8_t *fs = nullptr, *fe = nullptr;
-    int32_t *is = nullptr, *ie = nullptr;
-    PHX_HIP(phx_malloc(&fs, (size_t)nq)); PHX_HIP(phx_malloc(&fe, (size_t)nq));
-    PHX_HIP(phx_malloc(&is, sizeof(int32_t) * (size_t)nq)); PHX_HIP(phx_malloc(&ie, sizeof(int32_t) * (size_t)nq));
-    const dim3 gq((unsigned)phx_div_up(nq, 256));
-    k_seg_flags<<<gq, block, 0, st>>>(nq, s->perm, c0i, s->full_of_active, fs, fe);
-    int32_t nstart = 0, nend = 0;
-    PHX_CHECK(scan_u8_pair(st, fs, is, &nstart, fe, ie, &nend, nq));   // one host round trip for both totals
-    PHX_REQUIRE(nstart == nend, PHX_ERR_HIP, "stencil runs: %d starts, %d ends", nstart, nend);
-    s->nseg = nstart;
-    PHX_HIP(phx_malloc(&s->seg, sizeof(int32_t) * 6 * (size_t)std::max(nstart, 1)));
-    k_seg_fill<<<gq, block, 0, st>>>(nq, s->perm, s->iperm, fs, fe, is, ie, s->full_of_active, s->dof_of_vertex_u,
-                                     n0, n01, has_z, s->seg);
-    const int64_t nw = phx_div_up(nq, 64);
-    PHX_HIP(phx_malloc(&s->slice_seg, sizeof(int32_t) * 16 * (size_t)nw));
-    k_slice_seg<<<dim3((unsigned)phx_div_up(nw, 256)), block, 0, st>>>(nw, s->nseg, s->seg, s->slice_seg);
-    PHX_HIP(hipGetLastError());
-    later.push_back(fs); later.push_back(fe); later.push_back(is); later.push_back(ie);
-    // planes too large for the L2 window of a contiguous walk: per-plane eighths (see k_stmap_build)
-    const int nzp = has_z ? (int)(m->box_n[2] + 1) : 0;
-    if (has_z && m->stencil_plane_rows > 0 && nq / nzp >= m->stencil_plane_rows) {
-      int32_t *zstart = nullptr;
-      PHX_HIP(phx_malloc(&zstart, sizeof(int32_t) * (size_t)(nzp + 1)));
-      k_plane_starts<<<gq, block, 0, st>>>(nq, s->perm, s->full_of_active, n01, nzp, zstart);
-      s->st_chunk = nw / 128 + 2 * (int64_t)nzp + 2;
-      PHX_HIP(phx_malloc(&s->st_map, sizeof(int32_t) * 2 * 8 * (size_t)s->st_chunk));
-      k_stmap_build<<<8, 1024, 0, st>>>(nzp, nq, zstart, s->st_chunk, s->st_map);
-      PHX_HIP(hipGetLastError());
-      later.push_back(zstart);
-      s->sell_stream_bytes += 8 * 8 * s->st_chunk;
+  {
+    DevTemps late(st);   // temporaries whose last kernel is only enqueued: freed behind the last synchronisation
+    // ---- solver order: C0 rows (lattice order), other u rows, p rows
+    int32_t *rank = nullptr, nc0all = 0;
+    uint8_t *c0i = nullptr;   // [n] rows the stencil applies: C0 rows whose axis neighbours are C0 rows too
+    PHX_HIP(late.alloc(&rank, sizeof(int32_t) * (size_t)std::max<int64_t>(nu, 1)));
+    PHX_HIP(late.alloc(&c0i, (size_t)n));
+    PHX_HIP(hipMemsetAsync(c0i, 0, (size_t)n, st));
+    if (nu > 0) {
+      PHX_CHECK(scan_u8(st, s->c0, rank, nu, &nc0all, late));
+      k_c0_interior<<<gu, block, 0, st>>>(nu, s->c0, s->full_of_active, s->dof_of_vertex_u, n0, n01, has_z, c0i);
     }
-    s->sell_stream_bytes += 24 * (int64_t)s->nseg + 64 * nw;
+    PHX_HIP(phx_malloc(&s->perm, sizeof(int32_t) * (size_t)n));
+    PHX_HIP(phx_malloc(&s->iperm, sizeof(int32_t) * (size_t)n));
+    k_build_perm<<<gn, block, 0, st>>>(n, nu, s->c0, rank, nc0all, s->perm, s->iperm);
+    // ---- stored rows (everything the stencil does not apply): kept entries, diagonal
+    int32_t *list = nullptr, *len = nullptr;
+    int64_t ns = 0;
+    unsigned long long htot[2] = {0, 0};
+    PHX_CHECK(phx_select_indices(st, n, SelStored{c0i}, &list, &ns, &late.blocks));   // one host round trip (the count)
+    late.adopt(list);
+    PHX_CHECK(stored_row_meta(s, sv, nent, s->c0, ns, list, late, &len, htot));
+    s->n_sell_rows = ns;
+    s->nc0 = n - ns;
+    const int per_c0 = m->gdim == 3 ? 7 : 5, struct_c0 = m->gdim == 3 ? 15 : 7;
+    if (!s->rowptr) s->nnz = (int64_t)htot[0] + (int64_t)struct_c0 * s->nc0;     // structural entries (dolfinx pattern)
+    s->sell_true_nnz = (int64_t)htot[1] + (int64_t)per_c0 * s->nc0;              // non-zeros one SpMV applies
+    PHX_HIP(phx_malloc(&s->cscale, sizeof(double) * (size_t)n));
+    k_cscale<<<gn, block, 0, st>>>(n, nu, s->perm, s->diag, s->cscale);
+    // ---- SELL over the stored rows, longest first (stable: equal lengths keep their lattice order)
+    PHX_CHECK(sell_over_stored_rows(
+        s, ns, late,
+        [&](uint32_t *keys) { k_stored_keys<<<dim3((unsigned)phx_div_up(ns, 256)), block, 0, st>>>(ns, len, keys); },
+        [&](const uint32_t *keys, uint32_t *keys2, int32_t *rows_active, DevTemps &) {
+          // keys = 1023 - row length, and a row holds at most slot-capacity entries; the scratch stays to the end
+          const int wmax = std::min(std::max(sv.W, 1), 1023);
+          return phx_counting_sort_pairs(st, keys, keys2, list, rows_active, ns, (uint32_t)(1023 - wmax), wmax + 1, late);
+        },
+        [&](const int32_t *rows_active) {
+          const dim3 gf((unsigned)phx_div_up(ns * 64, 256));
+          if (sv.occ)
+            k_sell_fill_slots_box<<<gf, block, 0, st>>>(ns, rows_active, sv, s->c0, nent, s->dof_of_vertex_u, s->dof_of_vertex_p,
+                                                        nu, m->gdim, s->stencil, s->diag, s->iperm, s->slice_ptr, s->sell_col,
+                                                        s->sell_val, s->sell_val_raw, s->full_of_active, n0, n01);
+          else
+            k_sell_fill_slots<<<gf, block, 0, st>>>(ns, rows_active, sv, s->c0, nent, s->dof_of_vertex_u, s->dof_of_vertex_p, nu,
+                                                    m->gdim, s->stencil, s->diag, s->iperm, s->slice_ptr, s->sell_col, s->sell_val,
+                                                    s->sell_val_raw, s->full_of_active, n0, n01);
+          return PHX_OK;
+        }));
+    // ---- stencil runs over the positions of the C0 rows
+    s->nseg = 0;
+    s->nstencil_pos = nc0all;
+    if (s->nc0 > 0 && nc0all > 0) {
+      const int64_t nq = nc0all;
+      uint8_t *fs = nullptr, *fe = nullptr;
+      int32_t *is = nullptr, *ie = nullptr;
+      PHX_HIP(late.alloc(&fs, (size_t)nq)); PHX_HIP(late.alloc(&fe, (size_t)nq));
+      PHX_HIP(late.alloc(&is, sizeof(int32_t) * (size_t)nq)); PHX_HIP(late.alloc(&ie, sizeof(int32_t) * (size_t)nq));
+      const dim3 gq((unsigned)phx_div_up(nq, 256));
+      k_seg_flags<<<gq, block, 0, st>>>(nq, s->perm, c0i, s->full_of_active, fs, fe);
+      int32_t nstart = 0, nend = 0;
+      PHX_CHECK(scan_u8_pair(st, fs, is, &nstart, fe, ie, &nend, nq, late));   // one host round trip for both totals
+      PHX_REQUIRE(nstart == nend, PHX_ERR_HIP, "stencil runs: %d starts, %d ends", nstart, nend);
+      s->nseg = nstart;
+      PHX_HIP(phx_malloc(&s->seg, sizeof(int32_t) * 6 * (size_t)std::max(nstart, 1)));
+      k_seg_fill<<<gq, block, 0, st>>>(nq, s->perm, s->iperm, fs, fe, is, ie, s->full_of_active, s->dof_of_vertex_u,
+                                       n0, n01, has_z, s->seg);
+      const int64_t nw = phx_div_up(nq, 64);
+      PHX_HIP(phx_malloc(&s->slice_seg, sizeof(int32_t) * 16 * (size_t)nw));
+      k_slice_seg<<<dim3((unsigned)phx_div_up(nw, 256)), block, 0, st>>>(nw, s->nseg, s->seg, s->slice_seg);
+      PHX_HIP(hipGetLastError());
+      // planes too large for the L2 window of a contiguous walk: per-plane eighths (see k_stmap_build)
+      const int nzp = has_z ? (int)(m->box_n[2] + 1) : 0;
+      if (has_z && m->stencil_plane_rows > 0 && nq / nzp >= m->stencil_plane_rows) {
+        int32_t *zstart = nullptr;
+        PHX_HIP(late.alloc(&zstart, sizeof(int32_t) * (size_t)(nzp + 1)));
+        k_plane_starts<<<gq, block, 0, st>>>(nq, s->perm, s->full_of_active, n01, nzp, zstart);
+        s->st_chunk = nw / 128 + 2 * (int64_t)nzp + 2;
+        PHX_HIP(phx_malloc(&s->st_map, sizeof(int32_t) * 2 * 8 * (size_t)s->st_chunk));
+        k_stmap_build<<<8, 1024, 0, st>>>(nzp, nq, zstart, s->st_chunk, s->st_map);
+        PHX_HIP(hipGetLastError());
+        s->sell_stream_bytes += 8 * 8 * s->st_chunk;
+      }
+      s->sell_stream_bytes += 24 * (int64_t)s->nseg + 64 * nw;
+    }
+    PHX_HIP(hipGetLastError());
+    PHX_HIP(hipStreamSynchronize(st));
   }
-  PHX_HIP(hipGetLastError());
-  PHX_HIP(hipStreamSynchronize(st));
-  for (void *q : later) PHX_HIP(phx_free(q));
-  PHX_HIP(phx_free(c0i));
-  // solver workspace: 9 vectors + scalars
-  PHX_HIP(phx_malloc(&s->work, sizeof(double) * (size_t)n * 9));
-  PHX_HIP(phx_malloc(&s->scal, sizeof(double) * PHX_SCAL_DOUBLES));
-  PHX_CHECK(phx_mesh_pinned_scalars(s->mesh, &s->scal_h));
-  return PHX_OK;
+  return system_workspace(s);
 }
 
 extern "C" int phx_system_export_sell(phx_system *s, int64_t *slice_ptr, int32_t *col, double *val, int32_t *rows) {
@@ -984,10 +1013,8 @@ extern "C" int phx_system_export_sell(phx_system *s, int64_t *slice_ptr, int32_t
 // every collective of a multi-GPU solve with zero contributions.
 int phx_system_build_empty(phx_system *s) {
   s->n = 0; s->nu = 0; s->nnz = 0; s->nslices = 0; s->sell_nnz = 0; s->sell_true_nnz = 0;
-  PHX_HIP(phx_malloc(&s->work, sizeof(double) * 16));
-  PHX_HIP(phx_malloc(&s->scal, sizeof(double) * PHX_SCAL_DOUBLES));
+  PHX_CHECK(system_workspace(s));
   PHX_HIP(hipMemsetAsync(s->scal, 0, sizeof(double) * PHX_SCAL_DOUBLES, s->mesh->stream));
-  PHX_CHECK(phx_mesh_pinned_scalars(s->mesh, &s->scal_h));
   PHX_HIP(hipStreamSynchronize(s->mesh->stream));
   return PHX_OK;
 }

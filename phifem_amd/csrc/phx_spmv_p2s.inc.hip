@@ -136,6 +136,34 @@ __global__ void k_p2s_stored_keys(int64_t ns, const int32_t *__restrict__ list, 
   keys[i] = key | (uint32_t)(((q[2] / tile) * t1 + q[1] / tile) * t0 + q[0] / tile) << 10;
 }
 
+// solver order of a structured P2 system (C0 rows in lattice order, the other u rows, the p rows), latpos [NF] = rank of
+// a fine point among the C0 points, and the list of the stored rows.  Synchronises (the selection).
+static int p2s_order_rows(phx_system *s, const uint8_t *latc0, int32_t *latpos, int32_t *nc0all, int32_t **list,
+                          int64_t *ns) {
+  hipStream_t st = s->mesh->stream;
+  const phx_p2_lattice &L = s->p2s->lat;
+  const int64_t n = s->n, nu = s->nu, NF = L.F[0] * L.F[1] * L.F[2];
+  const dim3 block(256), gn((unsigned)phx_div_up(n, 256)), gu((unsigned)phx_div_up(std::max<int64_t>(nu, 1), 256));
+  DevTemps tmp(st);
+  int32_t *rank_not = nullptr, nnot = 0;
+  uint8_t *notc0 = nullptr;
+  PHX_CHECK(scan_u8(st, latc0, latpos, NF, nc0all, tmp));
+  PHX_HIP(tmp.alloc(&rank_not, sizeof(int32_t) * (size_t)std::max<int64_t>(nu, 1)));
+  PHX_HIP(tmp.alloc(&notc0, (size_t)std::max<int64_t>(nu, 1)));
+  if (nu > 0) {
+    k_p2s_not_c0<<<gu, block, 0, st>>>(nu, L, s->full_of_active, latc0, notc0);
+    PHX_CHECK(scan_u8(st, notc0, rank_not, nu, &nnot, tmp));
+  }
+  PHX_REQUIRE((int64_t)*nc0all + nnot == nu, PHX_ERR_HIP, "structured P2: %d C0 rows + %d others != %lld u rows",
+              *nc0all, nnot, (long long)nu);
+  PHX_HIP(phx_malloc(&s->perm, sizeof(int32_t) * (size_t)n));
+  PHX_HIP(phx_malloc(&s->iperm, sizeof(int32_t) * (size_t)n));
+  k_p2s_perm<<<gn, block, 0, st>>>(n, nu, L, s->full_of_active, latc0, latpos, rank_not, *nc0all, s->perm, s->iperm);
+  PHX_HIP(hipGetLastError());
+  // stored rows: everything the stencils do not apply
+  return phx_select_indices(st, n, SelStored{s->c0}, list, ns);
+}
+
 int phx_system_build_structured_p2(phx_system *s, const phx_slot_view &sv, int32_t nent, const uint8_t *latc0,
                                    const uint8_t *latc0i) {
   phx_mesh *m = s->mesh;
@@ -143,152 +171,93 @@ int phx_system_build_structured_p2(phx_system *s, const phx_slot_view &sv, int32
   phx_p2_struct *ps = s->p2s;
   const phx_p2_lattice &L = ps->lat;
   const int64_t n = s->n, nu = s->nu, NF = L.F[0] * L.F[1] * L.F[2];
-  const dim3 block(256), gn((unsigned)phx_div_up(n, 256)), gu((unsigned)phx_div_up(std::max<int64_t>(nu, 1), 256)),
-      gfine((unsigned)phx_div_up(NF, 256));
-  // ---- solver order
-  int32_t *latpos = nullptr, *rank_not = nullptr, nc0all = 0, nnot = 0;
-  uint8_t *notc0 = nullptr;
-  PHX_HIP(phx_malloc(&latpos, sizeof(int32_t) * (size_t)NF));
-  PHX_CHECK(scan_u8(st, latc0, latpos, NF, &nc0all));
-  PHX_HIP(phx_malloc(&rank_not, sizeof(int32_t) * (size_t)std::max<int64_t>(nu, 1)));
-  PHX_HIP(phx_malloc(&notc0, (size_t)std::max<int64_t>(nu, 1)));
-  if (nu > 0) {
-    k_p2s_not_c0<<<gu, block, 0, st>>>(nu, L, s->full_of_active, latc0, notc0);
-    PHX_CHECK(scan_u8(st, notc0, rank_not, nu, &nnot));
-  }
-  PHX_REQUIRE((int64_t)nc0all + nnot == nu, PHX_ERR_HIP, "structured P2: %d C0 rows + %d others != %lld u rows",
-              nc0all, nnot, (long long)nu);
-  PHX_HIP(phx_malloc(&s->perm, sizeof(int32_t) * (size_t)n));
-  PHX_HIP(phx_malloc(&s->iperm, sizeof(int32_t) * (size_t)n));
-  k_p2s_perm<<<gn, block, 0, st>>>(n, nu, L, s->full_of_active, latc0, latpos, rank_not, nc0all, s->perm, s->iperm);
-  PHX_HIP(hipGetLastError());
-  // ---- stored rows (everything the stencils do not apply): kept entries, diagonal
-  int32_t *list = nullptr;
-  int64_t ns = 0;
-  PHX_CHECK(phx_select_indices(st, n, SelStored{s->c0}, &list, &ns));   // synchronises
-  PHX_HIP(phx_free(rank_not)); PHX_HIP(phx_free(notc0));
-  int32_t *len = nullptr, *nstruct = nullptr;
-  unsigned long long *dtot = nullptr, htot[2] = {0, 0};
-  PHX_HIP(phx_malloc(&len, sizeof(int32_t) * (size_t)std::max<int64_t>(ns, 1)));
-  PHX_HIP(phx_malloc(&nstruct, sizeof(int32_t) * (size_t)std::max<int64_t>(ns, 1)));
-  PHX_HIP(phx_malloc(&dtot, sizeof(htot)));
-  PHX_HIP(hipMemsetAsync(dtot, 0, sizeof(htot), st));
-  if (ns > 0) {
-    PHX_REQUIRE_GRID(ns * 64, "stored-row scan");
-    k_slot_row_meta<<<dim3((unsigned)phx_div_up(ns * 64, 256)), block, 0, st>>>(
-        ns, list, sv, nullptr, nent, s->dof_of_vertex_u, s->dof_of_vertex_p, m->gdim, len, nstruct, s->diag);
-    k_sum2_i32<<<dim3((unsigned)std::min<int64_t>(phx_div_up(ns, 256), 512)), block, 0, st>>>(ns, nstruct, len, dtot);
-  }
-  PHX_HIP(hipMemcpyAsync(htot, dtot, sizeof(htot), hipMemcpyDeviceToHost, st));
-  PHX_HIP(hipStreamSynchronize(st));
-  PHX_HIP(phx_free(dtot)); PHX_HIP(phx_free(nstruct));
-  s->n_sell_rows = ns;
-  s->nc0 = n - ns;
-  ps->nc0i = n - ns;
-  // entries of the stencil rows: counted from the tables (structural = applied: the tables hold no explicit zeros)
+  const dim3 block(256), gn((unsigned)phx_div_up(n, 256)), gfine((unsigned)phx_div_up(NF, 256));
   {
-    int cnt[8];
-    std::vector<double> K(1000);
-    PHX_HIP(hipMemcpy(K.data(), ps->coef, sizeof(double) * 1000, hipMemcpyDeviceToHost));
-    double avg = 0.0;
-    for (int c = 0; c < 8; ++c) { cnt[c] = 0; for (int o = 0; o < 125; ++o) cnt[c] += K[(size_t)c * 125 + o] != 0.0; avg += cnt[c] / 8.0; }
-    // the eight classes are equally frequent among interior fine points
-    s->nnz = (int64_t)htot[0] + (int64_t)(avg * (double)s->nc0);
-    s->sell_true_nnz = (int64_t)htot[1] + (int64_t)(avg * (double)s->nc0);
-  }
-  PHX_HIP(phx_malloc(&s->cscale, sizeof(double) * (size_t)n));
-  k_cscale<<<gn, block, 0, st>>>(n, nu, s->perm, s->diag, s->cscale);
-  // ---- SELL over the stored rows, longest first
-  s->nslices = phx_div_up(ns, SELL_S);
-  PHX_HIP(phx_malloc(&s->slice_ptr, sizeof(int64_t) * (size_t)(s->nslices + 1)));
-  PHX_HIP(phx_malloc(&s->sell_rows, sizeof(int32_t) * (size_t)std::max<int64_t>(s->nslices * SELL_S, 1)));
-  int32_t *rows_active = nullptr;
-  PHX_HIP(phx_malloc(&rows_active, sizeof(int32_t) * (size_t)std::max<int64_t>(s->nslices * SELL_S, 1)));
-  if (ns > 0) {
-    uint32_t *keys = nullptr, *keys2 = nullptr;
-    PHX_HIP(phx_malloc(&keys, sizeof(uint32_t) * (size_t)ns));
-    PHX_HIP(phx_malloc(&keys2, sizeof(uint32_t) * (size_t)ns));
-    const dim3 gs((unsigned)phx_div_up(ns, 256));
-    int tile = P2S_TILE, tn[3], key_bits = 10;
-    for (int a = 0; a < 3; ++a) tn[a] = (int)(L.F[a] / tile + 1);
-    while ((int64_t)tn[0] * tn[1] * tn[2] > (1ll << 22)) {   // 22 + 10 key bits
-      tile *= 2;
-      for (int a = 0; a < 3; ++a) tn[a] = (int)(L.F[a] / tile + 1);
+    DevTemps whole(st);   // latpos: read until the run records are written
+    int32_t *latpos = nullptr, nc0all = 0;
+    PHX_HIP(whole.alloc(&latpos, sizeof(int32_t) * (size_t)NF));
+    {
+      DevTemps rows(st);   // list, len, rows_active: back behind the fill, before the run records are made
+      int32_t *list = nullptr, *len = nullptr;
+      int64_t ns = 0;
+      PHX_CHECK(p2s_order_rows(s, latc0, latpos, &nc0all, &list, &ns));
+      rows.adopt(list);
+      // ---- stored rows: kept entries, diagonal
+      unsigned long long htot[2] = {0, 0};
+      PHX_CHECK(stored_row_meta(s, sv, nent, nullptr, ns, list, rows, &len, htot));
+      s->n_sell_rows = ns;
+      s->nc0 = n - ns;
+      ps->nc0i = n - ns;
+      // entries of the stencil rows: counted from the tables (structural = applied: the tables hold no explicit zeros)
+      {
+        int cnt[8];
+        std::vector<double> K(1000);
+        PHX_HIP(hipMemcpy(K.data(), ps->coef, sizeof(double) * 1000, hipMemcpyDeviceToHost));
+        double avg = 0.0;
+        for (int c = 0; c < 8; ++c) { cnt[c] = 0; for (int o = 0; o < 125; ++o) cnt[c] += K[(size_t)c * 125 + o] != 0.0; avg += cnt[c] / 8.0; }
+        // the eight classes are equally frequent among interior fine points
+        s->nnz = (int64_t)htot[0] + (int64_t)(avg * (double)s->nc0);
+        s->sell_true_nnz = (int64_t)htot[1] + (int64_t)(avg * (double)s->nc0);
+      }
+      PHX_HIP(phx_malloc(&s->cscale, sizeof(double) * (size_t)n));
+      k_cscale<<<gn, block, 0, st>>>(n, nu, s->perm, s->diag, s->cscale);
+      // ---- SELL over the stored rows, longest first inside a tile
+      int key_bits = 10;
+      PHX_CHECK(sell_over_stored_rows(
+          s, ns, rows,
+          [&](uint32_t *keys) {
+            int tile = P2S_TILE, tn[3];
+            for (int a = 0; a < 3; ++a) tn[a] = (int)(L.F[a] / tile + 1);
+            while ((int64_t)tn[0] * tn[1] * tn[2] > (1ll << 22)) {   // 22 + 10 key bits
+              tile *= 2;
+              for (int a = 0; a < 3; ++a) tn[a] = (int)(L.F[a] / tile + 1);
+            }
+            while ((1ll << (key_bits - 10)) < (int64_t)tn[0] * tn[1] * tn[2]) ++key_bits;
+            k_p2s_stored_keys<<<dim3((unsigned)phx_div_up(ns, 256)), block, 0, st>>>(ns, list, len, keys, s->full_of_active,
+                                                                                     (int64_t)nent, L, tile, tn[0], tn[1]);
+          },
+          [&](uint32_t *keys, uint32_t *keys2, int32_t *rows_active, DevTemps &now) {
+            size_t bytes = 0;
+            void *work = nullptr;
+            PHX_HIP(phx_sort_pairs(nullptr, bytes, keys, keys2, list, rows_active, (size_t)ns, 0, key_bits, st));
+            PHX_HIP(now.alloc(&work, bytes));
+            PHX_HIP(phx_sort_pairs(work, bytes, keys, keys2, list, rows_active, (size_t)ns, 0, key_bits, st));
+            return PHX_OK;
+          },
+          [&](const int32_t *rows_active) {
+            const dim3 gf((unsigned)ns);
+            if (sv.W <= 128)
+              k_sell_fill_slots_wide<128><<<gf, dim3(128), 0, st>>>(ns, rows_active, sv, nent, s->dof_of_vertex_u, s->dof_of_vertex_p, nu, s->diag, s->iperm, s->slice_ptr, s->sell_col, s->sell_val, s->sell_val_raw);
+            else if (sv.W == 256)
+              k_sell_fill_slots_wide<256><<<gf, dim3(256), 0, st>>>(ns, rows_active, sv, nent, s->dof_of_vertex_u, s->dof_of_vertex_p, nu, s->diag, s->iperm, s->slice_ptr, s->sell_col, s->sell_val, s->sell_val_raw);
+            else if (sv.W == 512)
+              k_sell_fill_slots_wide<512><<<gf, dim3(512), 0, st>>>(ns, rows_active, sv, nent, s->dof_of_vertex_u, s->dof_of_vertex_p, nu, s->diag, s->iperm, s->slice_ptr, s->sell_col, s->sell_val, s->sell_val_raw);
+            else { phx_set_error("structured P2: unsupported slot capacity %d", sv.W); return PHX_ERR_VALUE; }
+            return PHX_OK;
+          }));
+      PHX_HIP(hipStreamSynchronize(st));
     }
-    while ((1ll << (key_bits - 10)) < (int64_t)tn[0] * tn[1] * tn[2]) ++key_bits;
-    k_p2s_stored_keys<<<gs, block, 0, st>>>(ns, list, len, keys, s->full_of_active, (int64_t)nent, L, tile, tn[0], tn[1]);
-    k_fill_i32<<<dim3((unsigned)phx_div_up(s->nslices * SELL_S, 256)), block, 0, st>>>(s->nslices * SELL_S, rows_active, -1, 0);
-    size_t bytes = 0;
-    PHX_HIP(phx_sort_pairs(nullptr, bytes, keys, keys2, list, rows_active, (size_t)ns, 0, key_bits, st));
-    void *tmp = nullptr;
-    PHX_HIP(phx_malloc(&tmp, bytes ? bytes : 16));
-    PHX_HIP(phx_sort_pairs(tmp, bytes, keys, keys2, list, rows_active, (size_t)ns, 0, key_bits, st));
-    PHX_HIP(hipMemcpyAsync(s->sell_rows, rows_active, sizeof(int32_t) * (size_t)(s->nslices * SELL_S), hipMemcpyDeviceToDevice, st));
-    k_map_i32<<<dim3((unsigned)phx_div_up(s->nslices * SELL_S, 256)), block, 0, st>>>(s->nslices * SELL_S, s->iperm, s->sell_rows);
-    int64_t *widths = nullptr;
-    PHX_HIP(phx_malloc(&widths, sizeof(int64_t) * (size_t)(s->nslices + 1)));
-    k_slice_widths16<<<dim3((unsigned)phx_div_up(s->nslices + 1, 256)), block, 0, st>>>(s->nslices, ns, keys2, widths);
-    size_t b2 = 0;
-    PHX_HIP(phx_exclusive_sum(nullptr, b2, widths, s->slice_ptr, (size_t)(s->nslices + 1), st));
-    void *t2 = nullptr;
-    PHX_HIP(phx_malloc(&t2, b2 ? b2 : 16));
-    PHX_HIP(phx_exclusive_sum(t2, b2, widths, s->slice_ptr, (size_t)(s->nslices + 1), st));
-    PHX_HIP(hipMemcpyAsync(&s->sell_nnz, s->slice_ptr + s->nslices, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    PHX_HIP(hipStreamSynchronize(st));
-    PHX_HIP(phx_free(tmp)); PHX_HIP(phx_free(t2)); PHX_HIP(phx_free(widths)); PHX_HIP(phx_free(keys)); PHX_HIP(phx_free(keys2));
-  } else {
-    PHX_HIP(hipMemsetAsync(s->slice_ptr, 0, sizeof(int64_t), st));
-    s->sell_nnz = 0;
+    // ---- stencil runs
+    s->nseg = 0;
+    s->nstencil_pos = nc0all;
+    ps->nrun = 0;
+    if (s->nc0 > 0) {
+      DevTemps runs(st);
+      uint8_t *fs = nullptr;
+      int32_t *runid = nullptr, nrun = 0;
+      PHX_HIP(runs.alloc(&fs, (size_t)NF));
+      PHX_HIP(runs.alloc(&runid, sizeof(int32_t) * (size_t)NF));
+      k_p2s_run_flags<<<gfine, block, 0, st>>>(NF, L.F[0], latc0i, fs);
+      PHX_CHECK(scan_u8(st, fs, runid, NF, &nrun, runs));
+      ps->nrun = nrun;
+      PHX_HIP(phx_malloc(&ps->runs, sizeof(int32_t) * PHX_P2S_REC * (size_t)std::max(nrun, 1)));
+      k_p2s_run_fill<<<gfine, block, 0, st>>>(NF, L, latc0i, fs, runid, latpos, ps->runs);
+      PHX_HIP(hipGetLastError());
+      PHX_HIP(hipStreamSynchronize(st));
+      s->sell_stream_bytes += 4 * PHX_P2S_REC * (int64_t)nrun;
+    }
   }
-  const size_t ne = (size_t)std::max<int64_t>(s->sell_nnz, 1);
-  PHX_HIP(phx_malloc(&s->sell_col, sizeof(int32_t) * ne));
-  PHX_HIP(phx_malloc(&s->sell_val, sizeof(double) * ne));
-  PHX_HIP(phx_malloc(&s->sell_val_raw, sizeof(double) * ne));
-  PHX_HIP(phx_malloc(&s->sell_kind, (size_t)std::max<int64_t>(s->nslices, 1) * 2));
-  s->sell_kind_raw = s->sell_kind + std::max<int64_t>(s->nslices, 1);
-  PHX_HIP(hipMemsetAsync(s->sell_kind, 0, (size_t)std::max<int64_t>(s->nslices, 1) * 2, st));
-  s->sell_stream_bytes = 0;
-  if (ns > 0) {
-    const dim3 gf((unsigned)ns);
-    if (sv.W <= 128)
-      k_sell_fill_slots_wide<128><<<gf, dim3(128), 0, st>>>(ns, rows_active, sv, nent, s->dof_of_vertex_u, s->dof_of_vertex_p, nu, s->diag, s->iperm, s->slice_ptr, s->sell_col, s->sell_val, s->sell_val_raw);
-    else if (sv.W == 256)
-      k_sell_fill_slots_wide<256><<<gf, dim3(256), 0, st>>>(ns, rows_active, sv, nent, s->dof_of_vertex_u, s->dof_of_vertex_p, nu, s->diag, s->iperm, s->slice_ptr, s->sell_col, s->sell_val, s->sell_val_raw);
-    else if (sv.W == 512)
-      k_sell_fill_slots_wide<512><<<gf, dim3(512), 0, st>>>(ns, rows_active, sv, nent, s->dof_of_vertex_u, s->dof_of_vertex_p, nu, s->diag, s->iperm, s->slice_ptr, s->sell_col, s->sell_val, s->sell_val_raw);
-    else { phx_set_error("structured P2: unsupported slot capacity %d", sv.W); return PHX_ERR_VALUE; }
-    if (ns < s->nslices * SELL_S)
-      k_sell_pad_tail<<<1, 64, 0, st>>>(ns, s->nslices, s->slice_ptr, s->sell_col, s->sell_val, s->sell_val_raw);
-    PHX_HIP(hipGetLastError());
-    s->sell_stream_bytes = 12 * s->sell_nnz + 8 * s->nslices + 4 * s->nslices * SELL_S;
-  }
-  PHX_HIP(hipStreamSynchronize(st));
-  PHX_HIP(phx_free(len)); PHX_HIP(phx_free(list)); PHX_HIP(phx_free(rows_active));
-  // ---- stencil runs
-  s->nseg = 0;
-  s->nstencil_pos = nc0all;
-  ps->nrun = 0;
-  if (s->nc0 > 0) {
-    uint8_t *fs = nullptr;
-    int32_t *runid = nullptr, nrun = 0;
-    PHX_HIP(phx_malloc(&fs, (size_t)NF));
-    PHX_HIP(phx_malloc(&runid, sizeof(int32_t) * (size_t)NF));
-    k_p2s_run_flags<<<gfine, block, 0, st>>>(NF, L.F[0], latc0i, fs);
-    PHX_CHECK(scan_u8(st, fs, runid, NF, &nrun));
-    ps->nrun = nrun;
-    PHX_HIP(phx_malloc(&ps->runs, sizeof(int32_t) * PHX_P2S_REC * (size_t)std::max(nrun, 1)));
-    k_p2s_run_fill<<<gfine, block, 0, st>>>(NF, L, latc0i, fs, runid, latpos, ps->runs);
-    PHX_HIP(hipGetLastError());
-    PHX_HIP(hipStreamSynchronize(st));
-    PHX_HIP(phx_free(fs)); PHX_HIP(phx_free(runid));
-    s->sell_stream_bytes += 4 * PHX_P2S_REC * (int64_t)nrun;
-  }
-  PHX_HIP(phx_free(latpos));
-  // solver workspace: 9 vectors + scalars
-  PHX_HIP(phx_malloc(&s->work, sizeof(double) * (size_t)n * 9));
-  PHX_HIP(phx_malloc(&s->scal, sizeof(double) * PHX_SCAL_DOUBLES));
-  PHX_CHECK(phx_mesh_pinned_scalars(s->mesh, &s->scal_h));
-  return PHX_OK;
+  return system_workspace(s);
 }
 
 // y_r = sum_o coef[class(r)][o] x[r + off(o)] over the runs; DOTS as k_spmv_sell.

@@ -787,16 +787,17 @@ int phx_collect_entities(phx_mesh *m) {
     return PHX_OK;
   }
   int32_t *list = nullptr, *cnt = nullptr, *off = nullptr;
-  std::vector<void *> later;   // freed behind the synchronisation at the end
+  DevTemps tmp(st);   // freed behind the synchronisation at the end
   {
     int64_t nsel = 0;
-    PHX_CHECK(phx_select_indices(st, m->nf, SelTag34{m->facet_tags}, &list, &nsel, &later,
+    PHX_CHECK(phx_select_indices(st, m->nf, SelTag34{m->facet_tags}, &list, &nsel, &tmp.blocks,
                                  m->sel_counts_valid ? m->sel_counts[1] : nullptr,
                                  m->sel_counts_valid ? m->sel_total[1] : -1));
+    tmp.adopt(list);
     PHX_REQUIRE(nsel == nmax, PHX_ERR_VALUE, "facet tag histogram and selection disagree");
   }
-  PHX_HIP(phx_malloc(&cnt, sizeof(int32_t) * 2 * (size_t)(nmax + 1)));
-  PHX_HIP(phx_malloc(&off, sizeof(int32_t) * 2 * (size_t)(nmax + 1)));
+  PHX_HIP(tmp.alloc(&cnt, sizeof(int32_t) * 2 * (size_t)(nmax + 1)));
+  PHX_HIP(tmp.alloc(&off, sizeof(int32_t) * 2 * (size_t)(nmax + 1)));
   PHX_HIP(hipMemsetAsync(cnt, 0, sizeof(int32_t) * 2 * (size_t)(nmax + 1), st));
   int32_t *cnt0 = cnt, *cnt1 = cnt + (nmax + 1), *off0 = off, *off1 = off + (nmax + 1);
   const dim3 grid((unsigned)phx_div_up(nmax, 256)), block(256);
@@ -807,15 +808,14 @@ int phx_collect_entities(phx_mesh *m) {
     int32_t tot[2] = {0, 0};
     size_t bytes = 0;
     PHX_HIP(phx_exclusive_sum(nullptr, bytes, cnt0, off0, (size_t)(nmax + 1), st));
-    void *tmp = nullptr;
-    PHX_HIP(phx_malloc(&tmp, bytes ? bytes : 16));
+    void *work = nullptr;
+    PHX_HIP(tmp.alloc(&work, bytes));
     for (int w = 0; w < 2; ++w) {
       int32_t *ci = w == 0 ? cnt0 : cnt1, *oi = w == 0 ? off0 : off1;
-      PHX_HIP(phx_exclusive_sum(tmp, bytes, ci, oi, (size_t)(nmax + 1), st));
+      PHX_HIP(phx_exclusive_sum(work, bytes, ci, oi, (size_t)(nmax + 1), st));
     }
     const phx_rb_item rb[2] = {{off0 + nmax, 4, &tot[0]}, {off1 + nmax, 4, &tot[1]}};
     PHX_CHECK(phx_read_back(st, rb, 2));
-    PHX_HIP(phx_free(tmp));
     for (int w = 0; w < 2; ++w) {
       m->ent_count[w] = tot[w];
       PHX_HIP(phx_malloc(&m->ent_buf[w], sizeof(int64_t) * 2 * (size_t)(tot[w] > 0 ? tot[w] : 1)));
@@ -826,8 +826,6 @@ int phx_collect_entities(phx_mesh *m) {
                                            m->ent_buf[0], m->ent_buf[1]);
   PHX_HIP(hipGetLastError());
   PHX_HIP(hipStreamSynchronize(st));
-  for (void *q : later) PHX_HIP(phx_free(q));
-  PHX_HIP(phx_free(list)); PHX_HIP(phx_free(cnt)); PHX_HIP(phx_free(off));
   m->have_entities = true;
   return PHX_OK;
 }
