@@ -745,6 +745,27 @@ int phx_estimate_poisson_wd(phx_mesh *m, int degree, const double *u, const doub
                             double *sums3);
 int phx_mark_dorfler(phx_mesh *m, int64_t n, const double *eta2, int loc_in, double theta, uint8_t *marked,
                      int loc_out, int64_t *n_marked);
+/* --- recovered gradient and the recovery-based (Zienkiewicz-Zhu) indicator ---------------------
+ * u: nodal values of `degree`, component-major [ncomp][nv] (degree 1) or [ncomp][nv + ne] (degree 2, vertices then
+ * the edges of PHX_ARR_C2E) at loc_u.  S = the cells whose byte of cell_mask[nc] (at loc_mask) is not 0; cell_mask
+ * NULL: the cells tagged 1 or 2 (tag & 0x7f) on the cell tags the mesh holds.  With S_v the cells of S that contain v
+ *   G(v) = sum_{T in S_v} |T| grad u_h|_T (x_v) / sum_{T in S_v} |T|        (exactly 0 where S_v is empty)
+ * -> grad[ncomp][nv][gdim] at loc_out; |T| the cell volume, grad u_h|_T (x_v) the gradient of T's own polynomial at
+ * its corner v.  eta2 (NULL: not wanted): [nc] at loc_out,
+ *   eta_T^2 = sum over the components of int_T |G_h - grad u_h|^2 for T in S,   exactly 0 for T not in S,
+ * G_h the P1 / Q1 interpolant of G; closed forms, exact for degrees 1 and 2.  sum (NULL: not wanted): the total of
+ * eta2 on the host.  An indicator for marking and a post-processed flux: neither a proven bound nor the residual of
+ * any scheme; at the rim of S the stars are one-sided and G is first-order accurate only.
+ *   degree 1: triangles, tetrahedra, rectangles (Q1); degree 2: simplices.
+ *   DETERMINISM RULE: the cells of S are listed in ascending order, the (vertex, listed cell) pairs sorted by a stable
+ *   radix sort, every vertex adds its star in that order and the total is folded from per-block slots in a fixed
+ *   order: no floating-point atomics.  The same mesh arrays, mask and values give the same bits on every run and on
+ *   every mesh object.  Work and temporaries scale with |S| (two memsets clear the rest of the outputs).
+ *   PHX_ERR_VALUE: no mask and no cell tags on the mesh (call compute_tags_measures first), a NULL array, ncomp < 1,
+ *   2^31 - 1 or more pairs; PHX_ERR_NOT_IMPLEMENTED: degree 2 on quadrilaterals, degree 3, non-rectangular
+ *   quadrilaterals.  Every temporary is released on every return (phx_pool_stats). */
+int phx_recover_gradient(phx_mesh *m, int degree, int ncomp, const double *u, int loc_u, const uint8_t *cell_mask,
+                         int loc_mask, double *grad, double *eta2, int loc_out, double *sum);
 
 /* Times `reps` launches of the SpMV kernel with HIP events on the mesh's stream.
  * out[3] = {avg ms per launch, algorithmic bytes per launch (12 nnz + 20 n), padded bytes}. */

@@ -17,7 +17,10 @@ Host side (this package) mirrors the reference's interface for the path:
     with a bounding-box tree and `interpolate_nonmatching`: P1 / P2 / Q1 functions at arbitrary points
   * `phifem_amd.estimate`, `phifem_amd.mark_dorfler` <- no counterpart (dolfinx users write the residual forms in UFL):
     residual error indicators of the weak-Dirichlet scheme per cell and the Doerfler selection, on the device
-  * `phifem_amd.io`                               <- XDMFFile.write_mesh / write_function / read_mesh
+  * `phifem_amd.recover_gradient`, `phifem_amd.estimate_zz` <- no counterpart (dolfinx users project the gradient with
+    a mass solve): the volume-weighted vertex average of the cell-wise gradient and the Zienkiewicz-Zhu indicator built
+    on it, for every solver here
+  * `phifem_amd.io`                              <- XDMFFile.write_mesh / write_function / read_mesh
 Everything numerical runs in `libphifem_hip.so` (hand-written HIP for gfx950) through the C ABI
 declared in `include/phifem_hip.h`.  There is no CPU fallback.
 """
@@ -25,6 +28,7 @@ from . import _lib  # noqa: F401  (fails loudly when the HIP library is missing)
 from .mesh import Mesh, MeshTags, create_box, create_rectangle, prolongate, refine, restrict  # noqa: F401
 from .evaluate import evaluate, interpolate_nonmatching, locate, locator_info  # noqa: F401
 from .estimate import estimate, mark_dorfler  # noqa: F401
+from .recover import estimate_zz, recover_gradient  # noqa: F401
 from . import io  # noqa: F401
 from .mesh_scripts import (DeviceExpression, NodalFunction, Quadric, compute_tags_measures,  # noqa: F401
                            interpolate)

@@ -123,6 +123,7 @@ SIGNATURES = {
     "phx_cell_errors": ([_vp, _i, _i, _vp, _vp, _i64, _vp, _i, _vp, _vp, _pd], _i),
     "phx_estimate_poisson_wd": ([_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _pd], _i),
     "phx_mark_dorfler": ([_vp, _i64, _vp, _i, _d, _vp, _i, _pi64], _i),
+    "phx_recover_gradient": ([_vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _pd], _i),
     "phx_system_destroy": ([_vp], _i),
     "phx_system_info": ([_vp, _pi64], _i),
     "phx_system_export": ([_vp, _vp, _vp, _vp, _vp, _vp], _i),

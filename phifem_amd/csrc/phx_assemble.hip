@@ -2128,3 +2128,4 @@ extern "C" int phx_system_export(phx_system *s, int64_t *rowptr, int32_t *col, d
 #include "phx_assemble_wd_quad.inc.hip"
 #include "phx_errors.inc.hip"
 #include "phx_estimate.inc.hip"
+#include "phx_recover.inc.hip"

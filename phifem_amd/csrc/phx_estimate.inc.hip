@@ -1,5 +1,5 @@
 // Residual error indicators of the weak-Dirichlet Poisson scheme and the Doerfler selection: included
-// LAST by phx_assemble.hip (shares Geo / load_cell / gram, the conical rules, the P2 basis, the Q1-rectangle layer,
+// by phx_assemble.hip after the assemblers, in front of phx_recover.inc.hip (shares Geo / load_cell / gram, the conical rules, the P2 basis, the Q1-rectangle layer,
 // DevTemps / to_device and the fixed-order sums of phx_errors.inc.hip).  For a cell T of Omega_h (cell tag 1 or 2)
 //   eta_T^2 = R_T + J_T + B_T
 //   R_T = h_T^2 int_T (f_h + Laplace u_h)^2
