@@ -525,6 +525,20 @@ int phx_assemble_poisson_flux(phx_mesh *m, const double *params, int facet_tag, 
 int phx_assemble_elasticity_if(phx_mesh *m, const double *params, const double *phi_h,
                                const double *f_h, const double *u_D, const int32_t *bc_vertices,
                                int64_t nbc, int loc, phx_system **out);
+/* Weak-Dirichlet linear elasticity, one material, displacement prescribed on {phi = 0}: mixed (u, p) in
+ * P1^d x P1^d on triangles / tetrahedra, the vector analogue of phx_assemble_poisson_wd (forms
+ * demo/weak-dirichlet/flower/main.py:112-135, 142-151 with sigma(u) : eps(v), (sigma(u) n) . v and the jump of
+ * sigma(u) n in place of the gradient terms; material law demo/interface-elasticity/data.py:5-36, plane strain in
+ * 2-D), on the tags held by the mesh (dx((1,2)), dx(2), dS((2,3)), ds = ds_bdy(100) in box mode or every exterior
+ * facet of a sub-mesh).  The coefficients are not rescaled by E.
+ *   params[4] = {E, nu, pen_coef, stab_coef}
+ *   phi_h[nv]; f_h, u_D: [d*nv] component-major nodal vector fields (host or device, `loc`).
+ * DoF layout: component-major blocks of nv: u[a] -> a, p[a] -> d+a; n_full = 2 d nv.  Active: u on the vertices of
+ * cells tagged 1 / 2, p on the vertices of cells tagged 2.  phx_solve preconditions with the vertex blocks.
+ * Quadrilateral meshes, slabs and partitioned ranks: PHX_ERR_NOT_IMPLEMENTED.  Rows longer than the last slot
+ * capacity (2-D: 64, 128, 256; 3-D: 128, 256, 512): PHX_ERR_CAPACITY. */
+int phx_assemble_elasticity_wd(phx_mesh *m, const double *params, const double *phi_h, const double *f_h,
+                               const double *u_D, int loc, phx_system **out);
 int phx_system_destroy(phx_system *s);
 /* info[14] = {n_active, n_active_u, nnz (structural, CSR), n_full (= 2*nv), sell_padded_nnz,
  *             slot_capacity, sell_nnz (explicit zeros dropped), n_slices, value-indexed slices,

@@ -9,6 +9,9 @@ Host side (this package) mirrors the reference's interface for the path:
   * `phifem_amd.solver.StrongDirichletSolver`        <- demo/strong-dirichlet/flower/main.py:83-182
   * `phifem_amd.solver.NeumannRobinSolver`           <- demo/robin/square/main.py:98-190 (simplices) and
     demo/neumann/square/main.py:49-158 (quadrilaterals)
+  * `phifem_amd.solver.InterfaceElasticitySolver`    <- demo/interface-elasticity/main.py:145-289
+  * `phifem_amd.solver.ElasticitySolver`             <- no counterpart: one-material linear elasticity with the
+    displacement prescribed on {phi = 0}, the vector analogue of the weak-Dirichlet scheme (P1^d x P1^d)
   * `phifem_amd.partition_cells`, `phifem_amd.distributed.PartitionedProblem`  <- no counterpart: unstructured
     background meshes partitioned over the ranks (the reference is serial, src/phifem/mesh_scripts.py:264)
   * `phifem_amd.refine`, `phifem_amd.prolongate`     <- dolfinx.mesh.refine (demo/interface-elasticity/main.py:390),
@@ -34,5 +37,5 @@ from .mesh_scripts import (DeviceExpression, NodalFunction, Quadric, compute_tag
                            interpolate)
 from .partition import partition_cells, partition_layout  # noqa: F401
 from .distributed import PartitionedProblem  # noqa: F401
-from .solver import (InterfaceElasticitySolver, NeumannRobinSolver, PhiFEMSolver,  # noqa: F401
+from .solver import (ElasticitySolver, InterfaceElasticitySolver, NeumannRobinSolver, PhiFEMSolver,  # noqa: F401
                      StrongDirichletSolver)

@@ -551,3 +551,75 @@ class InterfaceElasticitySolver(PhiFEMSolver):
                 "y_in": w[2 * d:2 * d + d * d].T.reshape(nv, d, d),
                 "y_out": w[2 * d + d * d:2 * d + 2 * d * d].T.reshape(nv, d, d),
                 "p": w[2 * d + 2 * d * d:].T}
+
+
+class ElasticitySolver(PhiFEMSolver):
+    """One-material linear elasticity with the displacement prescribed on the immersed boundary {phi = 0}: mixed
+    (u, p) in P1^d x P1^d on triangles / tetrahedra, the vector analogue of `PhiFEMSolver` (C ABI
+    `phx_assemble_elasticity_wd`; forms in DESIGN.md 7h).
+
+        a((u,p),(v,q)) = (sigma(u), eps(v))_{dx(1,2)} - ((sigma(u) n), v)_{ds}
+                         + pen h^-2 (u - phi p / h, v - phi q / h)_{dx(2)} + stab avg(h) ([sigma(u) n], [sigma(v) n])_{dS(2,3)}
+        L(v,q)         = (f, v)_{dx(1,2)} + pen h^-2 (u_D, v - phi q / h)_{dx(2)}
+
+    sigma(u) = lam tr eps(u) I + 2 mu eps(u) with lam = E nu / ((1 + nu)(1 - 2 nu)), mu = E / (2 (1 + nu)): the law
+    and plane-strain convention of `InterfaceElasticitySolver`.  The coefficients are NOT rescaled by E: pen_coef and
+    stab_coef are the caller's to choose for the units of E (the demo works at E = 1, as the reference's interface
+    demo does by dividing f by E_in).
+
+    The mesh is a tagged generated box / rectangle with simplex cells, a `Mesh.from_arrays` mesh, or the sub-mesh of
+    `compute_tags_measures(..., box_mode=False)`.  Solution layout: component-major blocks of nv entries, u_a -> a,
+    p_a -> d + a (`split`); inactive DoFs are exactly 0.  The solve preconditions with the vertex blocks
+    (`stats["precond"] == "vertex-block-jacobi"`); there is no coarse space or multilevel cycle for this system."""
+
+    def __init__(self, mesh, E=1.0, nu=0.3, pen_coef=1.0, stab_coef=1.0, deterministic=False, degree=1,
+                 coarse_space=None, multilevel=False):
+        if getattr(mesh, "cell_type", None) == "quadrilateral":
+            raise NotImplementedError("weak-Dirichlet elasticity is assembled on triangles and tetrahedra (no Q1 spaces)")
+        if degree != 1:
+            raise NotImplementedError("weak-Dirichlet elasticity: P1 x P1 is implemented (degree = 1)")
+        if coarse_space is not None:
+            raise NotImplementedError("weak-Dirichlet elasticity has no coarse-space correction (vertex-block Jacobi only)")
+        if multilevel is not False:
+            raise NotImplementedError("weak-Dirichlet elasticity has no multilevel preconditioner (vertex-block Jacobi only)")
+        super().__init__(mesh, pen_coef=pen_coef, stab_coef=stab_coef, deterministic=deterministic)
+        self.params = np.array([E, nu, pen_coef, stab_coef], dtype=np.float64)
+
+    def assemble(self, phi_h, f_h, u_D):
+        """phi_h: (nv,) nodal level-set; f_h, u_D: (nv, d) nodal vector fields on the host, or device tensors (nv,) and
+        component-major (d, nv).  All three on the host or all three on the device."""
+        self._free()
+        self._apply_options()
+        m = self.mesh
+        d = m.gdim
+        on_dev = [hasattr(a, "data_ptr") and a.is_cuda for a in (phi_h, f_h, u_D)]
+        if any(on_dev) and not all(on_dev):
+            raise ValueError("phi_h, f_h and u_D must all live on the host or all on the device")
+        h = C.c_void_p()
+        if all(on_dev):
+            if tuple(f_h.shape) != (d, m.nv) or tuple(u_D.shape) != (d, m.nv):
+                raise ValueError("device f_h and u_D must be component-major (d, nv)")
+            phi_h = self._arr(phi_h, m.nv)
+            f_cm, u_cm = self._arr(f_h, d * m.nv), self._arr(u_D, d * m.nv)
+            loc = L.DEVICE
+        else:
+            phi_h = np.ascontiguousarray(phi_h, dtype=np.float64)
+            f_h, u_D = np.asarray(f_h, dtype=np.float64), np.asarray(u_D, dtype=np.float64)
+            if phi_h.shape != (m.nv,) or f_h.shape != (m.nv, d) or u_D.shape != (m.nv, d):
+                raise ValueError("phi_h must be (nv,), f_h and u_D (nv, d)")
+            f_cm, u_cm = np.ascontiguousarray(f_h.T), np.ascontiguousarray(u_D.T)   # component-major
+            loc = L.HOST
+        self._keep = (phi_h, f_cm, u_cm)
+        L.check(L.lib.phx_assemble_elasticity_wd(m._h, self.params.ctypes.data_as(C.c_void_p), L.ptr(phi_h)[0],
+                                                 L.ptr(f_cm)[0], L.ptr(u_cm)[0], loc, C.byref(h)))
+        self._sys = h
+        return self.info()
+
+    def split(self, w):
+        """(u, p) of the mixed solution, each (nv, d)."""
+        d, nv = self.mesh.gdim, self.mesh.nv
+        w = w.reshape(2 * d, nv)
+        return w[:d].T, w[d:].T
+
+    def estimate(self, w, parts=False):
+        raise NotImplementedError(_OTHER_RESIDUALS)
