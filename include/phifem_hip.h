@@ -665,7 +665,8 @@ int phx_krylov_reduced_loop(const phx_system *s, int *on);
  * (r, r) -> scal[8 + 5] (all-reduced by the driver), 13 KR_RESTART restart of the recurrences from r.  Partitioned
  * coarse correction: 30 KR_CC_RESTRICT_P / 32 KR_CC_RESTRICT_S restrict p / s, 31 KR_CC_ADD_P / 33 KR_CC_ADD_S add the
  * prolonged correction.  52-55 (KR_ID_SPMV_P, KR_ID_UPDATE_S, KR_ID_SPMV_S, KR_ID_UPDATE_XRP) belong to the identity
- * loop of phx_solve and are not meant for this API. */
+ * loop of phx_solve and 56-63 to its reduced loop; their workspaces are built by phx_solve alone (phase 0 of this API
+ * never puts those loops in force), so they are refused with PHX_ERR_VALUE before anything is launched. */
 int phx_krylov_phase(phx_system *s, int phase);
 int phx_krylov_finish(phx_system *s, double *x, int loc);
 /* reset != 0: arm the SpMV event profile; else collect {average seconds, launches timed}. */

@@ -2319,6 +2319,11 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
   phx_mesh *m = s->mesh;
   const int64_t n = s->n;
   hipStream_t st = m->stream;
+  // the identity and reduced phases read kr_cmask / kr_red, which only phase 0 of a native solve (mode 0) builds
+  PHX_REQUIRE(phase < KR_ID_SPMV_P || phase > KR_ID_UPDATE_XRP || s->kr_ident_used, PHX_ERR_VALUE,
+              "Krylov phase %d belongs to the identity loop, which is not in force for this system", phase);
+  PHX_REQUIRE(phase < KR_RED_PRECOND_P || phase > KR_RED_RESTART || s->kr_red_used, PHX_ERR_VALUE,
+              "Krylov phase %d belongs to the reduced loop, which is not in force for this system", phase);
   if (phase == KR_BEGIN) {
     // (re)build the preconditioner for this system and ownership mask
     if (s->precond_state == 1 && s->precond->own_ptr != s->own) {

@@ -54,7 +54,7 @@ for k, c in enumerate(cases):
     if deg == 2:
         x = m.p2_dof_points()
     uex = np.prod(np.sin(x), axis=1)
-    s = P.PhiFEMSolver(m, degree=deg) if deg == 2 else P.PhiFEMSolver(m)
+    s = P.PhiFEMSolver(m, degree=deg) if deg == 2 else P.PhiFEMSolver(m, deterministic=bool(c.get("det")))
     s.assemble(phi, float(d) * uex, uex)
     w = s.solve(rtol=c["rtol"], max_iter=20000)
     st = dict(s.stats)
@@ -145,8 +145,11 @@ def test_stencil_rows_residual_at_rounding_level(runs):
 
 def test_repeated_solve_gives_the_same_answer(runs):
     """A second solve of the same system (workspace and maps kept) takes the reduced loop again and returns the same
-    solution within 100 rtol.  (Repeated solves are not bit-identical, not even with PHX_OPT_DETERMINISTIC: the
-    iteration counts of the full-length and the standard loop move between solves of one system as well.)"""
+    solution within 100 rtol.  (Without PHX_OPT_DETERMINISTIC repeated solves need not be bit-identical: the dot
+    products are summed by atomics in arrival order, and the iteration counts of the full-length and the standard loop
+    may move between solves of one system as well.  With it they ARE bit-identical, iterate by iterate, under all three
+    loops: tests/test_hip_krylov_loops.py.  The option has to be the solver's own, `PhiFEMSolver(deterministic=True)`:
+    `solve()` sets PHX_OPT_DETERMINISTIC from that flag, whatever was set on the mesh before.)"""
     stats, sols = runs["red"]
     for k, (c, a) in enumerate(zip(CASES, stats)):
         assert a["red2"] and a["conv2"] and a["host_relres2"] <= RTOL * (1 + 1e-4), (c, a)

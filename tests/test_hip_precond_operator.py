@@ -34,7 +34,10 @@ Every case prints its worst ratio to its bound.
 
 Not covered: P2 with `coarse_space` (the two-level form is pinned by test_hip_p2_coarse.py through whole solves; its
 application under the phase API is left out here), the elasticity coarse correction (not built under the phase API)
-and the reduced-loop phases 56 - 63 (native loop only, tests/test_hip_kr_reduced.py)."""
+and the identity- and reduced-loop phases 52 - 63 (native loop only; the phase API refuses them).  `Applied.one_iteration`
+runs a real iteration only to obtain a second p: the vector phases and scalar recurrences themselves are pinned one phase
+at a time by tests/test_hip_krylov_phases.py, the native loops (the reduced application `box_precond_apply_red` among
+them) through truncated solves by tests/test_hip_krylov_loops.py."""
 import ctypes as C
 import warnings
 
