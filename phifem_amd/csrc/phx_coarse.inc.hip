@@ -847,7 +847,7 @@ static int p2_coarse_build(phx_system *s, phx_coarse **out) {
   const int req = m->p2_coarse;
   if (req == 0) return PHX_OK;
   const auto t0 = std::chrono::steady_clock::now();
-  if (!m->is_box || m->is_submesh || !m->edges || s->own || s->kr_work || s->precond_state != 1 || !s->precond ||
+  if (!m->is_box || m->is_submesh || !m->edges || s->own || s->kr_work || kr_precond_kind(s) != KR_PC_BOX || !s->precond ||
       s->precond->dist || s->n == 0 || !s->u_p2_block) {
     s->cc_reason = PHX_CC_NOT_BOX;
     return PHX_OK;

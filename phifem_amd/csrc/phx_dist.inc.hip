@@ -369,7 +369,7 @@ extern "C" int phx_solve_distributed(phx_system *s, phx_comm *c, int npeers, con
       PHX_CHECK(coarse_build(s, s->el_nblk, &s->cc, &red));
     }
     // after the vote: the same on every rank (set up from all-reduced numbers)
-    const KrDist d{c, &H, overlap, s->precond_state == 1 && s->precond->dist, s->cc != nullptr && s->cc->dist, pc_all};
+    const KrDist d{c, &H, overlap, kr_slab_exact(s), s->cc != nullptr && s->cc->dist, pc_all};
     return kr_drive(s, &d, rtol, max_iter, x_out, loc, stats);
   };
   const int rc = body();

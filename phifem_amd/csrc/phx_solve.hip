@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "phx_common.h"
@@ -1689,6 +1690,25 @@ static int det_fold(phx_system *s, double *out0, double *out1, double *out2 = nu
   s->dpart_used = 0;
   return PHX_OK;
 }
+// One launch that accumulates dot products: `launch(grid, part)` runs on `nb` blocks, the block count that is also
+// reserved for its partial sums, and these are folded into out0 .. out3 (det_fold).
+template <class Launch>
+static int dot_pass(phx_system *s, int64_t nb, Launch &&launch, double *out0, double *out1 = nullptr, double *out2 = nullptr,
+                    double *out3 = nullptr, int add = 0) {
+  DotPart dp{nullptr, nullptr};
+  PHX_CHECK(det_part(s, nb, &dp));
+  launch(dim3((unsigned)nb), dp);
+  return det_fold(s, out0, out1, out2, out3, add);
+}
+
+// Number of fused dot products -> the DOTS argument of the SpMV kernels: f(std::integral_constant<int, DOTS>) for the
+// entry of the list that equals `dots` (the last entry serves every other value).
+template <int D0, int... DS, class F>
+static inline void with_dots(int dots, F &&f) {
+  if constexpr (sizeof...(DS) == 0) f(std::integral_constant<int, D0>{});
+  else if (dots == D0) f(std::integral_constant<int, D0>{});
+  else with_dots<DS...>(dots, f);
+}
 
 // part 0: every row.  Multi-GPU overlap (s->bnd set by phx_spmv_flag_rows): part 1 = every row that references no halo
 // entry (runs while the halo is in flight), part 2 = the flagged rows (after the unpack); both add into the same slots.
@@ -1706,9 +1726,9 @@ static int launch_spmv(phx_system *s, const double *vals, const double *x, doubl
     if (s->nbnd > 0) {
       const dim3 gb((unsigned)std::min<int64_t>(phx_div_up(s->nbnd, 256), 2048));
       if (dots > 0) PHX_CHECK(det_part(s, gb.x, &dp));
-      if (dots == 0) k_spmv_bnd<0><<<gb, block, 0, st>>>(s->nbnd, s->bnd_rec, s->slice_ptr, s->sell_col, vals, kinds, s->stencil, x, y, d0, o0, o1, dp);
-      else if (dots == 1) k_spmv_bnd<1><<<gb, block, 0, st>>>(s->nbnd, s->bnd_rec, s->slice_ptr, s->sell_col, vals, kinds, s->stencil, x, y, d0, o0, o1, dp);
-      else k_spmv_bnd<2><<<gb, block, 0, st>>>(s->nbnd, s->bnd_rec, s->slice_ptr, s->sell_col, vals, kinds, s->stencil, x, y, d0, o0, o1, dp);
+      with_dots<0, 1, 2>(dots, [&](auto D) {
+        k_spmv_bnd<decltype(D)::value><<<gb, block, 0, st>>>(s->nbnd, s->bnd_rec, s->slice_ptr, s->sell_col, vals, kinds, s->stencil, x, y, d0, o0, o1, dp);
+      });
       PHX_HIP(hipGetLastError());
     }
     if (dots > 0) PHX_CHECK(det_fold(s, o0, o1));   // ... together with the partial sums of the interior launch
@@ -1734,13 +1754,10 @@ static int launch_spmv(phx_system *s, const double *vals, const double *x, doubl
   if (nb == 0 && !s->p2s) return PHX_OK;
   const dim3 g2((unsigned)std::max<int64_t>(nb, 1));
   if (dots > 0 && nb > 0) PHX_CHECK(det_part(s, nb, &dp));
-  if (nb == 0) {}
-  else if (dots == 0)
-    k_spmv_sell<0><<<g2, block, 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, vals, x, y, own, d0, o0, o1, xg, kinds, rows, nb_sell, sa, bnd, dp, nullptr, nullptr);
-  else if (dots == 1)
-    k_spmv_sell<1><<<g2, block, 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, vals, x, y, own, d0, o0, o1, xg, kinds, rows, nb_sell, sa, bnd, dp, nullptr, nullptr);
-  else
-    k_spmv_sell<2><<<g2, block, 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, vals, x, y, own, d0, o0, o1, xg, kinds, rows, nb_sell, sa, bnd, dp, nullptr, nullptr);
+  if (nb > 0)
+    with_dots<0, 1, 2>(dots, [&](auto D) {
+      k_spmv_sell<decltype(D)::value><<<g2, block, 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, vals, x, y, own, d0, o0, o1, xg, kinds, rows, nb_sell, sa, bnd, dp, nullptr, nullptr);
+    });
   PHX_HIP(hipGetLastError());
   if (s->p2s && s->p2s->nrun > 0 && part_of == 0) {
     // structured P2: the interior rows from the eight class stencils, one wavefront per run
@@ -1748,9 +1765,9 @@ static int launch_spmv(phx_system *s, const double *vals, const double *x, doubl
     const dim3 gp((unsigned)std::min<int64_t>(phx_div_up(ps->nrun, 4), 4096));
     DotPart dq{nullptr, nullptr};
     if (dots > 0) PHX_CHECK(det_part(s, gp.x, &dq));
-    if (dots == 0) k_spmv_p2s<0><<<gp, block, 0, st>>>(ps->nrun, ps->runs, ps->tabE, ps->tabO, ps->linemask, x, y, d0, o0, o1, dq);
-    else if (dots == 1) k_spmv_p2s<1><<<gp, block, 0, st>>>(ps->nrun, ps->runs, ps->tabE, ps->tabO, ps->linemask, x, y, d0, o0, o1, dq);
-    else k_spmv_p2s<2><<<gp, block, 0, st>>>(ps->nrun, ps->runs, ps->tabE, ps->tabO, ps->linemask, x, y, d0, o0, o1, dq);
+    with_dots<0, 1, 2>(dots, [&](auto D) {
+      k_spmv_p2s<decltype(D)::value><<<gp, block, 0, st>>>(ps->nrun, ps->runs, ps->tabE, ps->tabO, ps->linemask, x, y, d0, o0, o1, dq);
+    });
     PHX_HIP(hipGetLastError());
   }
   if (dots > 0 && part_of == 0) PHX_CHECK(det_fold(s, o0, o1));
@@ -1889,6 +1906,28 @@ static int prof_collect(phx_system *s, double *avg_s, int *count, int c = 0) {
     s->mesh->timings[5] = (double)*count;
   }
   return PHX_OK;
+}
+
+// The preconditioner in force for the system, read from its fields each time it is asked (phx_krylov_precond_disable and
+// an ownership change alter them between solves).  NONE: Jacobi alone, folded into the stored values, phat / shat alias
+// p / s; U_JACOBI: unscaled u columns, D_u^-1 on the u rows; BOX: K_box^-1 on the lattice; VBLOCKS: dense vertex blocks
+// (interface elasticity); MULTILEVEL: the refinement hierarchy.  Where several are built the first of this order is
+// applied: multilevel, lattice box, vertex blocks, u-block Jacobi.  (ml_setup refuses a system the lattice serves.)
+enum KrPrecond { KR_PC_NONE, KR_PC_U_JACOBI, KR_PC_BOX, KR_PC_VBLOCKS, KR_PC_MULTILEVEL };
+static inline KrPrecond kr_precond_kind(const phx_system *s) {
+  if (s->ml) return KR_PC_MULTILEVEL;
+  if (s->precond_state == 1) return KR_PC_BOX;
+  if (s->bj) return KR_PC_VBLOCKS;
+  if (s->u_unscaled) return KR_PC_U_JACOBI;
+  return KR_PC_NONE;
+}
+// phat / shat are vectors of their own, which phases 7 / 8 fill and the SpMVs read
+static inline bool kr_hats_apart(const phx_system *s) { return kr_precond_kind(s) != KR_PC_NONE; }
+// the preconditioners that act on the u block alone and cost far more than an SpMV: the rows outside the u block are
+// copied by RestOut, and the convergence checks are scheduled from the rate (kr_drive)
+static inline bool kr_precond_on_u_block(const phx_system *s) {
+  const KrPrecond k = kr_precond_kind(s);
+  return k == KR_PC_BOX || k == KR_PC_MULTILEVEL;
 }
 
 #include "phx_precond.inc.hip"
@@ -2178,7 +2217,7 @@ static inline KrVecs kr_vecs(phx_system *s) {
   double *w = s->kr_work ? s->kr_work : s->work;
   const int64_t n = s->n;
   KrVecs V{w, w + n, w + 2 * n, w + 3 * n, w + 4 * n, w + 5 * n, w + 6 * n, w + 7 * n, w + 2 * n, w + 4 * n};
-  if (s->precond_state == 1 || s->u_unscaled || s->bj || s->ml) {
+  if (kr_hats_apart(s)) {
     // attached workspaces (multi-GPU drivers, 10 n doubles) carry the two extra vectors themselves
     V.phat = s->kr_work ? w + 8 * n : s->pvec;
     V.shat = s->kr_work ? w + 9 * n : s->pvec + n;
@@ -2186,6 +2225,13 @@ static inline KrVecs kr_vecs(phx_system *s) {
   return V;
 }
 static inline double *kr_scal(phx_system *s) { return s->kr_scal ? s->kr_scal : s->scal; }
+// identity part of the box and multilevel preconditioners, written to `hat` (phat or shat) by the producers of p and s
+static inline RestOut kr_rest_out(const phx_system *s, const KrVecs &V, double *hat) {
+  const bool on = kr_precond_on_u_block(s) && V.phat != V.p;
+  return RestOut{on ? hat : nullptr, s->structured ? nullptr : s->perm, s->nu};
+}
+// lattice preconditioner of a z-partitioned box, exact across the slabs: applied in two halves around an all-gather
+static inline bool kr_slab_exact(const phx_system *s) { return kr_precond_kind(s) == KR_PC_BOX && s->precond->dist; }
 
 // reduced loop: compact stored-row vectors (nslices * 16 entries each) and u in solver order (n)
 struct KrRed {
@@ -2202,7 +2248,7 @@ static inline KrRed kr_red_vecs(phx_system *s) {
 // the stencil row equal to the lattice row {2 (cx + cy + cz), -cx, -cy, -cz} of K_box (read once per system).
 static int kr_identity(phx_system *s, bool *on) {
   *on = false;
-  if (!phx_sw_kr_identity() || !s->structured || !s->u_unscaled || s->u_weighted || s->p2s || s->precond_state != 1 || !s->precond ||
+  if (!phx_sw_kr_identity() || !s->structured || !s->u_unscaled || s->u_weighted || s->p2s || kr_precond_kind(s) != KR_PC_BOX || !s->precond ||
       s->precond->f32 || s->precond->dist || s->own || s->kr_work || s->bnd || s->nseg <= 0 || s->n == 0)
     return PHX_OK;
   hipStream_t st = s->mesh->stream;
@@ -2244,35 +2290,26 @@ static int kr_reduced(phx_system *s, bool *on) {
 // unwritten).  dots 1: o0 += (y, d0);  dots 3: o0 += (y, d0), o1 += (y, y), o2 += (y, d1).  PHX_OPT_DETERMINISTIC:
 // the partial sums are ADDED to slot 0 (R_RV already holds the C-row share there).  compact (reduced loop): y, d0 and d1
 // are compact stored-row vectors (k_spmv_sell<DOTS, true>); dots 0: no dot product.
-template <bool CY>
-static int launch_spmv_stored_t(phx_system *s, const double *x, double *y, int dots, const double *d0, const double *d1,
-                                double *o0, double *o1, double *o2) {
+static int launch_spmv_stored(phx_system *s, const double *x, double *y, int dots, const double *d0, const double *d1,
+                              double *o0, double *o1, double *o2, bool compact = false) {
   hipStream_t st = s->mesh->stream;
   const int64_t nb = (phx_div_up(s->nslices, 4) + 7) & ~(int64_t)7;   // a multiple of 8, as launch_spmv
   if (nb == 0) return PHX_OK;
   const int xg = s->mesh->spmv_xcd_group;
   const StencilArgs sa{0, nullptr, 0, nullptr, nullptr, 0, nullptr};
-  DotPart dp{nullptr, nullptr};
-  if (dots > 0) PHX_CHECK(det_part(s, nb, &dp));
-  if (dots == 0)
-    k_spmv_sell<0, CY><<<dim3((unsigned)nb), dim3(256), 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, s->sell_val, x, y, nullptr,
-                                                                 nullptr, nullptr, nullptr, xg, s->sell_kind, s->sell_rows, nb, sa, nullptr,
-                                                                 dp, nullptr, nullptr);
-  else if (dots == 1)
-    k_spmv_sell<1, CY><<<dim3((unsigned)nb), dim3(256), 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, s->sell_val, x, y, nullptr,
-                                                                 d0, o0, nullptr, xg, s->sell_kind, s->sell_rows, nb, sa, nullptr, dp,
-                                                                 nullptr, nullptr);
-  else
-    k_spmv_sell<3, CY><<<dim3((unsigned)nb), dim3(256), 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, s->sell_val, x, y, nullptr,
-                                                                 d0, o0, o1, xg, s->sell_kind, s->sell_rows, nb, sa, nullptr, dp, d1, o2);
+  // the operands a kernel does not accumulate (d1, o1, o2 with one dot product, all of them with none) are nullptr
+  // here and never read there
+  const auto launch = [&](dim3 grid, DotPart dp) {
+    with_dots<0, 1, 3>(dots, [&](auto D) {
+      const auto kernel = compact ? k_spmv_sell<decltype(D)::value, true> : k_spmv_sell<decltype(D)::value, false>;
+      kernel<<<grid, dim3(256), 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, s->sell_val, x, y, nullptr, d0, o0, o1, xg,
+                                         s->sell_kind, s->sell_rows, nb, sa, nullptr, dp, d1, o2);
+    });
+  };
+  if (dots > 0) return dot_pass(s, nb, launch, o0, o1, o2, nullptr, 1);
+  launch(dim3((unsigned)nb), DotPart{nullptr, nullptr});
   PHX_HIP(hipGetLastError());
-  if (dots == 0) return PHX_OK;
-  return det_fold(s, o0, dots == 3 ? o1 : nullptr, dots == 3 ? o2 : nullptr, nullptr, 1);
-}
-static int launch_spmv_stored(phx_system *s, const double *x, double *y, int dots, const double *d0, const double *d1,
-                              double *o0, double *o1, double *o2, bool compact = false) {
-  return compact ? launch_spmv_stored_t<true>(s, x, y, dots, d0, d1, o0, o1, o2)
-                 : launch_spmv_stored_t<false>(s, x, y, dots, d0, d1, o0, o1, o2);
+  return PHX_OK;
 }
 
 // Phases of kr_phase.  The numbers are ABI (phx_krylov_phase; dist_solver.py names them alike).
@@ -2313,6 +2350,114 @@ enum KrPhase {
   KR_RED_RESTART = 63,     // after KR_TRUE_RESIDUAL: u_C += r_C, recurrences restarted from r_B
 };
 
+// Everything phase 0 decides before its launches: the preconditioner (re)built for this system and ownership mask,
+// phat / shat allocated where they stand apart, and the loop variant (identity and reduced: the native loop, mode 0, only).
+static int kr_setup(phx_system *s, int mode) {
+  phx_mesh *m = s->mesh;
+  const int64_t n = s->n;
+  if (s->precond_state == 1 && s->precond->own_ptr != s->own) {
+    phx_box_precond_destroy(s->precond);
+    s->precond = nullptr;
+    s->precond_state = 0;
+  }
+  if (s->precond_state == 0) PHX_CHECK(box_precond_setup(s));
+  if (s->el_nblk > 0 && !s->bj && !s->bj_tried && m->precond != 0 && s->rowptr && n > 0) {
+    s->bj_tried = true;
+    PHX_CHECK(blockjac_build(s, s->el_nblk, &s->bj));   // nullptr when a vertex block is singular: scalar Jacobi then
+    // coarse correction on top of the vertex blocks (one rank; a partitioned box keeps the blocks alone)
+    if (s->bj && !s->own && !s->kr_work && !s->cc_tried) {
+      s->cc_tried = true;
+      const auto t0 = std::chrono::steady_clock::now();
+      PHX_CHECK(coarse_build(s, s->el_nblk, &s->cc));
+      if (s->cc) s->cc->build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    }
+  }
+  // P2 weak Dirichlet: coarse correction on top of the lattice preconditioner (PHX_OPT_P2_COARSE), once per system
+  if (s->u_p2_block && m->p2_coarse != 0 && !s->cc_tried) {
+    s->cc_tried = true;
+    PHX_CHECK(p2_coarse_build(s, &s->cc));
+  }
+  // multilevel preconditioner over the refinement hierarchy (PHX_OPT_MULTILEVEL), once per system.  The option speaks
+  // of P1 weak-Dirichlet systems on simplices: every other system of the mesh is solved as without it
+  if (m->multilevel != 0 && !s->ml && n > 0 && ml_kind_served(s)) PHX_CHECK(ml_setup(s));
+  if (kr_hats_apart(s) && n > 0 && !s->kr_work) {
+    // phat / shat: rows the preconditioner never writes (u rows another rank owns) stay zero
+    if (!s->pvec) PHX_HIP(phx_malloc(&s->pvec, sizeof(double) * (size_t)n * 2));
+    PHX_HIP(hipMemsetAsync(s->pvec, 0, sizeof(double) * (size_t)n * 2, m->stream));
+  }
+  bool ident = false, red = false;
+  if (mode == 0) PHX_CHECK(kr_identity(s, &ident));
+  if (ident) PHX_CHECK(kr_reduced(s, &red));
+  s->kr_ident_used = ident;
+  s->kr_red_used = red;
+  return PHX_OK;
+}
+
+// out = P in, the preconditioner in force (phases 7 / 8; nothing to do where out aliases in).  A slab-exact lattice
+// preconditioner is applied in two halves: stage 0 is then its first, stage 2 (phases 9 / 10, after the all-gather of
+// the carries) its second; every other preconditioner is whole at stage 0.
+static int kr_precond_apply(phx_system *s, const double *in, double *out, int stage) {
+  if (stage == 2) return kr_slab_exact(s) ? box_precond_apply(s, in, out, 2) : PHX_OK;
+  switch (kr_precond_kind(s)) {
+    case KR_PC_MULTILEVEL:
+      return ml_apply(s, in, out);
+    case KR_PC_BOX:
+      PHX_CHECK(box_precond_apply(s, in, out, kr_slab_exact(s) ? 1 : 0));
+      return s->cc && s->cc->p2 ? coarse_apply_add(s, s->cc, in, out) : PHX_OK;
+    case KR_PC_VBLOCKS:
+      PHX_CHECK(blockjac_apply(s, s->bj, in, out));
+      return coarse_apply_add(s, s->cc, in, out);
+    case KR_PC_U_JACOBI:
+      if (s->n > 0) k_jacobi_u<<<vec_grid(s->n), dim3(256), 0, s->mesh->stream>>>(s->n, s->nu, s->perm, s->diag, in, out);
+      return PHX_OK;
+    default:   // KR_PC_NONE: out is in
+      return PHX_OK;
+  }
+}
+
+// The phases that exist once for p and once for s differ in their operands alone: the vector that is preconditioned,
+// its hat, the product A hat, and the dot products the SpMV accumulates -- (out, d0) [, (out, out) [, (out, d1)]] into
+// the quantities q[0 .. dots) of the running parity.  fold0 / nfold: the quantities k_reduce_slots folds into R behind
+// the phase in mode 1 (none after an inner SpMV, whose halo part follows, and none in the native-only loops).
+struct KrOperands {
+  double *in, *hat, *out;
+  int dots;
+  const double *d0, *d1;
+  int q[3];
+  bool compact;   // reduced loop: in, out, d0, d1 are compact stored-row vectors
+  int fold0, nfold;
+};
+static KrOperands kr_operands(int phase, const KrVecs &V, const KrRed &R) {
+  KrOperands o{};
+  switch (phase) {
+    case KR_SPMV_P: case KR_SPMV_P_INNER: case KR_SPMV_P_HALO: case KR_PRECOND_P: case KR_EXACT_P: case KR_CC_RESTRICT_P: case KR_CC_ADD_P:
+    case KR_ID_SPMV_P:   // I_RV is R_RV
+      o = {V.p, V.phat, V.v, 1, V.rhat, nullptr, {R_RV}};
+      break;
+    case KR_SPMV_S: case KR_SPMV_S_INNER: case KR_SPMV_S_HALO: case KR_PRECOND_S: case KR_EXACT_S: case KR_CC_RESTRICT_S: case KR_CC_ADD_S:
+      o = {V.sv, V.shat, V.t, 2, V.sv, nullptr, {R_TS, R_TT}};
+      break;
+    case KR_ID_SPMV_S:
+      o = {V.sv, V.shat, V.t, 3, V.sv, V.rhat, {I_TS_B, I_TT_B, I_RT_B}};
+      break;
+    case KR_RED_PRECOND_P: case KR_RED_SPMV_P:   // compact p_B, v_B, rhat_B
+      o = {R.p, V.phat, R.v, 1, R.rhat, nullptr, {I_RV}, true};
+      break;
+    case KR_RED_PRECOND_S: case KR_RED_SPMV_S:
+      o = {R.sv, V.shat, R.t, 3, R.sv, R.rhat, {I_TS_B, I_TT_B, I_RT_B}, true};
+      break;
+    case KR_UPDATE_XR:   // no P/S pair: the two dot products of the x / r pass, folded like those of an SpMV
+      o = {nullptr, nullptr, nullptr, 2, nullptr, nullptr, {R_RHO, R_RR}};
+      break;
+  }
+  switch (phase) {
+    case KR_SPMV_P: case KR_SPMV_S: case KR_SPMV_P_HALO: case KR_SPMV_S_HALO: case KR_UPDATE_XR:
+      o.fold0 = o.q[0];
+      o.nfold = o.dots;
+  }
+  return o;
+}
+
 // mode 1 (phase API, multi-GPU): every dot product is folded into R right after its producer so
 // the driver can all-reduce it; mode 0 (native loop): consumers fold the slots, `par` alternates.
 static int kr_phase(phx_system *s, int phase, int mode, int par) {
@@ -2324,69 +2469,29 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
               "Krylov phase %d belongs to the identity loop, which is not in force for this system", phase);
   PHX_REQUIRE(phase < KR_RED_PRECOND_P || phase > KR_RED_RESTART || s->kr_red_used, PHX_ERR_VALUE,
               "Krylov phase %d belongs to the reduced loop, which is not in force for this system", phase);
-  if (phase == KR_BEGIN) {
-    // (re)build the preconditioner for this system and ownership mask
-    if (s->precond_state == 1 && s->precond->own_ptr != s->own) {
-      phx_box_precond_destroy(s->precond);
-      s->precond = nullptr;
-      s->precond_state = 0;
-    }
-    if (s->precond_state == 0) PHX_CHECK(box_precond_setup(s));
-    if (s->el_nblk > 0 && !s->bj && !s->bj_tried && m->precond != 0 && s->rowptr && n > 0) {
-      s->bj_tried = true;
-      PHX_CHECK(blockjac_build(s, s->el_nblk, &s->bj));   // nullptr when a vertex block is singular: scalar Jacobi then
-      // coarse correction on top of the vertex blocks (one rank; a partitioned box keeps the blocks alone)
-      if (s->bj && !s->own && !s->kr_work && !s->cc_tried) {
-        s->cc_tried = true;
-        const auto t0 = std::chrono::steady_clock::now();
-        PHX_CHECK(coarse_build(s, s->el_nblk, &s->cc));
-        if (s->cc) s->cc->build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-      }
-    }
-    // P2 weak Dirichlet: coarse correction on top of the lattice preconditioner (PHX_OPT_P2_COARSE), once per system
-    if (s->u_p2_block && m->p2_coarse != 0 && !s->cc_tried) {
-      s->cc_tried = true;
-      PHX_CHECK(p2_coarse_build(s, &s->cc));
-    }
-    // multilevel preconditioner over the refinement hierarchy (PHX_OPT_MULTILEVEL), once per system.  The option speaks
-    // of P1 weak-Dirichlet systems on simplices: every other system of the mesh is solved as without it
-    if (m->multilevel != 0 && !s->ml && n > 0 && ml_kind_served(s)) PHX_CHECK(ml_setup(s));
-    if ((s->precond_state == 1 || s->u_unscaled || s->bj || s->ml) && n > 0 && !s->kr_work) {
-      // phat / shat: rows the preconditioner never writes (u rows another rank owns) stay zero
-      if (!s->pvec) PHX_HIP(phx_malloc(&s->pvec, sizeof(double) * (size_t)n * 2));
-      PHX_HIP(hipMemsetAsync(s->pvec, 0, sizeof(double) * (size_t)n * 2, st));
-    }
-    bool ident = false, red = false;
-    if (mode == 0) PHX_CHECK(kr_identity(s, &ident));
-    if (ident) PHX_CHECK(kr_reduced(s, &red));
-    s->kr_ident_used = ident;
-    s->kr_red_used = red;
-  }
+  if (phase == KR_BEGIN) PHX_CHECK(kr_setup(s, mode));
   const KrVecs V = kr_vecs(s);
   double *S = kr_scal(s);
   const dim3 block(256);
-  // identity part of the box preconditioner, written by the producers of p and s (RestOut)
-  const bool rest_out = (s->precond_state == 1 || s->ml) && V.phat != V.p;
-  const int32_t *rperm = s->structured ? nullptr : s->perm;
-  const RestOut rop{rest_out ? V.phat : nullptr, rperm, s->nu}, ros{rest_out ? V.shat : nullptr, rperm, s->nu};
+  const RestOut rop = kr_rest_out(s, V, V.phat), ros = kr_rest_out(s, V, V.shat);
   const KrRed R = s->kr_red_used ? kr_red_vecs(s) : KrRed{};
   const int64_t nb = s->n_sell_rows;
+  const KrOperands o = kr_operands(phase, V, R);
+  const auto slot = [&](int k) { return k < o.dots ? slot_base(S, par, o.q[k]) : nullptr; };   // of o's k-th dot product
   switch (phase) {
-    case KR_BEGIN:
+    case KR_BEGIN: {
       PHX_HIP(hipMemsetAsync(S, 0, sizeof(double) * PHX_SCAL_DOUBLES, st));
-      {
-        DotPart dp{nullptr, nullptr};
-        PHX_CHECK(det_part(s, vec_grid(n).x, &dp));
-        const uint32_t *cm = s->kr_ident_used && !s->kr_red_used ? s->kr_cmask : nullptr;
+      const uint32_t *cm = s->kr_ident_used && !s->kr_red_used ? s->kr_cmask : nullptr;
+      PHX_CHECK(dot_pass(s, vec_grid(n).x, [&](dim3 grid, DotPart dp) {
         if (s->kr_red_used)
-          k_red_begin<<<vec_grid(n), block, 0, st>>>(n, s->perm, s->rhs, s->kr_cmask, V.b, R.u, S, dp);
+          k_red_begin<<<grid, block, 0, st>>>(n, s->perm, s->rhs, s->kr_cmask, V.b, R.u, S, dp);
         else
-          k_kr_begin<<<vec_grid(n), block, 0, st>>>(n, s->perm, s->rhs, s->own, V.b, V.r, V.rhat, V.p, V.y, S, rop, dp, cm);
-        PHX_CHECK(det_fold(s, slot_base(S, 0, R_RHO), cm ? slot_base(S, 0, R_RV) : nullptr));
-      }
+          k_kr_begin<<<grid, block, 0, st>>>(n, s->perm, s->rhs, s->own, V.b, V.r, V.rhat, V.p, V.y, S, rop, dp, cm);
+      }, slot_base(S, 0, R_RHO), cm ? slot_base(S, 0, R_RV) : nullptr));
       k_reduce_slots<<<1, 64, 0, st>>>(S, 0, R_RHO, 1, 1);
       if (mode) k_set_scalar<<<1, 1, 0, st>>>(S + R_OFF + R_RR, s->precond_veto ? 1.0 : 0.0);
       break;
+    }
     case KR_BEGIN2:
       k_kr_begin2<<<1, 1, 0, st>>>(S, mode);
       if (s->kr_red_used) {
@@ -2394,165 +2499,93 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
         PHX_CHECK(box_precond_apply(s, R.u, V.y));
         if (n > s->nu) PHX_HIP(hipMemcpyAsync(V.y + s->nu, R.u + s->nu, sizeof(double) * (size_t)(n - s->nu), hipMemcpyDeviceToDevice, st));
         PHX_CHECK(launch_spmv_stored(s, V.y, R.t, 0, nullptr, nullptr, nullptr, nullptr, nullptr, true));
-        DotPart dp{nullptr, nullptr};
-        PHX_CHECK(det_part(s, vec_grid(nb).x, &dp));
-        k_red_from<<<vec_grid(nb), block, 0, st>>>(nb, s->sell_rows, s->nu, V.b, R.t, R.r, R.rhat, R.p, R.ub, V.phat, S, dp);
-        PHX_CHECK(det_fold(s, slot_base(S, 0, R_RR), nullptr));
+        PHX_CHECK(dot_pass(s, vec_grid(nb).x, [&](dim3 grid, DotPart dp) {
+          k_red_from<<<grid, block, 0, st>>>(nb, s->sell_rows, s->nu, V.b, R.t, R.r, R.rhat, R.p, R.ub, V.phat, S, dp);
+        }, slot_base(S, 0, R_RR)));
         k_reduce_slots<<<1, 64, 0, st>>>(S, 0, R_RR, 1, 1);
         k_red_rho<<<1, 1, 0, st>>>(S, 0);
       }
       break;
-    case KR_SPMV_P:
+    case KR_SPMV_P: case KR_SPMV_S:   // v = A phat | t = A shat
       PHX_CHECK(prof_begin(s));
-      PHX_CHECK(launch_spmv(s, s->sell_val, V.phat, V.v, 1, V.rhat, slot_base(S, par, R_RV), nullptr));
+      PHX_CHECK(launch_spmv(s, s->sell_val, o.hat, o.out, o.dots, o.d0, slot(0), slot(1)));
       PHX_CHECK(prof_end(s));
-      if (mode) k_reduce_slots<<<1, 64, 0, st>>>(S, par, R_RV, 1, 1);
+      break;
+    case KR_SPMV_P_INNER: case KR_SPMV_S_INNER:
+      PHX_CHECK(prof_begin(s));
+      PHX_CHECK(launch_spmv(s, s->sell_val, o.hat, o.out, o.dots, o.d0, slot(0), slot(1), 1));
+      PHX_CHECK(prof_end(s));
+      break;
+    case KR_SPMV_P_HALO: case KR_SPMV_S_HALO:
+      PHX_CHECK(launch_spmv(s, s->sell_val, o.hat, o.out, o.dots, o.d0, slot(0), slot(1), 2));
       break;
     case KR_UPDATE_S:
       k_update_s<<<vec_grid(n), block, 0, st>>>(n, par, s->own, V.r, V.v, V.sv, S, ros);
       break;
-    case KR_SPMV_S:
-      PHX_CHECK(prof_begin(s));
-      PHX_CHECK(launch_spmv(s, s->sell_val, V.shat, V.t, 2, V.sv, slot_base(S, par, R_TS), slot_base(S, par, R_TT)));
-      PHX_CHECK(prof_end(s));
-      if (mode) k_reduce_slots<<<1, 64, 0, st>>>(S, par, R_TS, 2, 1);
-      break;
     case KR_UPDATE_XR:
-      {
-        DotPart dp{nullptr, nullptr};
-        PHX_CHECK(det_part(s, vec_grid(n).x, &dp));
-        k_update_xr<<<vec_grid(n), block, 0, st>>>(n, par, s->own, V.phat, V.shat, V.sv, V.t, V.rhat, V.y, V.r, S, dp);
-        PHX_CHECK(det_fold(s, slot_base(S, par, R_RHO), slot_base(S, par, R_RR)));
-      }
-      if (mode) k_reduce_slots<<<1, 64, 0, st>>>(S, par, R_RHO, 2, 1);
+      PHX_CHECK(dot_pass(s, vec_grid(n).x, [&](dim3 grid, DotPart dp) {
+        k_update_xr<<<grid, block, 0, st>>>(n, par, s->own, V.phat, V.shat, V.sv, V.t, V.rhat, V.y, V.r, S, dp);
+      }, slot(0), slot(1)));
       break;
     case KR_UPDATE_P:
       k_update_p<<<vec_grid(n), block, 0, st>>>(n, par, s->own, V.r, V.v, V.p, V.rhat, S, rop);
       break;
-    case KR_PRECOND_P:
-      if (s->ml) PHX_CHECK(ml_apply(s, V.p, V.phat));
-      else if (s->precond_state == 1) {
-        PHX_CHECK(box_precond_apply(s, V.p, V.phat, s->precond->dist ? 1 : 0));
-        if (s->cc && s->cc->p2) PHX_CHECK(coarse_apply_add(s, s->cc, V.p, V.phat));
-      } else if (s->bj) { PHX_CHECK(blockjac_apply(s, s->bj, V.p, V.phat)); PHX_CHECK(coarse_apply_add(s, s->cc, V.p, V.phat)); }
-      else if (s->u_unscaled && n > 0) k_jacobi_u<<<vec_grid(n), block, 0, st>>>(n, s->nu, s->perm, s->diag, V.p, V.phat);
+    case KR_PRECOND_P: case KR_PRECOND_S:   // phat = P p | shat = P s
+      PHX_CHECK(kr_precond_apply(s, o.in, o.hat, 0));
       break;
-    case KR_PRECOND_S:
-      if (s->ml) PHX_CHECK(ml_apply(s, V.sv, V.shat));
-      else if (s->precond_state == 1) {
-        PHX_CHECK(box_precond_apply(s, V.sv, V.shat, s->precond->dist ? 1 : 0));
-        if (s->cc && s->cc->p2) PHX_CHECK(coarse_apply_add(s, s->cc, V.sv, V.shat));
-      } else if (s->bj) { PHX_CHECK(blockjac_apply(s, s->bj, V.sv, V.shat)); PHX_CHECK(coarse_apply_add(s, s->cc, V.sv, V.shat)); }
-      else if (s->u_unscaled && n > 0) k_jacobi_u<<<vec_grid(n), block, 0, st>>>(n, s->nu, s->perm, s->diag, V.sv, V.shat);
+    case KR_EXACT_P: case KR_EXACT_S:
+      PHX_CHECK(kr_precond_apply(s, o.in, o.hat, 2));
       break;
-    case KR_CC_RESTRICT_P: if (s->cc) PHX_CHECK(coarse_restrict(s, s->cc, V.p)); break;
-    case KR_CC_ADD_P: if (s->cc) PHX_CHECK(coarse_apply_end(s, s->cc, V.phat)); break;
-    case KR_CC_RESTRICT_S: if (s->cc) PHX_CHECK(coarse_restrict(s, s->cc, V.sv)); break;
-    case KR_CC_ADD_S: if (s->cc) PHX_CHECK(coarse_apply_end(s, s->cc, V.shat)); break;
-    case KR_SPMV_P_INNER:
-      PHX_CHECK(prof_begin(s));
-      PHX_CHECK(launch_spmv(s, s->sell_val, V.phat, V.v, 1, V.rhat, slot_base(S, par, R_RV), nullptr, 1));
-      PHX_CHECK(prof_end(s));
-      break;
-    case KR_SPMV_P_HALO:
-      PHX_CHECK(launch_spmv(s, s->sell_val, V.phat, V.v, 1, V.rhat, slot_base(S, par, R_RV), nullptr, 2));
-      if (mode) k_reduce_slots<<<1, 64, 0, st>>>(S, par, R_RV, 1, 1);
-      break;
-    case KR_SPMV_S_INNER:
-      PHX_CHECK(prof_begin(s));
-      PHX_CHECK(launch_spmv(s, s->sell_val, V.shat, V.t, 2, V.sv, slot_base(S, par, R_TS), slot_base(S, par, R_TT), 1));
-      PHX_CHECK(prof_end(s));
-      break;
-    case KR_SPMV_S_HALO:
-      PHX_CHECK(launch_spmv(s, s->sell_val, V.shat, V.t, 2, V.sv, slot_base(S, par, R_TS), slot_base(S, par, R_TT), 2));
-      if (mode) k_reduce_slots<<<1, 64, 0, st>>>(S, par, R_TS, 2, 1);
-      break;
+    case KR_CC_RESTRICT_P: case KR_CC_RESTRICT_S: if (s->cc) PHX_CHECK(coarse_restrict(s, s->cc, o.in)); break;
+    case KR_CC_ADD_P: case KR_CC_ADD_S: if (s->cc) PHX_CHECK(coarse_apply_end(s, s->cc, o.hat)); break;
     case KR_TRUE_SPMV:
       PHX_CHECK(launch_spmv(s, s->sell_val, V.y, V.t, 0, nullptr, nullptr, nullptr));
       break;
     case KR_TRUE_RESIDUAL:
-      if (n > 0) {
-        DotPart dp{nullptr, nullptr};
-        PHX_CHECK(det_part(s, vec_grid(n).x, &dp));
-        k_true_residual<<<vec_grid(n), block, 0, st>>>(n, s->own, V.b, V.t, V.r, S, dp);
-        PHX_CHECK(det_fold(s, slot_base(S, 0, R_RR), nullptr));
-      }
+      if (n > 0)
+        PHX_CHECK(dot_pass(s, vec_grid(n).x, [&](dim3 grid, DotPart dp) {
+          k_true_residual<<<grid, block, 0, st>>>(n, s->own, V.b, V.t, V.r, S, dp);
+        }, slot_base(S, 0, R_RR)));
       k_reduce_slots<<<1, 64, 0, st>>>(S, 0, R_RR, 1, 1);
       break;
     case KR_RESTART:
       if (s->kr_ident_used) {   // (r, r) over the stencil rows = (rhat, A phat)_C of the next iteration, parity `par`
-        DotPart dp{nullptr, nullptr};
-        PHX_CHECK(det_part(s, vec_grid(n).x, &dp));
-        k_restart_from_r<<<vec_grid(n), block, 0, st>>>(n, V.r, V.rhat, V.p, S, rop, s->kr_cmask, par, dp);
-        PHX_CHECK(det_fold(s, slot_base(S, par, R_RV), nullptr));
+        PHX_CHECK(dot_pass(s, vec_grid(n).x, [&](dim3 grid, DotPart dp) {
+          k_restart_from_r<<<grid, block, 0, st>>>(n, V.r, V.rhat, V.p, S, rop, s->kr_cmask, par, dp);
+        }, slot_base(S, par, R_RV)));
       } else {
         k_restart_from_r<<<vec_grid(n), block, 0, st>>>(n, V.r, V.rhat, V.p, S, rop);
       }
       break;
     // --- identity loop (kr_identity; native loop only)
-    case KR_ID_SPMV_P:
+    case KR_ID_SPMV_P: case KR_ID_SPMV_S: case KR_RED_SPMV_P: case KR_RED_SPMV_S:   // on the stored rows
       PHX_CHECK(prof_begin(s));
-      PHX_CHECK(launch_spmv_stored(s, V.phat, V.v, 1, V.rhat, nullptr, slot_base(S, par, I_RV), nullptr, nullptr));
+      PHX_CHECK(launch_spmv_stored(s, o.hat, o.out, o.dots, o.d0, o.d1, slot(0), slot(1), slot(2), o.compact));
       PHX_CHECK(prof_end(s));
       break;
     case KR_ID_UPDATE_S:
-      {
-        DotPart dp{nullptr, nullptr};
-        PHX_CHECK(det_part(s, vec_grid(n).x, &dp));
-        k_ident_s<<<vec_grid(n), block, 0, st>>>(n, par, s->kr_cmask, V.r, V.v, V.p, V.rhat, V.sv, S, ros, dp);
-        PHX_CHECK(det_fold(s, slot_base(S, par, I_RS), slot_base(S, par, I_SS), slot_base(S, par, I_SS_C),
-                           slot_base(S, par, I_RS_C)));
-      }
-      break;
-    case KR_ID_SPMV_S:
-      PHX_CHECK(prof_begin(s));
-      PHX_CHECK(launch_spmv_stored(s, V.shat, V.t, 3, V.sv, V.rhat, slot_base(S, par, I_TS_B), slot_base(S, par, I_TT_B),
-                                   slot_base(S, par, I_RT_B)));
-      PHX_CHECK(prof_end(s));
+      PHX_CHECK(dot_pass(s, vec_grid(n).x, [&](dim3 grid, DotPart dp) {
+        k_ident_s<<<grid, block, 0, st>>>(n, par, s->kr_cmask, V.r, V.v, V.p, V.rhat, V.sv, S, ros, dp);
+      }, slot_base(S, par, I_RS), slot_base(S, par, I_SS), slot_base(S, par, I_SS_C), slot_base(S, par, I_RS_C)));
       break;
     case KR_ID_UPDATE_XRP:
-      {
-        DotPart dp{nullptr, nullptr};
-        PHX_CHECK(det_part(s, vec_grid(n).x, &dp));
-        k_ident_xrp<<<vec_grid(n), block, 0, st>>>(n, par, s->kr_cmask, V.phat, V.shat, V.sv, V.t, V.v, V.rhat, V.y, V.r, V.p,
-                                                   S, rop, dp);
-        PHX_CHECK(det_fold(s, slot_base(S, par, I_RR), slot_base(S, par ^ 1, I_RV), nullptr, nullptr, 1));
-      }
+      PHX_CHECK(dot_pass(s, vec_grid(n).x, [&](dim3 grid, DotPart dp) {
+        k_ident_xrp<<<grid, block, 0, st>>>(n, par, s->kr_cmask, V.phat, V.shat, V.sv, V.t, V.v, V.rhat, V.y, V.r, V.p, S, rop, dp);
+      }, slot_base(S, par, I_RR), slot_base(S, par ^ 1, I_RV), nullptr, nullptr, 1));
       break;
-    // --- reduced loop (kr_reduced; native loop only)
-    case KR_RED_PRECOND_P:
-      PHX_CHECK(box_precond_apply_red(s, R.p, V.phat));
-      break;
-    case KR_RED_SPMV_P:
-      PHX_CHECK(prof_begin(s));
-      PHX_CHECK(launch_spmv_stored(s, V.phat, R.v, 1, R.rhat, nullptr, slot_base(S, par, I_RV), nullptr, nullptr, true));
-      PHX_CHECK(prof_end(s));
+    // --- reduced loop (kr_reduced; native loop only; its SpMVs are with those of the identity loop)
+    case KR_RED_PRECOND_P: case KR_RED_PRECOND_S:
+      PHX_CHECK(box_precond_apply_red(s, o.in, o.hat));
       break;
     case KR_RED_UPDATE_S:
-      {
-        DotPart dp{nullptr, nullptr};
-        PHX_CHECK(det_part(s, vec_grid(nb).x, &dp));
-        k_red_s<<<vec_grid(nb), block, 0, st>>>(nb, par, s->sell_rows, s->nu, R.r, R.v, R.rhat, R.sv, V.shat, S, dp);
-        PHX_CHECK(det_fold(s, slot_base(S, par, I_RS), slot_base(S, par, I_SS)));
-      }
-      break;
-    case KR_RED_PRECOND_S:
-      PHX_CHECK(box_precond_apply_red(s, R.sv, V.shat));
-      break;
-    case KR_RED_SPMV_S:
-      PHX_CHECK(prof_begin(s));
-      PHX_CHECK(launch_spmv_stored(s, V.shat, R.t, 3, R.sv, R.rhat, slot_base(S, par, I_TS_B), slot_base(S, par, I_TT_B),
-                                   slot_base(S, par, I_RT_B), true));
-      PHX_CHECK(prof_end(s));
+      PHX_CHECK(dot_pass(s, vec_grid(nb).x, [&](dim3 grid, DotPart dp) {
+        k_red_s<<<grid, block, 0, st>>>(nb, par, s->sell_rows, s->nu, R.r, R.v, R.rhat, R.sv, V.shat, S, dp);
+      }, slot_base(S, par, I_RS), slot_base(S, par, I_SS)));
       break;
     case KR_RED_UPDATE_XRP:
-      {
-        DotPart dp{nullptr, nullptr};
-        PHX_CHECK(det_part(s, vec_grid(nb).x, &dp));
-        k_red_xrp<<<vec_grid(nb), block, 0, st>>>(nb, par, s->sell_rows, s->nu, R.sv, R.t, R.v, R.rhat, R.ub, R.r, R.p, V.phat,
-                                                  S, dp);
-        PHX_CHECK(det_fold(s, slot_base(S, par, I_RR), nullptr));
-      }
+      PHX_CHECK(dot_pass(s, vec_grid(nb).x, [&](dim3 grid, DotPart dp) {
+        k_red_xrp<<<grid, block, 0, st>>>(nb, par, s->sell_rows, s->nu, R.sv, R.t, R.v, R.rhat, R.ub, R.r, R.p, V.phat, S, dp);
+      }, slot_base(S, par, I_RR)));
       break;
     case KR_RED_FORM_X:
       k_red_put_u<<<vec_grid(nb), block, 0, st>>>(nb, s->sell_rows, R.ub, R.u);
@@ -2561,25 +2594,18 @@ static int kr_phase(phx_system *s, int phase, int mode, int par) {
       break;
     case KR_RED_RESTART:
       k_red_add_c<<<vec_grid(n), block, 0, st>>>(n, s->kr_cmask, V.r, R.u);
-      {
-        DotPart dp{nullptr, nullptr};
-        PHX_CHECK(det_part(s, vec_grid(nb).x, &dp));
-        k_red_from<<<vec_grid(nb), block, 0, st>>>(nb, s->sell_rows, s->nu, V.r, nullptr, R.r, R.rhat, R.p, nullptr, V.phat, S, dp);
-        PHX_CHECK(det_fold(s, slot_base(S, 0, R_RR), nullptr));
-      }
+      PHX_CHECK(dot_pass(s, vec_grid(nb).x, [&](dim3 grid, DotPart dp) {
+        k_red_from<<<grid, block, 0, st>>>(nb, s->sell_rows, s->nu, V.r, nullptr, R.r, R.rhat, R.p, nullptr, V.phat, S, dp);
+      }, slot_base(S, 0, R_RR)));
       k_reduce_slots<<<1, 64, 0, st>>>(S, 0, R_RR, 1, 1);
       k_red_rho<<<1, 1, 0, st>>>(S, 1);
-      break;
-    case KR_EXACT_P:
-      if (s->precond_state == 1 && s->precond->dist) PHX_CHECK(box_precond_apply(s, V.p, V.phat, 2));
-      break;
-    case KR_EXACT_S:
-      if (s->precond_state == 1 && s->precond->dist) PHX_CHECK(box_precond_apply(s, V.sv, V.shat, 2));
       break;
     default:
       phx_set_error("unknown Krylov phase %d", phase);
       return PHX_ERR_VALUE;
   }
+  // mode 1: the dot products of the phase, folded into R for the driver's all-reduce
+  if (mode && o.nfold > 0) k_reduce_slots<<<1, 64, 0, st>>>(S, par, o.fold0, o.nfold, 1);
   PHX_HIP(hipGetLastError());
   return PHX_OK;
 }
@@ -2616,7 +2642,7 @@ extern "C" int phx_krylov_finish(phx_system *s, double *x_out, int loc) {
 // the vectors a multi-GPU driver must halo-exchange instead of p / s)
 extern "C" int phx_krylov_precond_active(const phx_system *s, int *active) {
   // 1: the SpMV inputs are phat / shat (box preconditioner, or the u-block Jacobi of a structured system)
-  *active = (s->precond_state == 1 || s->u_unscaled || s->bj || s->ml) ? 1 : 0;
+  *active = kr_hats_apart(s) ? 1 : 0;
   return PHX_OK;
 }
 
@@ -2688,14 +2714,15 @@ extern "C" int phx_krylov_profile(phx_system *s, int reset, double *avg_seconds,
 //           sampled average seconds of a y-pass launch, launches sampled, bytes per lattice value (4 / 8)}
 extern "C" int phx_precond_info(phx_system *s, double *out) {
   for (int i = 0; i < 8; ++i) out[i] = 0.0;
-  if (s->bj) out[0] = s->cc ? 3.0 : 2.0;   // dense vertex blocks (interface elasticity), 3: with the coarse correction
   if (s->cc) { out[1] = (double)s->cc->ratio; out[4] = (double)s->cc->nc; }
-  if (s->ml) {   // 5: multilevel: {levels, n_0, coarse kind, sum of the level sizes}
+  const KrPrecond kind = kr_precond_kind(s);
+  if (kind == KR_PC_VBLOCKS) out[0] = s->cc ? 3.0 : 2.0;   // dense vertex blocks (interface elasticity), 3: with the coarse correction
+  if (kind == KR_PC_MULTILEVEL) {   // 5: multilevel: {levels, n_0, coarse kind, sum of the level sizes}
     out[0] = 5.0; out[1] = (double)s->ml->lv.size(); out[2] = (double)s->ml->lv[0].nv; out[3] = (double)s->ml->coarse_kind;
     out[4] = (double)s->ml->points; out[7] = 8.0;
     return PHX_OK;
   }
-  if (s->precond_state != 1) return PHX_OK;
+  if (kind != KR_PC_BOX) return PHX_OK;
   const BoxGrid &g = s->precond->g;
   out[0] = s->cc && s->cc->p2 ? 4.0 : 1.0;   // 4: with the P2 coarse correction
   for (int a = 0; a < 3; ++a) out[1 + a] = (double)g.L[a];
@@ -2761,7 +2788,7 @@ static int kr_drive(phx_system *s, const KrDist *d, double rtol, int64_t max_ite
   const KrVecs V = kr_vecs(s);
   const bool ident = s->kr_ident_used;   // decided by phase 0 (kr_identity; never in mode 1)
   const bool red = s->kr_red_used;       // kr_reduced (only with ident)
-  const bool pc = d ? d->pc_all : (s->precond_state == 1 || s->ml);
+  const bool pc = d ? d->pc_all : kr_precond_on_u_block(s);
   const double bb = s->scal_h[S_BB];
   auto read_head = [&](const char *what) -> int {
     PHX_HIP(hipMemcpyAsync(s->scal_h, S, sizeof(double) * 16, hipMemcpyDeviceToHost, st));

@@ -41,6 +41,7 @@ pytestmark = pytest.mark.gpu
 
 EPS = np.finfo(np.float64).eps
 VEC_GRID_ROWS = 2048 * 256          # vec_grid: at most 2048 blocks of 256 threads
+UNASSIGNED_PHASES = (-1, 14, 19, 22, 29, 34, 39, 42, 51, 64)   # next to every run of assigned numbers of KrPhase
 
 
 @pytest.fixture(scope="module")
@@ -372,7 +373,9 @@ def test_grid_stride_of_the_vector_kernels(P):
 
 def test_identity_and_reduced_phases_are_refused(P):
     """Phases 52 - 55 need the identity loop and 56 - 63 the reduced loop of a native solve; the phase API never puts
-    them in force (kr_cmask and kr_red are not built), so it answers PHX_ERR_VALUE before any launch."""
+    them in force (kr_cmask and kr_red are not built), so it answers PHX_ERR_VALUE before any launch.  So does every
+    number between the assigned phases (the holes of KrPhase), below the first and above the last: "unknown Krylov
+    phase", with the workspace and the scalars left as they were."""
     ap, rest, ex = open_case(P, "box_p1_lattice", "all")
     L = ap.b.L
     before = ap.read()
@@ -383,3 +386,12 @@ def test_identity_and_reduced_phases_are_refused(P):
             L.check(rc)
     after = ap.read()
     assert all(same_bits(before[k], after[k]) for k in K.NAMES)
+    scal = ap.scal.cpu().numpy().copy()
+    for phase in UNASSIGNED_PHASES:
+        rc = L.lib.phx_krylov_phase(ap.b.sys, phase)
+        assert rc == L.ERR_VALUE, (phase, rc)
+        with pytest.raises(ValueError, match=f"unknown Krylov phase {phase}$"):
+            L.check(rc)
+    after = ap.read()
+    assert all(same_bits(before[k], after[k]) for k in K.NAMES)
+    assert same_bits(scal, ap.scal.cpu().numpy())
