@@ -2,7 +2,7 @@
 """Linear elasticity on a level-set domain with the displacement prescribed on {phi = 0}: `phifem_amd.ElasticitySolver`.
 
     python main.py {bg,sub} [--dim 2|3] [--cubes N] [--levels K] [--adapt] [--repeat R] [--compare-interface]
-                            [--skip-errors]
+                            [--skip-errors] [--coarse R]
 
 Unit circle / sphere in [-1.5, 1.5]^d, E = 1, nu = 0.3, manufactured solution
     2-D: u = (sin x cos y, cos(x + y/2)),    3-D: u = (sin x cos y cos z, cos(x + y/2) sin z, sin(x - z) cos y),
@@ -13,7 +13,12 @@ background mesh -- uniformly, or with --adapt the cells `mark_dorfler` selects f
 active DoFs, BiCGStab iterations, relative L2 / H1_0 errors of u_h on Omega_h (`cell_errors`), then the slopes fitted
 over the levels, and the tag / assemble / solve times of the last call (`mesh.timings()`: device events on the mesh's
 stream; --repeat 2 reports the second, warm call).  --compare-interface also times `InterfaceElasticitySolver.assemble`
-on the same mesh (27 / 14 blocks, one workgroup per element): a point of comparison, not the same problem."""
+on the same mesh (27 / 14 blocks, one workgroup per element): a point of comparison, not the same problem.
+--coarse R (0: off, -1: automatic, >= 5: H / h) adds the Galerkin coarse space of `ElasticitySolver(coarse=R)` to the
+vertex blocks wherever the level is a generated box lattice solved in box mode: level 0, and the uniformly refined levels,
+which are then generated as boxes of N 2^level cubes instead of being refined.  Adapted levels and sub-meshes keep the
+vertex blocks alone, and say so.  The line of a level names the preconditioner, the coarse DoFs and the seconds of the
+coarse build (paid once per system, inside its first solve)."""
 import argparse
 import os
 import sys
@@ -62,6 +67,7 @@ def main():
     ap.add_argument("--repeat", type=int, default=1, help="assemble + solve this many times, report the last")
     ap.add_argument("--compare-interface", action="store_true")
     ap.add_argument("--skip-errors", action="store_true", help="no cell_errors (timing runs at large sizes)")
+    ap.add_argument("--coarse", type=int, default=0, help="coarse space: 0 off, -1 automatic, >= 5 the ratio H / h")
     args = ap.parse_args()
     d = args.dim
     exact, source = manufactured(d)
@@ -79,10 +85,13 @@ def main():
         t_tag = bg.timings()
         work = bg if args.mesh_type == "bg" else sub
         x = work.x
-        solver = P.ElasticitySolver(work, E=E, nu=NU)
+        lattice = args.mesh_type == "bg" and (lv == 0 or not args.adapt)
+        solver = P.ElasticitySolver(work, E=E, nu=NU, coarse=args.coarse if lattice else 0)
+        builds = []
         for _ in range(max(args.repeat, 1)):
             info = solver.assemble(levelset(x), source(x.T).T, exact(x.T).T)
             w = solver.solve(rtol=1e-8, max_iter=500000)
+            builds.append(solver.stats.get("coarse_build_s", 0.0))
         u, _ = solver.split(w)
         u = np.ascontiguousarray(u)
         tags = work.cell_tag_values()
@@ -96,6 +105,12 @@ def main():
         print(f"level {lv}: {bg.nc} background cells, {info['n_active']} active DoFs, nnz {info['nnz']}, "
               f"{st['iterations']} iterations ({st['precond']}, relres {st['relres']:.1e}), "
               f"L2 {e['l2_relative']:.3e}  H10 {e['h10_relative']:.3e}")
+        if args.coarse != 0 and not lattice:
+            print("         no coarse space on this level: an adapted level or a sub-mesh is no box lattice")
+        elif args.coarse != 0:
+            why = f" -- not built: {st['coarse_reason']}" if st["coarse_reason"] else ""
+            print(f"         coarse space: H = {st['coarse_ratio']} h, {st['coarse_dofs']} coarse DoFs, build "
+                  f"{1e3 * builds[-1]:.3f} ms (host clock, inside the solve of that call){why}")
         print(f"         tag cells {1e3 * t_tag['tag_cells']:.3f} ms, tag facets {1e3 * t_tag['tag_facets']:.3f} ms, "
               f"assemble {1e3 * t['assemble']:.3f} ms, solve {1e3 * t['solve']:.3f} ms "
               f"(slot capacity {info['slot_capacity']})")
@@ -123,6 +138,8 @@ def main():
             print(f"         eta_zz = {np.sqrt(eta2.sum()):.4e}, marked {int(marked.sum())} cells -> "
                   f"{fine.refine_info[0]} edges in {fine.refine_info[1]} sweeps")
             bg = fine
+        elif args.coarse != 0:      # the same lattice as a generated box: the coarse space is built on those
+            bg = P.create_box([-1.5] * d, [1.5] * d, [args.cubes * 2 ** (lv + 1)] * d)
         else:
             bg = P.refine(bg)
     if len(rows) > 1:

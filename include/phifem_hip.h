@@ -237,6 +237,15 @@ enum phx_option {
                                quadrilaterals) are solved as without the option; a P1 weak-Dirichlet system that
                                cannot be served (no living parent, Kuhn box, sub-mesh, slab, ...) fails its solve
                                with the status phx_multilevel_setup reports.  0 (default): off, nothing changes  */
+  PHX_OPT_ELWD_COARSE = 15, /* coarse-space correction of the weak-Dirichlet elasticity solve
+                               (phx_assemble_elasticity_wd) on generated simplicial boxes, 2-D and 3-D, one rank: the
+                               Galerkin problem of PHX_OPT_EL_COARSE on multilinear functions of spacing H = value * h,
+                               one set per displacement component u_a (the p blocks have no coarse part), added to the
+                               vertex-block Jacobi.  0 (default): off, vertex blocks alone; -1: automatic (ratio and
+                               on/off chosen by the library); >= 5: this ratio; 1..4: PHX_ERR_VALUE.  Read
+                               when a system is assembled (0: that system never builds one) and on its first solve;
+                               phx_coarse_info reports the correction or why it was not built.  Independent of
+                               PHX_OPT_EL_COARSE, which speaks of interface-elasticity systems only             */
   PHX_OPT_ALLOW_EMPTY = 6, /* 1: phx_assemble_poisson_wd returns an EMPTY system (n_active = 0) when no cell
                                is tagged 1 / 2 instead of PHX_ERR_VALUE: a slab of a partitioned box that
                                does not touch the domain still joins every collective of the solve          */

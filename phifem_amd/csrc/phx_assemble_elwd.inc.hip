@@ -289,7 +289,8 @@ static int assemble_elwd_with_capacity(phx_mesh *m, const double *params, const 
   phx_system *s = sys.s;
   Slots &sl = sys.sl;
   s->el_nblk = 2 * D;     // phx_solve: vertex-block Jacobi over the (u, p) DoFs of a vertex
-  s->cc_tried = true;     // no coarse space for this layout (PHX_OPT_EL_COARSE belongs to the interface system)
+  s->cc_layout = phx_system::PHX_CC_LAYOUT_ELWD;   // coarse functions on the d blocks u_a (phx_coarse.inc.hip)
+  s->cc_tried = m->elwd_coarse == 0;               // PHX_OPT_ELWD_COARSE off while assembling: vertex blocks only, for good
   const dim3 block(256);
   ElwdArgs A;
   memset(&A, 0, sizeof(A));

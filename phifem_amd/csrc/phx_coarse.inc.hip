@@ -18,6 +18,26 @@
 // Partitioned boxes (native RCCL loop, phx_dist.inc.hip): the coarse lattice is the one of the GLOBAL box; every rank
 // restricts its owned rows, the coarse right-hand side is all-reduced (a few thousand doubles per application), every
 // rank holds Ac^-1 (its own rows' share of Ac summed over the ranks once per system) and prolongs onto its owned rows.
+//
+// Weak-Dirichlet elasticity (phx_assemble_elwd.inc.hip, PHX_OPT_ELWD_COARSE; one rank): the same build with the layout
+// PHX_CC_LAYOUT_ELWD -- u_a sits in block a, so d blocks carry coarse functions instead of 2 d, the p blocks have no
+// coarse part, and no row is a Dirichlet row (the condition is weak: every active u row is eligible).  CPU prototype
+// on the numpy specification (tools/experiments/elasticity_wd_coarse.py): 339 -> 78 iterations at 128^2 with H = 8h,
+// 312 -> 136 at 32^3 with H = 8h, 326 -> 122 at 16^3 with H = 5h.
+//   * Probing colours.  Only the u-u part of A enters Ac (R vanishes on p).  It couples two vertices when they share a
+//     cell -- at most 1 lattice step apart per axis: a Kuhn simplex lies in one cube -- or when they belong to the
+//     macro-element of a ghost-penalty facet pair, the D + 2 vertices of two cells that share a facet: the two cells
+//     may lie in neighbouring cubes, the two vertices opposite the facet are then 2 steps apart along one axis.  The
+//     reach is 2 steps per axis, that of the interface operator.  With H = r h the hat of node c covers
+//     |i - r c| <= r - 1 and its image under A |i - r c| <= r + 1.  Same-colour nodes are 3 r apart: the images are
+//     disjoint when 2 (r + 1) < 3 r, r >= 3.  The split of cc_part (half a coarse cell beyond the node of the test
+//     function) separates the images of nodes c - 1 and c + 2 when r c + 1 < r c + r / 2 and r (c + 1) - 1 >= r c + r / 2,
+//     r >= 3 again; a test function (support r - 1) meets images of nodes at most 2 cells away, which the eight parts
+//     cover.  The option takes r >= 5 as PHX_OPT_EL_COARSE does: the minimum is not raised.
+//   * The build ends with a check (the interface build has none): for one vector x of the coarse space,
+//     Ac^-1 (R^T A R x) through the solver's operator and the passes below must give x back; if not -- a colour
+//     argument broken by another operator, an inverse ruined by its condition -- the correction is dropped, with
+//     s->cc_reason and a line on stderr, never applied wrong.
 #include <chrono>
 #include <functional>
 
@@ -59,9 +79,10 @@ static void coarse_free(phx_coarse *c) {
 void phx_coarse_destroy(phx_coarse *c) { coarse_free(c); }
 
 // ---- set-up kernels ---------------------------------------------------------------------------------------------
-// eligible fine DoFs: active rows of the displacement blocks that are not Dirichlet rows (a constrained u_in row is the
-// unit row `1 * u = u_D`: a single entry on the diagonal)
-__global__ void k_cc_positions(int64_t n, int64_t nv, int nblk_u, int d, const int64_t *__restrict__ full_of_active,
+// eligible fine DoFs: active rows of the displacement blocks that are not Dirichlet rows (interface layout: a
+// constrained u_in row, blocks [0, dir_blocks), is the unit row `1 * u = u_D`: a single entry on the diagonal; the
+// weak-Dirichlet layout has no such rows, dir_blocks = 0)
+__global__ void k_cc_positions(int64_t n, int64_t nv, int nblk_u, int dir_blocks, const int64_t *__restrict__ full_of_active,
                                const int64_t *__restrict__ rowptr, const int32_t *__restrict__ iperm,
                                const double *__restrict__ diag, const uint8_t *__restrict__ own, int32_t *__restrict__ cpos,
                                double *__restrict__ dpos) {
@@ -73,7 +94,7 @@ __global__ void k_cc_positions(int64_t n, int64_t nv, int nblk_u, int d, const i
   const int64_t f = full_of_active[r];
   const int blk = (int)(f / nv);
   if (blk >= nblk_u) return;
-  if (blk < d && rowptr[r + 1] - rowptr[r] == 1) return;
+  if (blk < dir_blocks && rowptr[r + 1] - rowptr[r] == 1) return;
   cpos[f] = pos;
 }
 
@@ -629,71 +650,130 @@ __global__ void k_cc_flags_to_f64(int64_t n, const uint8_t *__restrict__ f, doub
 // Builds the coarse correction of `s` (*out = nullptr when it does not apply: not a generated box, rocSOLVER missing,
 // a singular coarse matrix, PHX_OPT_EL_COARSE = 0).  `reduce` (partitioned boxes): in-place sum of a device buffer of
 // doubles over the ranks, enqueued on the solver stream -- EVERY rank then walks the same sequence of reductions
-// (a veto of one rank switches the correction off on all of them).
+// (a veto of one rank switches the correction off on all of them).  The layout of the system (s->cc_layout) says which
+// blocks carry coarse functions and whose option is read; a weak-Dirichlet elasticity system (one rank only) also
+// leaves in s->cc_reason why nothing was built (PHX_CC_*, as p2_coarse_build does).
 typedef std::function<int(double *, size_t)> CcReduce;
+enum { PHX_CC_NOT_BOX = 1, PHX_CC_SMALL_BOX = 2, PHX_CC_TOO_MANY = 3, PHX_CC_SINGULAR = 4, PHX_CC_CHECK = 5,
+       PHX_CC_AUTO_OFF = 6 };
+// Automatic choice of PHX_OPT_ELWD_COARSE = -1.  Measured on one MI355X with demo/elasticity/main.py (unit sphere,
+// second call, device events; "solve" contains the build, which every new system pays once; DESIGN.md 7h has the table).
+//   * Ratio: the smallest H / h >= 5 whose compact coarse space has at most PHX_ELWD_AUTO_NC_CAP DoFs.  The cap is the
+//     count that minimises build + solve at 256^3 among those measured there -- 1 467 DoFs (H = 24 h): 688 ms, 2 235
+//     (20 h): 593 ms, 3 879 (16 h): 599 ms, 7 770 (12 h): 682 ms, against 1 123 - 1 208 ms on the vertex blocks alone -- so
+//     2 500 admits the second and not the third.  The same count is the best measured at 160^3 (2 559 DoFs, 12 h: 224 ms;
+//     3 879: 226; 6 615: 293; 13 833: 863): beyond a few thousand DoFs the dense inverse and the two gemvs per
+//     iteration cost more than the iterations they save.
+//   * Size: on from PHX_ELWD_AUTO_MIN_N_3D / _2D cubes along the longest axis, the smallest size measured at which
+//     build + solve with the correction beats the solve on the vertex blocks alone by more than the spread of two runs of
+//     the latter (3-D: 4 % at 256^3, 6 % at 128^3; 2-D: 20 % at 256^2).  3-D: 96^3 57 ms plain, 63 - 145 with; 128^3
+//     106 - 112 plain, 124 - 251 with: the build (28 - 167 ms) eats what the iterations save; 160^3 315 -> 224.  2-D:
+//     128^2 13.7 -> 11.1 and 256^2 30.1 - 36.6 -> 17.4 - 26.9 ms are inside or at the spread; 512^2 86 -> 23 - 46 ms.
+//     Sizes between the measured ones were not run: the mode stays off there.
+#define PHX_ELWD_AUTO_NC_CAP 2500
+#define PHX_ELWD_AUTO_MIN_N_3D 160
+#define PHX_ELWD_AUTO_MIN_N_2D 512
 static int coarse_build(phx_system *s, int nblk, phx_coarse **out, const CcReduce *reduce = nullptr) {
   *out = nullptr;
   phx_mesh *m = s->mesh;
   hipStream_t st = m->stream;
-  const int req = m->el_coarse;   // PHX_OPT_EL_COARSE: -1 automatic, 0 off, > 0 the ratio H / h
-  // decided from numbers every rank shares
-  if (req == 0 || !m->is_box || m->is_submesh) return PHX_OK;
-  if (!reduce && (!s->rowptr || s->n == 0)) return PHX_OK;
+  // the layout: which blocks carry coarse functions, which of them hold Dirichlet rows, whose option it is.  The
+  // weak-Dirichlet system says why nothing was built (s->cc_reason); the interface system stays silent, as it was
+  const bool wd = s->cc_layout == phx_system::PHX_CC_LAYOUT_ELWD;
   const int d = m->gdim;
+  const int nblk_u = wd ? d : 2 * d, dir_blocks = wd ? 0 : d;
+  const int req = wd ? m->elwd_coarse : m->el_coarse;   // -1 automatic, 0 off, > 0 the ratio H / h
+  auto why = [&](int reason) -> int { if (wd) s->cc_reason = reason; return PHX_OK; };
+  (void)why(0);
+  // decided from numbers every rank shares
+  if (req == 0) return PHX_OK;
+  if (!m->is_box || m->is_submesh || (wd && (reduce || s->own))) return why(PHX_CC_NOT_BOX);
+  if (!reduce && (!s->rowptr || s->n == 0)) return why(PHX_CC_NOT_BOX);
   int64_t nglob[3];
   for (int a = 0; a < 3; ++a) nglob[a] = a < d ? (m->box_nglob[a] > 0 ? m->box_nglob[a] : m->box_n[a]) : 1;
   const int64_t nmax = std::max(nglob[0], std::max(nglob[1], nglob[2]));
-  // automatic: the probing passes and the inverse cost about as much as 50-100 iterations of the plain loop, which is
-  // what the correction saves from ~64 cubes per axis on (48^3: 176 -> 88 iterations but 52 -> 73 ms)
-  if (req < 0 && nmax < 80) return PHX_OK;
-  // coarse cells per axis: 8 up to 128 cubes (~3 000 coarse DoFs: the dense inverse takes 30 ms), growing to 13 at 256
-  // (~10 000: 0.25 s) -- measured at 256^3: H = 16 h 104 iterations / 2.9 s, 20 h 112 / 2.3 s, 24 h 152 / 2.7 s
-  const double cells = 8.0 + (nmax > 128 ? (double)(nmax - 128) / 25.0 : 0.0);
-  int ratio = req > 0 ? req : (int)ceil((double)nmax / cells);
-  if (ratio < 5) ratio = 5;   // the split of the probing passes needs H > 4 h
-  if (nmax < 2 * ratio) return PHX_OK;   // nothing coarser than the mesh itself
+  int ratio;
+  if (wd) {
+    if (req < 0 && nmax < (d == 3 ? PHX_ELWD_AUTO_MIN_N_3D : PHX_ELWD_AUTO_MIN_N_2D)) return why(PHX_CC_AUTO_OFF);
+    ratio = req > 0 ? req : 5;   // automatic: raised below until the compact space fits the cap
+  } else {
+    // automatic: the probing passes and the inverse cost about as much as 50-100 iterations of the plain loop, which is
+    // what the correction saves from ~64 cubes per axis on (48^3: 176 -> 88 iterations but 52 -> 73 ms)
+    if (req < 0 && nmax < 80) return PHX_OK;
+    // coarse cells per axis: 8 up to 128 cubes (~3 000 coarse DoFs: the dense inverse takes 30 ms), growing to 13 at 256
+    // (~10 000: 0.25 s) -- measured at 256^3: H = 16 h 104 iterations / 2.9 s, 20 h 112 / 2.3 s, 24 h 152 / 2.7 s
+    const double cells = 8.0 + (nmax > 128 ? (double)(nmax - 128) / 25.0 : 0.0);
+    ratio = req > 0 ? req : (int)ceil((double)nmax / cells);
+    if (ratio < 5) ratio = 5;   // the split of the probing passes needs H > 4 h
+  }
+  if (nmax < 2 * ratio) return why(req > 0 ? PHX_CC_SMALL_BOX : PHX_CC_AUTO_OFF);   // nothing coarser than the mesh itself
   // from here on a partitioned box must reach the veto reduction on every rank
   bool veto = false;
   phx_coarse *c = new phx_coarse();
   auto fail = [&](int code) { coarse_free(c); return code; };
-  c->d = d; c->nblk_u = 2 * d; c->ratio = ratio; c->ratio_h = ratio; c->dist = reduce != nullptr;
-  c->M = 1;
+  // weak-Dirichlet layout: a failed allocation leaves the system on the vertex blocks (said, nothing kept)
+  auto no_memory = [&]() -> int {
+    (void)hipGetLastError();
+    coarse_free(c);
+    if (!wd) return (int)PHX_ERR_HIP;
+    fprintf(stderr, "phifem_hip: no device memory for the coarse correction of the elasticity solve: it keeps the vertex blocks alone\n");
+    return why(PHX_CC_TOO_MANY);
+  };
+  c->d = d; c->nblk_u = nblk_u; c->dist = reduce != nullptr;
   for (int a = 0; a < 3; ++a) {
     c->nf[a] = a < d ? m->box_n[a] + 1 : 1;
     c->off[a] = a < d ? (int)m->box_off[a] : 0;
-    c->m[a] = a < d ? (int)phx_div_up(nglob[a], ratio) + 1 : 1;
-    c->M *= c->m[a];
   }
-  const CcDims g{{c->nf[0], c->nf[1], c->nf[2]}, {c->m[0], c->m[1], c->m[2]}, c->ratio, c->M, {c->off[0], c->off[1], c->off[2]}};
   const int64_t nv = m->nv, n = s->n, nb = c->nblk_u, tf = nb * nv;
   const bool rows = n > 0 && s->rowptr;   // false: a slab outside the domain, it only joins the reductions
   if (n > 0 && (!s->rowptr || !s->bj)) veto = true;   // without the vertex blocks phat aliases p: nothing to add a correction to
-  if (phx_malloc(&c->cpos, sizeof(int32_t) * (size_t)tf) != hipSuccess || phx_malloc(&c->dpos, sizeof(double) * (size_t)std::max<int64_t>(n, 1)) != hipSuccess ||
-      phx_malloc(&c->cmap, sizeof(int32_t) * (size_t)(nb * c->M)) != hipSuccess)
-    return fail(PHX_ERR_HIP);
+  if (phx_malloc(&c->cpos, sizeof(int32_t) * (size_t)tf) != hipSuccess || phx_malloc(&c->dpos, sizeof(double) * (size_t)std::max<int64_t>(n, 1)) != hipSuccess)
+    return no_memory();
   PHX_HIP(hipMemsetAsync(c->cpos, 0xff, sizeof(int32_t) * (size_t)tf, st));
-  if (rows) k_cc_positions<<<cc_grid(n), dim3(256), 0, st>>>(n, nv, c->nblk_u, d, s->full_of_active, s->rowptr, s->iperm, s->diag, s->own, c->cpos, c->dpos);
-  uint8_t *used = nullptr;
-  double *usedf = nullptr;
-  if (phx_malloc(&used, (size_t)(nb * c->M)) != hipSuccess || phx_malloc(&usedf, sizeof(double) * (size_t)(nb * c->M)) != hipSuccess) {
+  if (rows) k_cc_positions<<<cc_grid(n), dim3(256), 0, st>>>(n, nv, c->nblk_u, dir_blocks, s->full_of_active, s->rowptr, s->iperm, s->diag, s->own, c->cpos, c->dpos);
+  // the compact coarse space of the ratio; the automatic weak-Dirichlet choice counts it per candidate ratio (as
+  // p2c_count_used does) and takes the first that fits its cap
+  // coarse DoFs the dense inverse is asked to take.  It stages 20 480 rows at most (phx_dense.inc.hip): between that and
+  // 24 000 the interface build ends in its PHX_ERR_VALUE; the weak-Dirichlet build stops at the inverse's own limit and
+  // gives the reason instead (measured: 256^3 with H = 8 h, 22 131 coarse DoFs)
+  const int nc_max = wd ? 20000 : 24000;
+  std::vector<int32_t> hmap, hnode;
+  for (;; ++ratio) {
+    if (nmax < 2 * ratio) { coarse_free(c); return why(PHX_CC_TOO_MANY); }   // (automatic weak-Dirichlet choice only)
+    c->ratio = ratio; c->ratio_h = ratio;
+    c->M = 1;
+    for (int a = 0; a < 3; ++a) {
+      c->m[a] = a < d ? (int)phx_div_up(nglob[a], ratio) + 1 : 1;
+      c->M *= c->m[a];
+    }
+    const CcDims gr{{c->nf[0], c->nf[1], c->nf[2]}, {c->m[0], c->m[1], c->m[2]}, c->ratio, c->M, {c->off[0], c->off[1], c->off[2]}};
+    uint8_t *used = nullptr;
+    double *usedf = nullptr;
+    if (phx_malloc(&used, (size_t)(nb * c->M)) != hipSuccess || phx_malloc(&usedf, sizeof(double) * (size_t)(nb * c->M)) != hipSuccess) {
+      (void)phx_free(used); (void)phx_free(usedf);
+      return no_memory();
+    }
+    int rrc = hipMemsetAsync(used, 0, (size_t)(nb * c->M), st) == hipSuccess ? PHX_OK : PHX_ERR_HIP;
+    if (rrc == PHX_OK) {
+      k_cc_used<<<cc_grid(tf), dim3(256), 0, st>>>(tf, nv, gr, c->cpos, used);
+      k_cc_flags_to_f64<<<cc_grid(nb * c->M), dim3(256), 0, st>>>(nb * c->M, used, usedf);
+      if (reduce) rrc = (*reduce)(usedf, (size_t)(nb * c->M));
+    }
+    std::vector<double> hused((size_t)(nb * c->M));
+    if (rrc == PHX_OK && hipMemcpyAsync(hused.data(), usedf, sizeof(double) * hused.size(), hipMemcpyDeviceToHost, st) != hipSuccess) rrc = PHX_ERR_HIP;
+    if (rrc == PHX_OK && hipStreamSynchronize(st) != hipSuccess) rrc = PHX_ERR_HIP;
     (void)phx_free(used); (void)phx_free(usedf);
-    return fail(PHX_ERR_HIP);
+    if (rrc != PHX_OK) return fail(rrc);
+    hmap.assign(hused.size(), -1);
+    hnode.clear();
+    for (size_t q = 0; q < hused.size(); ++q)
+      if (hused[q] > 0.0) { hmap[q] = (int32_t)hnode.size(); hnode.push_back((int32_t)q); }
+    if (!(wd && req < 0) || (int)hnode.size() <= PHX_ELWD_AUTO_NC_CAP) break;
   }
-  PHX_HIP(hipMemsetAsync(used, 0, (size_t)(nb * c->M), st));
-  k_cc_used<<<cc_grid(tf), dim3(256), 0, st>>>(tf, nv, g, c->cpos, used);
-  k_cc_flags_to_f64<<<cc_grid(nb * c->M), dim3(256), 0, st>>>(nb * c->M, used, usedf);
-  int rrc = reduce ? (*reduce)(usedf, (size_t)(nb * c->M)) : PHX_OK;
-  std::vector<double> hused((size_t)(nb * c->M));
-  if (rrc == PHX_OK && hipMemcpyAsync(hused.data(), usedf, sizeof(double) * hused.size(), hipMemcpyDeviceToHost, st) != hipSuccess) rrc = PHX_ERR_HIP;
-  if (rrc == PHX_OK && hipStreamSynchronize(st) != hipSuccess) rrc = PHX_ERR_HIP;
-  (void)phx_free(used); (void)phx_free(usedf);
-  if (rrc != PHX_OK) return fail(rrc);
-  std::vector<int32_t> hmap(hused.size(), -1), hnode;
-  for (size_t q = 0; q < hused.size(); ++q)
-    if (hused[q] > 0.0) { hmap[q] = (int32_t)hnode.size(); hnode.push_back((int32_t)q); }
+  const CcDims g{{c->nf[0], c->nf[1], c->nf[2]}, {c->m[0], c->m[1], c->m[2]}, c->ratio, c->M, {c->off[0], c->off[1], c->off[2]}};
   c->nc = (int)hnode.size();
-  const int nc_max = 24000;   // coarse DoFs the dense inverse is asked to take
-  if (c->nc == 0 || c->nc > nc_max) { coarse_free(c); return PHX_OK; }   // the same numbers on every rank
+  if (c->nc == 0 || c->nc > nc_max) { coarse_free(c); return why(PHX_CC_TOO_MANY); }   // the same numbers on every rank
+  if (phx_malloc(&c->cmap, sizeof(int32_t) * (size_t)(nb * c->M)) != hipSuccess) return no_memory();
   const int nc = c->nc;
   c->nc_blk[0] = nc;
   const int64_t t1 = nb * c->nf[2] * c->nf[1] * c->m[0], t2 = nb * c->nf[2] * c->m[1] * c->m[0], t3 = nb * c->M;
@@ -723,7 +803,7 @@ static int coarse_build(phx_system *s, int nblk, phx_coarse **out, const CcReduc
     if (reduce) veto = true;   // the SpMV probes would need the halo of every probing vector
     else mem_ok = phx_malloc(&wv, sizeof(double) * (size_t)n) == hipSuccess && phx_malloc(&tv, sizeof(double) * (size_t)n) == hipSuccess;
   }
-  if (!mem_ok) { (void)hipGetLastError(); if (!reduce) { drop_scratch(); return fail(PHX_ERR_HIP); } veto = true; }
+  if (!mem_ok) { (void)hipGetLastError(); if (!reduce) { drop_scratch(); return no_memory(); } veto = true; }
   if (reduce) {   // one veto and nobody corrects
     const double v = veto ? 1.0 : 0.0;
     double hv = 0.0;
@@ -788,7 +868,45 @@ static int coarse_build(phx_system *s, int nblk, phx_coarse **out, const CcReduc
     fprintf(stderr, "phifem_hip: the Galerkin coarse matrix of the elasticity correction (%d x %d) is singular to working precision: "
                     "the solve keeps the vertex blocks alone\n", nc, nc);
     coarse_free(c);
-    return PHX_OK;
+    return why(PHX_CC_SINGULAR);
+  }
+  if (wd) {
+    // ---- the check: x in the coarse space, zc = Ac^-1 R^T (A D^-1) (D R x) must be x (the elimination flags a
+    // singular pivot only when it is exactly zero, and nothing above tests the colour argument)
+    double *wv = nullptr, *tv = nullptr;
+    if (phx_malloc(&wv, sizeof(double) * (size_t)n) != hipSuccess || phx_malloc(&tv, sizeof(double) * (size_t)n) != hipSuccess) {
+      (void)phx_free(wv); (void)phx_free(tv);
+      return no_memory();
+    }
+    std::vector<double> hv((size_t)nc), hz((size_t)nc);
+    for (int i = 0; i < nc; ++i) hv[(size_t)i] = 1.0 + (double)((i * 7) % 13) / 13.0;
+    int rc2 = PHX_OK;
+    if (hipMemcpyAsync(c->zc, hv.data(), sizeof(double) * (size_t)nc, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemsetAsync(wv, 0, sizeof(double) * (size_t)n, st) != hipSuccess)
+      rc2 = PHX_ERR_HIP;
+    if (rc2 == PHX_OK) rc2 = coarse_prolong_add(s, c, wv);
+    if (rc2 == PHX_OK) rc2 = launch_spmv(s, s->sell_val, wv, tv, 0, nullptr, nullptr, nullptr, 0);
+    if (rc2 == PHX_OK) rc2 = coarse_restrict(s, c, tv);
+    if (rc2 == PHX_OK) {
+      k_cc_gemv<<<dim3((unsigned)phx_div_up(nc, 4)), dim3(256), 0, st>>>(nc, c->Ainv, c->gc, c->zc);
+      ++c->probes;
+      if (hipMemcpyAsync(hz.data(), c->zc, sizeof(double) * (size_t)nc, hipMemcpyDeviceToHost, st) != hipSuccess ||
+          hipStreamSynchronize(st) != hipSuccess)
+        rc2 = PHX_ERR_HIP;
+    }
+    (void)phx_free(wv); (void)phx_free(tv);
+    if (rc2 != PHX_OK) return fail(rc2);
+    double e2 = 0.0, v2 = 0.0;
+    for (int i = 0; i < nc; ++i) {
+      e2 += (hz[(size_t)i] - hv[(size_t)i]) * (hz[(size_t)i] - hv[(size_t)i]);
+      v2 += hv[(size_t)i] * hv[(size_t)i];
+    }
+    if (!(e2 <= 1e-12 * v2)) {   // NaN included
+      fprintf(stderr, "phifem_hip: the coarse correction of the weak-Dirichlet elasticity solve (H = %d h, %d coarse DoFs) fails its check "
+                      "|Ac^-1 R^T A R x - x| = %.2e |x|: the solve keeps the vertex blocks alone\n", ratio, nc, sqrt(e2 / v2));
+      coarse_free(c);
+      return why(PHX_CC_CHECK);
+    }
   }
   *out = c;
   return PHX_OK;
@@ -805,8 +923,6 @@ static int coarse_build(phx_system *s, int nblk, phx_coarse **out, const CcReduc
 //     2 r (c + 1) - 3 >= 2 r c + r, i.e. r >= 4.  The option takes r >= 5.
 //   * Column scaling.  The loop iterates on A C (C = 1 on the u columns of a structured system, D^-1 elsewhere: the
 //     u_unscaled convention); the probes are C^-1 R e, so that A C (C^-1 R e) = A R e, and the prolongation is C^-1 R.
-enum { PHX_CC_NOT_BOX = 1, PHX_CC_SMALL_BOX = 2, PHX_CC_TOO_MANY = 3, PHX_CC_SINGULAR = 4, PHX_CC_CHECK = 5,
-       PHX_CC_AUTO_OFF = 6 };
 #define PHX_P2C_NC_MAX 20000      // phx_dense_inverse
 // automatic choice: on for PHX_P2C_AUTO_MIN_N <= n < PHX_P2C_AUTO_MAX_N cubes per axis only.  Measured on MI355X
 // ("P2 coarse space"): the correction saves seconds at 96^3 (0.57 -> 0.46 s), breaks even at 64^3 and

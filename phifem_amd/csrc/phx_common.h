@@ -187,6 +187,7 @@ struct phx_mesh {
   int allow_empty = 0;             // PHX_OPT_ALLOW_EMPTY: assembly returns an EMPTY system when no cell is tagged 1 / 2
   int el_coarse = -1;              // PHX_OPT_EL_COARSE
   int p2_coarse = 0;               // PHX_OPT_P2_COARSE: 0 off, -1 automatic, >= 5 the ratio H / h
+  int elwd_coarse = 0;             // PHX_OPT_ELWD_COARSE: 0 off, -1 automatic, >= 5 the ratio H / h
   int deterministic = 0;           // PHX_OPT_DETERMINISTIC: bit-reproducible P2 / elasticity assembly and Krylov dot products
   int multilevel = 0;              // PHX_OPT_MULTILEVEL: V-cycle over the refinement hierarchy as the u preconditioner
   // A caller-supplied mesh that IS a Kuhn box in some vertex / cell order (what dolfinx's create_box / create_rectangle
@@ -328,7 +329,12 @@ struct phx_system {
   struct phx_coarse *cc = nullptr; // coarse correction on top of the vertex blocks (phx_coarse.inc.hip)
   struct phx_multilevel *ml = nullptr;   // multilevel preconditioner of the u block (phx_multilevel.inc.hip)
   bool cc_tried = false;
-  int cc_reason = 0;               // P2 coarse correction asked for but not built: PHX_CC_* reason (phx_coarse.inc.hip)
+  int cc_reason = 0;               // P2 / weak-Dirichlet elasticity coarse correction asked for but not built: PHX_CC_* reason (phx_coarse.inc.hip)
+  // coarse functions of a vertex-block system (phx_coarse.inc.hip): 0 interface elasticity (u_in[a], u_out[a]: blocks
+  // 0 .. 2 d - 1, Dirichlet rows in the first d, PHX_OPT_EL_COARSE), 1 weak-Dirichlet elasticity (u_a: blocks 0 .. d - 1,
+  // no Dirichlet rows, PHX_OPT_ELWD_COARSE)
+  enum { PHX_CC_LAYOUT_INTERFACE = 0, PHX_CC_LAYOUT_ELWD = 1 };
+  int cc_layout = PHX_CC_LAYOUT_INTERFACE;
   // PHX_OPT_DETERMINISTIC: every block of a dot-product kernel leaves its partial sum in its own entry of `dpart`
   // ([4][dpart_cap]) instead of adding it to a slot atomically; k_fold_partials sums them in a fixed order
   double *dpart = nullptr;

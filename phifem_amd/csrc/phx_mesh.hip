@@ -1259,6 +1259,10 @@ extern "C" int phx_set_option(phx_mesh *m, int option, int64_t value) {
       PHX_REQUIRE(value == -1 || value == 0 || (value >= 5 && value <= 4096), PHX_ERR_VALUE, "coarse ratio %lld: -1, 0 or >= 5", (long long)value);
       m->p2_coarse = (int)value;
       return PHX_OK;
+    case PHX_OPT_ELWD_COARSE:
+      PHX_REQUIRE(value == -1 || value == 0 || (value >= 5 && value <= 4096), PHX_ERR_VALUE, "coarse ratio %lld: -1, 0 or >= 5", (long long)value);
+      m->elwd_coarse = (int)value;
+      return PHX_OK;
     case PHX_OPT_PRECOND:
       PHX_REQUIRE(value >= 0 && value <= 2, PHX_ERR_VALUE, "unknown preconditioner %lld", (long long)value);
       m->precond = (int)value;

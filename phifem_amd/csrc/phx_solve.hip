@@ -2370,6 +2370,8 @@ static int kr_setup(phx_system *s, int mode) {
       const auto t0 = std::chrono::steady_clock::now();
       PHX_CHECK(coarse_build(s, s->el_nblk, &s->cc));
       if (s->cc) s->cc->build_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    } else if (s->cc_layout == phx_system::PHX_CC_LAYOUT_ELWD && !s->cc_tried && m->elwd_coarse != 0) {
+      s->cc_reason = PHX_CC_NOT_BOX;   // no vertex blocks, a slab rank or the phase API: said, as coarse_build says the rest
     }
   }
   // P2 weak Dirichlet: coarse correction on top of the lattice preconditioner (PHX_OPT_P2_COARSE), once per system

@@ -134,6 +134,8 @@ class PhiFEMSolver:
         L.check(L.lib.phx_set_option(self.mesh._h, L.OPT_MULTILEVEL, int(getattr(self, "_ml_on", False))))
         if hasattr(self, "coarse"):
             L.check(L.lib.phx_set_option(self.mesh._h, L.OPT_EL_COARSE, self.coarse))
+        if hasattr(self, "_elwd_coarse"):     # ElasticitySolver: its own option, PHX_OPT_EL_COARSE is the sibling's
+            L.check(L.lib.phx_set_option(self.mesh._h, L.OPT_ELWD_COARSE, self._elwd_coarse))
 
     def __del__(self):
         self._free()
@@ -308,6 +310,12 @@ class PhiFEMSolver:
         L.check(L.lib.phx_krylov_reduced_loop(self._sys, C.byref(ident)))
         self.stats["reduced_loop"] = bool(ident.value)
         self.stats.update(self.precond_info())
+        if getattr(self, "_elwd_coarse", 0) != 0:
+            self.stats.update(self.coarse_info())
+            reason = self.stats["coarse_reason"]
+            if reason and self._elwd_coarse > 0:
+                warnings.warn(f"coarse={self._elwd_coarse}: no coarse correction was built ({reason}); the solve used the "
+                              f"vertex blocks alone", RuntimeWarning, stacklevel=2)
         if getattr(self, "_p2_coarse", 0) != 0:
             self.stats.update(self.coarse_info())
             reason = self.stats["coarse_reason"]
@@ -361,7 +369,7 @@ class PhiFEMSolver:
         return {"coarse_ratio": int(o[0]) if built else 0, "coarse_dofs": int(o[1] + o[2]),
                 "coarse_dofs_u": int(o[1]), "coarse_dofs_p": int(o[2]), "coarse_build_s": o[3],
                 "coarse_probes": int(o[4]), "coarse_apply_bytes": int(o[5]),
-                "coarse_reason": None if built else _COARSE_REASONS.get(int(-o[0]))}
+                "coarse_reason": None if built else getattr(self, "_coarse_reasons", _COARSE_REASONS).get(int(-o[0]))}
 
     def coarse_export(self):
         """(node_of, Ac^-1) of the coarse correction (phx_coarse_export): node_of[i] = field * M + node of compact
@@ -570,19 +578,39 @@ class ElasticitySolver(PhiFEMSolver):
     The mesh is a tagged generated box / rectangle with simplex cells, a `Mesh.from_arrays` mesh, or the sub-mesh of
     `compute_tags_measures(..., box_mode=False)`.  Solution layout: component-major blocks of nv entries, u_a -> a,
     p_a -> d + a (`split`); inactive DoFs are exactly 0.  The solve preconditions with the vertex blocks
-    (`stats["precond"] == "vertex-block-jacobi"`); there is no coarse space or multilevel cycle for this system."""
+    (`stats["precond"] == "vertex-block-jacobi"`), and on request with a Galerkin coarse space on top of them
+    (`coarse=`, "vertex-block-jacobi+coarse"); there is no multilevel cycle for this system."""
+
+    _coarse_reasons = {**_COARSE_REASONS,
+                       1: "not a box: the correction needs a single-rank system on a generated simplicial box (not a "
+                          "sub-mesh, a caller-supplied or a refined mesh) with its vertex blocks",
+                       3: "too many coarse DoFs for the dense inverse (20000) or for the device memory left"}
 
     def __init__(self, mesh, E=1.0, nu=0.3, pen_coef=1.0, stab_coef=1.0, deterministic=False, degree=1,
-                 coarse_space=None, multilevel=False):
+                 coarse_space=None, multilevel=False, coarse=0):
+        """coarse (PHX_OPT_ELWD_COARSE): spacing H / h of the coarse-space correction of the solve on generated boxes
+        (2-D and 3-D, one rank): multilinear functions of spacing H per displacement component, Galerkin coarse matrix,
+        added to the vertex blocks -- the iteration count then follows H / h instead of growing with the box.  0
+        (default): off; -1: the library picks H and leaves the correction off where it does not pay (DESIGN.md 7h);
+        an int >= 5: this ratio.  Built on the first solve; `stats` then carries `coarse_info()`, and a ratio that was
+        asked for and could not be served is reported by a RuntimeWarning and `stats["coarse_reason"]`.  Independent of
+        `InterfaceElasticitySolver(coarse=)`: the two solvers may share a mesh.  `coarse_space=` and `multilevel=` are
+        the spellings of `PhiFEMSolver` options that this system does not have."""
         if getattr(mesh, "cell_type", None) == "quadrilateral":
             raise NotImplementedError("weak-Dirichlet elasticity is assembled on triangles and tetrahedra (no Q1 spaces)")
         if degree != 1:
             raise NotImplementedError("weak-Dirichlet elasticity: P1 x P1 is implemented (degree = 1)")
         if coarse_space is not None:
-            raise NotImplementedError("weak-Dirichlet elasticity has no coarse-space correction (vertex-block Jacobi only)")
+            raise NotImplementedError("weak-Dirichlet elasticity: the coarse-space correction is asked for with coarse= "
+                                      "(coarse_space is the P2 option of PhiFEMSolver)")
         if multilevel is not False:
             raise NotImplementedError("weak-Dirichlet elasticity has no multilevel preconditioner (vertex-block Jacobi only)")
+        if isinstance(coarse, bool) or not isinstance(coarse, (int, np.integer)) or not (coarse in (0, -1) or 5 <= coarse <= 4096):
+            raise ValueError(f"coarse={coarse!r}: 0 (off), -1 (automatic) or an int >= 5 (H / h)")
+        if coarse > 0 and getattr(mesh, "parent", None) is not None:
+            raise NotImplementedError("coarse needs the box mesh (box_mode=True), not a sub-mesh")
         super().__init__(mesh, pen_coef=pen_coef, stab_coef=stab_coef, deterministic=deterministic)
+        self._elwd_coarse = int(coarse)
         self.params = np.array([E, nu, pen_coef, stab_coef], dtype=np.float64)
 
     def assemble(self, phi_h, f_h, u_D):
