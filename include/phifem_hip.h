@@ -246,6 +246,12 @@ enum phx_option {
                                when a system is assembled (0: that system never builds one) and on its first solve;
                                phx_coarse_info reports the correction or why it was not built.  Independent of
                                PHX_OPT_EL_COARSE, which speaks of interface-elasticity systems only             */
+  PHX_OPT_BOX_FACET_ROWS = 16, /* 1 (default): where a P1 weak-Dirichlet assembly on a Kuhn box addresses its stored rows
+                               by lattice offset code (structured system, no CSR copy, not deterministic), the ghost
+                               penalty is gathered per stored row from the facet tags, the per-type tables of
+                               phx_box_facet_tables and the vertex coordinates, without atomics; 0: the facet kernel that scatters with f64
+                               atomics runs there too.  Same matrix to round-off: 0 is the reference path of
+                               tests/test_box_facet_rows.py                                                      */
   PHX_OPT_ALLOW_EMPTY = 6, /* 1: phx_assemble_poisson_wd returns an EMPTY system (n_active = 0) when no cell
                                is tagged 1 / 2 instead of PHX_ERR_VALUE: a slab of a partitioned box that
                                does not touch the domain still joins every collective of the solve          */
@@ -491,6 +497,23 @@ int phx_locate_timings(const phx_mesh *m, double *t);
  * PHX_ERR_NOT_IMPLEMENTED. */
 int phx_assemble_poisson_wd(phx_mesh *m, double pen_coef, double stab_coef, const double *phi_h,
                             const double *f_h, const double *u_D, int loc, phx_system **out);
+/* [host] The facet classes of a Kuhn box of uniform spacings h[gdim] behind PHX_OPT_BOX_FACET_ROWS: *ntypes = 12 (3-D)
+ * or 3 (2-D) facet types in the generator's numbering (facet id = base[type] + anchor index).  cells and offsets are the
+ * tables the row kernel walks; J and w are what its closed form gives where every cube has the spacings h (the kernel
+ * takes each facet's spacings from the vertex coordinates, as the scattering kernel does).  Per type t:
+ *   cells[2 t + side]                 the two simplices of the facet as axis-permutation indices (cell = cube * nper +
+ *                                     index); the first one lies in the cube below the anchor for the types in a
+ *                                     plane x_a = const, in the anchor cube otherwise, the second one in the anchor cube
+ *   offsets[(t (gdim + 2) + l) gdim + a]  the gdim + 2 vertices of the macro-element as lattice offsets from the anchor:
+ *                                     the gdim + 1 vertices of the first cell, then the vertex of the second cell
+ *                                     opposite the facet
+ *   J[t (gdim + 2) + l]               jump of the normal derivative of the hat function of vertex l across the facet
+ *                                     (a shared vertex carries both one-sided terms; exactly 0.0 where it vanishes)
+ *   w[t]                              stab_coef avg(h) |F| with h the cell diameter (main.py:129-134)
+ * Entry (l, m) of the facet tensor is w[t] J[l] J[m].  Any output may be NULL.  PHX_ERR_VALUE if the tables do not
+ * fit the lattice offset codes of the row slots (a library defect). */
+int phx_box_facet_tables(int gdim, const double *h, double stab_coef, int *ntypes, int32_t *cells, int32_t *offsets,
+                         double *J, double *w);
 /* The same forms with primal_degree = auxiliary_degree = 2 (BASELINE configs[2]); the
  * div(grad(.)) terms of main.py:123-128,150 are live.  DoFs per field: vertex v -> v, edge e ->
  * nv + e (PHX_ARR_EDGES / PHX_ARR_C2E), p block shifted by nv + ne.  f_h, u_D: nodal P2 arrays

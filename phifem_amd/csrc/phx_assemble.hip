@@ -164,6 +164,143 @@ __device__ __forceinline__ void slot_add_box_owned(const Slots &s, int64_t base,
   s.vals[base + code] += v;
 }
 
+// Facet classes of a Kuhn box (phx_mesh.hip, "Device generator for Kuhn boxes"), from the same simplex table as
+// BoxCodes: facet type t joins simplex cell[t][0] -- of the cube below the anchor for the types A(a, s), whose
+// first cell lies on the low side of the plane x_a = const, of the anchor cube otherwise -- to simplex cell[t][1] of the
+// anchor cube, as k_box_f2c pairs them.  d[t][l]: the D + 2 vertices of the macro-element as lattice offsets from the
+// anchor, in facet_macro's order (the D + 1 path vertices of the first cell, then the vertex of the second cell
+// opposite the facet).  The column offsets d[t][m] - d[t][l] of all types, in lattice order (dz, dy, dx), number the
+// accumulators of k_assemble_facet_rows_box: k[t][l][m] -> off[k].  Integers of D alone: evaluated by the compiler.
+template <int D>
+struct FacetClasses {
+  static constexpr int NT = D == 3 ? 12 : 3, M = D + 2;
+  int8_t cell[NT][2];     // permutation indices of the two cells
+  int8_t lf[NT][2];       // the facet as local facet of each
+  int8_t axis[NT];        // a of A(a, s): anchors with o[a] == 0 or o[a] == n[a] are boundary facets; -1: type B
+  int8_t single[NT];      // type B in 3-D: the axis outside the pair (the facet normal lies in the plane of the other two); -1
+  int8_t d[NT][M][3];
+  // closed form of the jump coefficients (facet_type_coef): J[l] = sgn[t][l] * mag[side[t][l]] -- type A: mag = 1 / h_a
+  // of the cube below the anchor (side 0) and of the anchor cube (side 1); type B: |g_lf| of the anchor cube (side 0)
+  int8_t sgn[NT][M], side[NT][M];
+  int8_t k[NT][M][M];
+  int8_t off[64][3];
+  int nk;
+};
+template <int D>
+__host__ __device__ constexpr FacetClasses<D> facet_classes() {
+  constexpr int NT = FacetClasses<D>::NT, M = FacetClasses<D>::M;
+  FacetClasses<D> F{};
+  for (int t = 0; t < NT; ++t) {
+    int pa[3] = {0, 0, 0}, pb[3] = {0, 0, 0}, lfa = 0, lfb = 0, axis = -1;
+    if (D == 3) {
+      const int a = t < 6 ? t / 2 : (t < 9 ? t - 6 : t - 9);   // the single axis of the type
+      const int r0 = a == 0 ? 1 : 0, r1 = a == 2 ? 1 : 2;      // remaining axes, ascending
+      if (t < 6) {
+        const int s0 = t % 2 ? r1 : r0, s1 = t % 2 ? r0 : r1;
+        pa[0] = a; pa[1] = s0; pa[2] = s1; lfa = 0;
+        pb[0] = s0; pb[1] = s1; pb[2] = a; lfb = 3;
+        axis = a;
+      } else if (t < 9) {
+        pa[0] = r0; pa[1] = r1; pa[2] = a; lfa = 1;
+        pb[0] = r1; pb[1] = r0; pb[2] = a; lfb = 1;
+      } else {
+        pa[0] = a; pa[1] = r0; pa[2] = r1; lfa = 2;
+        pb[0] = a; pb[1] = r1; pb[2] = r0; lfb = 2;
+      }
+      F.cell[t][0] = (int8_t)(pa[0] * 2 + (pa[1] > pa[2] ? 1 : 0));   // perm_index3
+      F.cell[t][1] = (int8_t)(pb[0] * 2 + (pb[1] > pb[2] ? 1 : 0));
+    } else {
+      if (t < 2) {
+        pa[0] = t; pa[1] = 1 - t; lfa = 0;
+        pb[0] = 1 - t; pb[1] = t; lfb = 2;
+        axis = t;
+      } else {
+        pa[0] = 0; pa[1] = 1; lfa = 1;
+        pb[0] = 1; pb[1] = 0; lfb = 1;
+      }
+      F.cell[t][0] = (int8_t)pa[0];
+      F.cell[t][1] = (int8_t)pb[0];
+    }
+    F.lf[t][0] = (int8_t)lfa;
+    F.lf[t][1] = (int8_t)lfb;
+    F.axis[t] = (int8_t)axis;
+    F.single[t] = (int8_t)(D == 3 && axis < 0 ? (t < 9 ? t - 6 : t - 9) : -1);
+    // signs in the order of d[t][.]; facet_classes_check holds them against simplex_geometry on both cells
+    constexpr int SA3[5] = {-1, 1, 0, 1, -1}, SP3[5] = {1, -1, 1, 0, -1}, SS3[5] = {0, 1, -1, 1, -1};   // A, 6 + c, 9 + a
+    constexpr int SA2[4] = {-1, 1, 1, -1}, SB2[4] = {1, -1, 1, -1};
+    for (int l = 0; l < M; ++l) {
+      F.sgn[t][l] = (int8_t)(D == 3 ? (axis >= 0 ? SA3[l] : (t < 9 ? SP3[l] : SS3[l])) : (axis >= 0 ? SA2[l % 4] : SB2[l % 4]));
+      F.side[t][l] = (int8_t)(axis >= 0 && l >= M / 2 ? 1 : 0);
+    }
+    int v[3] = {0, 0, 0};
+    if (axis >= 0) v[axis] = -1;
+    for (int q = 0; q <= D; ++q) {
+      for (int a = 0; a < 3; ++a) F.d[t][q][a] = (int8_t)v[a];
+      if (q < D) v[pa[q]] += 1;
+    }
+    int u[3] = {0, 0, 0};
+    for (int q = 0; q < lfb; ++q) u[pb[q]] += 1;
+    for (int a = 0; a < 3; ++a) F.d[t][D + 1][a] = (int8_t)u[a];
+  }
+  bool in[125] = {};
+  for (int t = 0; t < NT; ++t)
+    for (int l = 0; l < M; ++l)
+      for (int m = 0; m < M; ++m)
+        in[(F.d[t][m][2] - F.d[t][l][2] + 2) * 25 + (F.d[t][m][1] - F.d[t][l][1] + 2) * 5 + F.d[t][m][0] - F.d[t][l][0] + 2] = true;
+  int idx[125] = {};
+  int nk = 0;
+  for (int o = 0; o < 125; ++o) {
+    idx[o] = -1;
+    if (!in[o]) continue;
+    idx[o] = nk;
+    if (nk < 64) { F.off[nk][0] = (int8_t)(o % 5 - 2); F.off[nk][1] = (int8_t)((o / 5) % 5 - 2); F.off[nk][2] = (int8_t)(o / 25 - 2); }
+    ++nk;
+  }
+  F.nk = nk;
+  for (int t = 0; t < NT; ++t)
+    for (int l = 0; l < M; ++l)
+      for (int m = 0; m < M; ++m)
+        F.k[t][l][m] = (int8_t)idx[(F.d[t][m][2] - F.d[t][l][2] + 2) * 25 + (F.d[t][m][1] - F.d[t][l][1] + 2) * 5 + F.d[t][m][0] - F.d[t][l][0] + 2];
+  return F;
+}
+static_assert(facet_classes<3>().nk <= 64 && facet_classes<2>().nk <= 64, "one occupancy bit per accumulator");
+// what the spacings add: the jump coefficient of every vertex of the macro-element and the weight sigma avg(h) |F| --
+// entry (l, m) of the facet tensor of type t is w[t] J[t][l] J[t][m].  facet_coef_build evaluates them for a box of
+// uniform spacings with simplex_geometry (host: phx_box_facet_tables and the check of the closed form below).
+struct FacetCoef { double J[12][5], w[12]; };
+// The same in closed form, for the facet of type t whose anchor cube has the spacings hc (inverses ic) and, for a type
+// A(a, s), whose cube below the anchor has the spacing hl (inverse il) along a.  The gradients of a Kuhn simplex are
+// -e_p0 / h_p0, e_p(k-1) / h_p(k-1) - e_pk / h_pk, e_p(D-1) / h_p(D-1), so with n = -g_lf / |g_lf|:
+//   A: g_lf = -+ e_a / h_a on the two sides: J = -+ 1 / h_a of that side's cube, |F| = prod_{b != a} h_b / (D - 1)!
+//   B: g_lf = +- (e_r0 / h_r0 - e_r1 / h_r1) for the pair (r0, r1): J = +- |g_lf|, |F| = D |K| |g_lf|
+// and h (ufl.CellDiameter) the main diagonal of each cell's cube.  J[l] = sgn[t][l] * mag[side[t][l]].
+template <int D>
+__host__ __device__ __forceinline__ void facet_type_coef(int t, const double *hc, const double *ic, double hl, double il,
+                                                         double sigma, double *mag, double *w) {
+  constexpr FacetClasses<D> F = facet_classes<D>();
+  const int a = F.axis[t], s = F.single[t];
+  double d2 = 0.0;
+  for (int b = 0; b < D; ++b) d2 += hc[b] * hc[b];
+  const double dc = sqrt(d2);
+  if (a >= 0) {
+    double area = D == 3 ? 0.5 : 1.0, dl2 = hl * hl;
+    for (int b = 0; b < D; ++b)
+      if (b != a) { area *= hc[b]; dl2 += hc[b] * hc[b]; }
+    mag[0] = il;
+    mag[1] = ic[a];
+    *w = sigma * 0.5 * (sqrt(dl2) + dc) * area;
+  } else {
+    double g2 = 0.0, vol = D == 3 ? 1.0 / 6.0 : 0.5;
+    for (int b = 0; b < D; ++b) {
+      vol *= hc[b];
+      if (b != s) g2 += ic[b] * ic[b];
+    }
+    const double gn = sqrt(g2);
+    mag[0] = mag[1] = gn;
+    *w = sigma * 0.5 * (dc + dc) * (D * vol * gn);
+  }
+}
+
 __device__ __forceinline__ int det_expo(double v) { return (int)((__double_as_longlong(v) >> 52) & 0x7ff); }
 __device__ __forceinline__ void det_split(double v, int e, double &hi, double &lo) {
   const int E = e - 1023;                       // every |contribution| < 2^(E+1)
@@ -229,7 +366,7 @@ struct Geo {
 };
 
 template <int D>
-__device__ __forceinline__ void simplex_geometry(const double (*X)[D], Geo<D> &G) {
+__host__ __device__ __forceinline__ void simplex_geometry(const double (*X)[D], Geo<D> &G) {
   if constexpr (D == 2) {
     const double a = X[1][0] - X[0][0], b = X[2][0] - X[0][0];
     const double c = X[1][1] - X[0][1], d = X[2][1] - X[0][1];
@@ -1047,6 +1184,113 @@ __global__ void __launch_bounds__(256) k_assemble_facets(int64_t nlist, const in
     for (int b = 0; b < M; ++b) slot_add(A.slots, rows[a], vd[b], w * Jd[a] * Jd[b]);
 }
 
+// --- ghost penalty as ROW GATHERS on a Kuhn box with box slots (PHX_OPT_BOX_FACET_ROWS): one thread per stored u row, as
+// the mode-2 launch of k_assemble_rows_box walks them.  The row's vertex c is position l of the macro-element of the
+// facet of type t anchored at c - d[t][l] (FacetClasses): 12 x 5 (3 x 4) incidences, each one facet-tag byte at a
+// closed-form address -- the committed tags and SelGhostFacet's rule, so user-overwritten tags count as in the scatter
+// kernel, and the interior facets are the anchors inside [lo, n) with lo = 1 along the axis of an A type (the set
+// f2c[2f + 1] >= 0).  A stabilised incidence adds row l of its facet's tensor, w J_l J_m, to accumulators numbered at
+// compile time; the row then takes them with plain read-modify-writes at its own slots.  No connectivity or dof-map
+// load, no simplex geometry, no atomics: rows are owned, the kernel is their only writer while it runs.
+// Coefficients: the closed form facet_type_coef on the spacings of the facet's OWN cubes, taken as differences of the
+// vertex coordinates along the three lattice lines through c (five per axis) -- the numbers the scatter kernel forms
+// its edge vectors from.  A table of the nominal spacing box_h would be more accurate than either and is NOT the same
+// matrix: where |x| / h is large the rounded coordinates carry the spacing to |x| / h ulps only (200 on the 400 x 256
+// x 8 box of tests/test_hip_stencil_paths.py), the ghost-penalty entries with it, and the stored rows must stay the
+// rows of the re-assembled CSR (PHX_OPT_EXPORT_CSR, which scatters) to a few ulps.
+// Every slot of a stabilised incidence is marked occupied, an exactly vanishing product included (the structural
+// pattern is the scatter kernel's), and receives no add when its sum is exactly 0.
+template <int D>
+__global__ void __launch_bounds__(256)
+k_assemble_facet_rows_box(int64_t nrows, const int32_t *__restrict__ rows, const int64_t *__restrict__ full, int64_t nu,
+                          BoxDims bd, AsmArgs A) {
+  constexpr FacetClasses<D> F = facet_classes<D>();
+  constexpr int NT = FacetClasses<D>::NT, M = FacetClasses<D>::M, NK = F.nk;
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (tid >= nrows) return;
+  const int32_t row = rows[tid];
+  if (row >= nu) return;
+  const int64_t vtx = full[row];
+  const int64_t n0 = bd.n[0] + 1, n1 = bd.n[1] + 1;
+  const int64_t c[3] = {vtx % n0, D == 3 ? (vtx / n0) % n1 : vtx / n0, D == 3 ? vtx / (n0 * n1) : 0};
+  // tags of all incidences first: independent loads in flight (an incidence outside the box reads tag 0 of facet 0)
+  uint64_t stab = 0;
+  int64_t fbase = 0;   // k_box_f2c: facet id = base[type] + anchor index inside the type's extent
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    int64_t ext[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) ext[a] = a < D ? bd.n[a] + (a == F.axis[t] ? 1 : 0) : 1;
+#pragma unroll
+    for (int l = 0; l < M; ++l) {
+      bool in = true;
+      int64_t o[3] = {0, 0, 0};
+#pragma unroll
+      for (int a = 0; a < D; ++a) {
+        o[a] = c[a] - F.d[t][l][a];
+        in = in && o[a] >= (a == F.axis[t] ? 1 : 0) && o[a] < bd.n[a];
+      }
+      const int64_t f = in ? fbase + o[0] + ext[0] * (o[1] + ext[1] * o[2]) : 0;
+      const int tag = A.ftags[f];
+      if (in && (tag == 2 || tag == 3)) stab |= 1ull << (t * M + l);
+    }
+    fbase += ext[0] * ext[1] * ext[2];
+  }
+  if (stab == 0) return;
+  // hh[a][j]: spacing of the interval [c_a - 2 + j, c_a - 1 + j] along axis a (an interval outside the box: 0, never used --
+  // the cubes of an interior facet lie inside), ih: its inverse
+  double hh[D][4], ih[D][4];
+#pragma unroll
+  for (int a = 0; a < D; ++a) {
+    const int64_t vs = a == 0 ? 1 : (a == 1 ? n0 : n0 * n1);
+    double xs[5];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      int64_t q = c[a] + j - 2;
+      q = q < 0 ? 0 : (q > bd.n[a] ? bd.n[a] : q);
+      xs[j] = A.x[(vtx + (q - c[a]) * vs) * D + a];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { hh[a][j] = xs[j + 1] - xs[j]; ih[a][j] = 1.0 / hh[a][j]; }
+  }
+  double acc[NK];
+#pragma unroll
+  for (int k = 0; k < NK; ++k) acc[k] = 0.0;
+  uint64_t seen = 0;
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+#pragma unroll
+    for (int l = 0; l < M; ++l) {
+      if (!((stab >> (t * M + l)) & 1ull)) continue;
+#pragma unroll
+      for (int m = 0; m < M; ++m) seen |= 1ull << F.k[t][l][m];
+      if (F.sgn[t][l] == 0) continue;   // a vertex without a jump: slots only
+      // the anchor cube is the interval 2 - d[t][l][a] of each axis, the cube below an A facet the one before it
+      double hc[D], ic[D], hl = 0.0, il = 0.0, mag[2], w;
+#pragma unroll
+      for (int a = 0; a < D; ++a) {
+        hc[a] = hh[a][2 - F.d[t][l][a]];
+        ic[a] = ih[a][2 - F.d[t][l][a]];
+        if (a == F.axis[t]) { hl = hh[a][1 - F.d[t][l][a]]; il = ih[a][1 - F.d[t][l][a]]; }
+      }
+      facet_type_coef<D>(t, hc, ic, hl, il, A.sigma, mag, &w);
+      const double wj = w * ((double)F.sgn[t][l] * mag[F.side[t][l]]);
+#pragma unroll
+      for (int m = 0; m < M; ++m)
+        if (F.sgn[t][m] != 0) acc[F.k[t][l][m]] += wj * ((double)F.sgn[t][m] * mag[F.side[t][m]]);
+    }
+  }
+  const int64_t base = A.slots.off[row];
+#pragma unroll
+  for (int k = 0; k < NK; ++k) {
+    if (!((seen >> k) & 1ull)) continue;
+    const int code = c_box[D - 2].lut[0][(F.off[k][2] + 2) * 25 + (F.off[k][1] + 2) * 5 + F.off[k][0] + 2];
+    if (code < 0) { atomicOr(A.slots.overflow, 1); continue; }
+    A.slots.occ[base + code] = 1;
+    if (acc[k] != 0.0) A.slots.vals[base + code] += acc[k];
+  }
+}
+
 // deterministic accumulation: value = hi + lo
 __global__ void k_det_finalize(int64_t n, double *__restrict__ acc, const double *__restrict__ lo) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -1455,6 +1699,133 @@ static const BoxCodes *box_codes(int device, int D) {
     uploaded[device] = true;
   }
   return &host[D - 2];
+}
+
+// Jump coefficients and weights of the facet types of a box of spacings h: simplex_geometry and the formulas of
+// facet_macro on the two cells of each type, placed on a reference cube at the origin: what phx_box_facet_tables hands
+// out, and what facet_classes_check holds the closed form of the row kernel against.  The gradients of a Kuhn simplex
+// have exact zero components there and the dot products are sums of products, so a jump that vanishes comes out as
+// exactly 0.0.
+template <int D>
+static void facet_coef_build(const double *h, double sigma, FacetCoef &C) {
+  constexpr FacetClasses<D> F = facet_classes<D>();
+  constexpr int N = D + 1;
+  const int P[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};   // k_box_cells
+  const int P2[2][3] = {{0, 1, 0}, {1, 0, 0}};
+  memset(&C, 0, sizeof(C));
+  for (int t = 0; t < F.NT; ++t) {
+    int v[2][N][3];
+    double J[2][N], hsum = 0.0, area = 0.0;
+    for (int side = 0; side < 2; ++side) {
+      const int p = F.cell[t][side];
+      int c[3] = {0, 0, 0};
+      if (side == 0 && F.axis[t] >= 0) c[F.axis[t]] = -1;   // the first cell of an A type lies in the cube below the anchor
+      double X[N][D];
+      for (int q = 0; q < N; ++q) {
+        for (int a = 0; a < 3; ++a) v[side][q][a] = c[a];
+        for (int a = 0; a < D; ++a) X[q][a] = (double)c[a] * h[a];
+        if (q < D) c[D == 3 ? P[p][q] : P2[p][q]] += 1;
+      }
+      Geo<D> G;
+      simplex_geometry<D>(X, G);
+      const int lf = F.lf[t][side];
+      double gn = 0.0;
+      for (int a = 0; a < D; ++a) gn += G.g[lf][a] * G.g[lf][a];
+      gn = sqrt(gn);
+      if (side == 0) area = D * G.vol * gn;
+      hsum += G.h;
+      for (int j = 0; j < N; ++j) {
+        double sj = 0.0;
+        for (int a = 0; a < D; ++a) sj += G.g[j][a] * G.g[lf][a];
+        J[side][j] = -sj / gn;
+      }
+    }
+    for (int j = 0; j < N; ++j) C.J[t][j] = J[0][j];
+    for (int j = 0; j < N; ++j) {
+      if (j == F.lf[t][1]) { C.J[t][N] = J[1][j]; continue; }
+      for (int q = 0; q < N; ++q)
+        if (v[0][q][0] == v[1][j][0] && v[0][q][1] == v[1][j][1] && v[0][q][2] == v[1][j][2]) C.J[t][q] += J[1][j];
+    }
+    for (int l = 0; l <= N; ++l)
+      if (C.J[t][l] == 0.0) C.J[t][l] = 0.0;   // no negative zero
+    C.w[t] = sigma * 0.5 * hsum * area;
+  }
+}
+
+// what k_assemble_facet_rows_box relies on: the macro-element of every type is the one its two cells span (the first
+// cell's path, then the far vertex of the second), its D + 2 vertices are distinct -- a row vertex then meets a type in
+// exactly D + 2 incidences, one per position -- and every column offset has a u code in BoxCodes
+template <int D>
+static bool facet_classes_check(const BoxCodes &codes) {
+  constexpr FacetClasses<D> F = facet_classes<D>();
+  const int P[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
+  const int P2[2][3] = {{0, 1, 0}, {1, 0, 0}};
+  for (int t = 0; t < F.NT; ++t) {
+    int c[3] = {0, 0, 0}, shared = 0;   // the second cell: D of its vertices are the first cell's, the other is d[t][D + 1]
+    for (int q = 0; q <= D; ++q) {
+      int hit = -1;
+      for (int l = 0; l <= D + 1; ++l)
+        if (F.d[t][l][0] == c[0] && F.d[t][l][1] == c[1] && F.d[t][l][2] == c[2]) hit = l;
+      if (hit < 0 || (q == F.lf[t][1]) != (hit == D + 1)) return false;
+      if (hit <= D) { ++shared; if (hit == F.lf[t][0]) return false; }
+      if (q < D) c[D == 3 ? P[F.cell[t][1]][q] : P2[F.cell[t][1]][q]] += 1;
+    }
+    if (shared != D) return false;
+    for (int l = 0; l < F.M; ++l)
+      for (int m = 0; m < F.M; ++m) {
+        const int dx = F.d[t][m][0] - F.d[t][l][0], dy = F.d[t][m][1] - F.d[t][l][1], dz = F.d[t][m][2] - F.d[t][l][2];
+        if (l != m && dx == 0 && dy == 0 && dz == 0) return false;
+        if (dx < -2 || dx > 2 || dy < -2 || dy > 2 || dz < -2 || dz > 2) return false;
+        if (codes.lut[0][(dz + 2) * 25 + (dy + 2) * 5 + dx + 2] < 0) return false;
+      }
+  }
+  // the closed form the kernel evaluates against simplex_geometry on both cells, on spacings that differ per axis
+  const double h[3] = {0.3, 0.2, 0.4}, ih[3] = {1.0 / h[0], 1.0 / h[1], 1.0 / h[2]};
+  FacetCoef C;
+  facet_coef_build<D>(h, 1.0, C);
+  for (int t = 0; t < F.NT; ++t) {
+    const int a = F.axis[t] >= 0 ? F.axis[t] : 0;
+    double mag[2], w;
+    facet_type_coef<D>(t, h, ih, h[a], ih[a], 1.0, mag, &w);
+    if (fabs(w - C.w[t]) > 1e-13 * C.w[t]) return false;
+    for (int l = 0; l < F.M; ++l) {
+      const double J = (double)F.sgn[t][l] * mag[F.side[t][l]];
+      if ((F.sgn[t][l] == 0) != (C.J[t][l] == 0.0) || fabs(J - C.J[t][l]) > 1e-13 * fabs(C.J[t][l])) return false;
+    }
+  }
+  return true;
+}
+
+// both checks against the host copy of BoxCodes, once
+static bool facet_classes_ok(int D) {
+  static const bool ok2 = facet_classes_check<2>(*box_codes(-1, 2)), ok3 = facet_classes_check<3>(*box_codes(-1, 3));
+  return D == 2 ? ok2 : ok3;
+}
+
+template <int D>
+static void facet_tables_export(const FacetCoef &C, int32_t *cells, int32_t *offsets, double *J, double *w) {
+  constexpr FacetClasses<D> F = facet_classes<D>();
+  for (int t = 0; t < F.NT; ++t) {
+    if (cells) { cells[2 * t] = F.cell[t][0]; cells[2 * t + 1] = F.cell[t][1]; }
+    for (int l = 0; l < F.M; ++l) {
+      if (offsets) for (int a = 0; a < D; ++a) offsets[(t * F.M + l) * D + a] = F.d[t][l][a];
+      if (J) J[t * F.M + l] = C.J[t][l];
+    }
+    if (w) w[t] = C.w[t];
+  }
+}
+
+extern "C" int phx_box_facet_tables(int gdim, const double *h, double sigma, int *ntypes, int32_t *cells,
+                                    int32_t *offsets, double *J, double *w) {
+  PHX_REQUIRE(gdim == 2 || gdim == 3, PHX_ERR_VALUE, "gdim must be 2 or 3");
+  PHX_REQUIRE(h != nullptr, PHX_ERR_VALUE, "spacings missing");
+  for (int a = 0; a < gdim; ++a) PHX_REQUIRE(h[a] > 0.0, PHX_ERR_VALUE, "h[%d] must be positive", a);
+  PHX_REQUIRE(facet_classes_ok(gdim), PHX_ERR_VALUE, "facet-class tables do not match the box slot codes");
+  FacetCoef C;
+  if (gdim == 2) { facet_coef_build<2>(h, sigma, C); facet_tables_export<2>(C, cells, offsets, J, w); }
+  else { facet_coef_build<3>(h, sigma, C); facet_tables_export<3>(C, cells, offsets, J, w); }
+  if (ntypes) *ntypes = gdim == 3 ? 12 : 3;
+  return PHX_OK;
 }
 
 static int free_slots(Slots &sl) {
@@ -1905,10 +2276,21 @@ static int p1_launch_pass(phx_mesh *m, phx_system *s, const BoxDims &bd, const A
     else k_assemble_ds<3><<<g, block, 0, m->stream>>>(ds.n, ds.packed, ds.pairs, A);
   }
   PHX_HIP(hipGetLastError());
-  if (w.n_fac > 0) {
+  if (w.n_fac > 0 && w.box_slots && m->box_facet_rows) {
+    // box slots (structured system, no CSR copy, not deterministic): the ghost penalty as row gathers over the stored rows
+    // -- every vertex of a stabilised facet is `touched`, so every row it reaches is a stored one.  0.23 ms against
+    // 0.90 ms for the scatter kernel at 256^3 (profiles/r09)
+    PHX_REQUIRE(facet_classes_ok(D), PHX_ERR_VALUE, "facet-class tables do not match the box slot codes");
+    if (w.n_stored_rows > 0) {
+      const dim3 g((unsigned)phx_div_up(w.n_stored_rows, 256));
+      if (D == 2) k_assemble_facet_rows_box<2><<<g, block, 0, m->stream>>>(w.n_stored_rows, w.stored_rows, s->full_of_active, s->nu, bd, A);
+      else k_assemble_facet_rows_box<3><<<g, block, 0, m->stream>>>(w.n_stored_rows, w.stored_rows, s->full_of_active, s->nu, bd, A);
+    }
+  } else if (w.n_fac > 0) {
     // (Per-class macro-element tables for generated boxes -- vertices as anchor + class offsets, the tensor w Jd Jd^T from
     // a table, no f2c / cells / c2f / coordinate loads and no simplex geometry per facet -- were measured at 1.46 ms against
-    // 1.49 ms for this kernel at 256^3: the 5e7 hashed f64 atomics are the whole cost.  Not kept.)
+    // 1.49 ms for this kernel at 256^3: the 5e7 hashed f64 atomics are the whole cost.  Not kept as a SCATTER; the tables
+    // pay with owned box slots, above.)
     const dim3 g((unsigned)phx_div_up(w.n_fac, 256));
     if (D == 2) k_assemble_facets<2><<<g, block, 0, m->stream>>>(w.n_fac, w.l_fac, A);
     else k_assemble_facets<3><<<g, block, 0, m->stream>>>(w.n_fac, w.l_fac, A);
