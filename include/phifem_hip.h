@@ -571,6 +571,23 @@ int phx_assemble_elasticity_if(phx_mesh *m, const double *params, const double *
  * capacity (2-D: 64, 128, 256; 3-D: 128, 256, 512): PHX_ERR_CAPACITY. */
 int phx_assemble_elasticity_wd(phx_mesh *m, const double *params, const double *phi_h, const double *f_h,
                                const double *u_D, int loc, phx_system **out);
+/* Reaction-diffusion c u - Lap u = f + c g in the P1 x P1 weak-Dirichlet scheme of phx_assemble_poisson_wd (same
+ * tags, DoF layout, active set, "inactive DoFs = 0"), c = `reaction` >= 0 a constant -- one implicit time step of the
+ * heat equation (backward Euler: c = 1 / dt, g = u^n; BDF2: c = 3 / (2 dt), g = (4 u^n - u^{n-1}) / 3):
+ *   a = a_Poisson + c (u, v)_{dx(1,2)} + stab c^2 h_T^2 (u, v)_{dx(2)}
+ *   L = L_Poisson(f + c g; u_D) + stab c h_T^2 (f + c g, v)_{dx(2)}
+ * with the consistent mass (1 + delta_ij) |T| / ((d+1)(d+2)).  g_h may be NULL (= 0).  The system stores every row
+ * (never stencil-coded, no detour over the generated box behind a caller-supplied Kuhn mesh) and keeps (reaction,
+ * pen_coef, stab_coef) for phx_system_update_rhs, which also produced its right-hand side.  phx_solve treats it as a
+ * P1 Poisson system that is not stencil-coded (lattice preconditioner where the mesh has a lattice, else Jacobi).
+ * reaction < 0 or not finite: PHX_ERR_VALUE.  Quadrilaterals, slabs and partitioned ranks: PHX_ERR_NOT_IMPLEMENTED. */
+int phx_assemble_reaction_wd(phx_mesh *m, double pen_coef, double stab_coef, double reaction, const double *phi_h,
+                             const double *f_h, const double *g_h, const double *u_D, int loc, phx_system **out);
+/* Overwrites the right-hand side of a phx_assemble_reaction_wd system with L above for new data (on the tags the mesh
+ * holds) and leaves the matrix alone: one lane per active vertex gathers its u and p row over the vertex star in a
+ * fixed order, no atomics -- the same data give the same bytes.  Any other system: PHX_ERR_VALUE. */
+int phx_system_update_rhs(phx_system *s, const double *phi_h, const double *f_h, const double *g_h,
+                          const double *u_D, int loc);
 int phx_system_destroy(phx_system *s);
 /* info[14] = {n_active, n_active_u, nnz (structural, CSR), n_full (= 2*nv), sell_padded_nnz,
  *             slot_capacity, sell_nnz (explicit zeros dropped), n_slices, value-indexed slices,
@@ -603,6 +620,12 @@ enum phx_method { PHX_BICGSTAB_JACOBI = 0 };
  * ill-conditioned systems), the iteration restarts from it. */
 int phx_solve(phx_system *s, int method, double rtol, int64_t max_iter, double *x, int loc,
               double *stats);
+/* phx_solve started from x0 (FULL numbering, same `loc` as x, may be x itself; NULL: phx_solve).  r0 = b - A x0 on
+ * the active rows; ||r0|| <= rtol ||b||: x = x0 with 0 iterations; else phx_solve on A delta = r0 with the tolerance
+ * rtol ||b|| / ||r0|| and x = x0 + delta.  stats[1] = ||b - A x|| / ||b||, the other entries are the inner solve's.
+ * Single-rank systems only (externally attached Krylov buffers: PHX_ERR_NOT_IMPLEMENTED). */
+int phx_solve_from(phx_system *s, int method, double rtol, int64_t max_iter, const double *x0, double *x, int loc,
+                   double *stats);
 
 /* --- pieces of the solve for externally driven (multi-GPU) iterations ------------------------
  * The driver owns the loop, does the halo exchange of the SpMV inputs before phases 2 / 4 and

@@ -121,6 +121,8 @@ SIGNATURES = {
     "phx_assemble_poisson_flux": ([_vp, _vp, _i, _i, _vp, _vp, _vp, _i, C.POINTER(_vp)], _i),
     "phx_assemble_elasticity_if": ([_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, C.POINTER(_vp)], _i),
     "phx_assemble_elasticity_wd": ([_vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_vp)], _i),
+    "phx_assemble_reaction_wd": ([_vp, _d, _d, _d, _vp, _vp, _vp, _vp, _i, C.POINTER(_vp)], _i),
+    "phx_system_update_rhs": ([_vp, _vp, _vp, _vp, _vp, _i], _i),
     "phx_reference_nodes": ([_i, _i, _vp, C.POINTER(C.c_int)], _i),
     "phx_cell_errors": ([_vp, _i, _i, _vp, _vp, _i64, _vp, _i, _vp, _vp, _pd], _i),
     "phx_estimate_poisson_wd": ([_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _pd], _i),
@@ -131,6 +133,7 @@ SIGNATURES = {
     "phx_system_export": ([_vp, _vp, _vp, _vp, _vp, _vp], _i),
     "phx_system_export_sell": ([_vp, _vp, _vp, _vp, _vp], _i),
     "phx_solve": ([_vp, _i, _d, _i64, _vp, _i, _pd], _i),
+    "phx_solve_from": ([_vp, _i, _d, _i64, _vp, _vp, _i, _pd], _i),
     "phx_krylov_identity_loop": ([_vp, C.POINTER(C.c_int)], _i),
     "phx_krylov_reduced_loop": ([_vp, C.POINTER(C.c_int)], _i),
     "phx_spmv": ([_vp, _vp, _vp, _i], _i),

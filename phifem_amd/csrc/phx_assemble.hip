@@ -2512,3 +2512,4 @@ extern "C" int phx_system_export(phx_system *s, int64_t *rowptr, int32_t *col, d
 #include "phx_errors.inc.hip"
 #include "phx_estimate.inc.hip"
 #include "phx_recover.inc.hip"
+#include "phx_assemble_react.inc.hip"

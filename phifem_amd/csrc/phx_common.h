@@ -352,6 +352,9 @@ struct phx_system {
   // (applied where full DoF indices leave the library: the solution vector, phx_system_export's dof map)
   const int32_t *out_vertex = nullptr;
   phx_mesh *outer = nullptr;       // the caller's mesh (timings are mirrored there)
+  // reaction system (phx_assemble_react.inc.hip): what phx_system_update_rhs needs to evaluate the linear form again
+  bool react = false;
+  double react_c = 0.0, react_pen = 0.0, react_stab = 0.0;
 };
 
 // helpers implemented in phx_mesh.hip

@@ -2986,3 +2986,5 @@ extern "C" int phx_spmv_bench(phx_system *s, int reps, double *out) {
   m->timings[4] = out[0] * 1e-3;
   return PHX_OK;
 }
+
+#include "phx_solve_from.inc.hip"

@@ -283,15 +283,25 @@ class PhiFEMSolver:
                                         dof.ctypes.data_as(C.c_void_p)))
         return rhs, dof
 
-    def solve(self, rtol=1e-8, max_iter=20000, out=None, profile_spmv=False, strict=False):
+    def solve(self, rtol=1e-8, max_iter=20000, out=None, profile_spmv=False, strict=False, x0=None):
         """Replaces the KSP/MUMPS block of main.py:162-182.  Returns the mixed solution in the
         full numbering [u (nv), p (nv)] with inactive DoFs at zero; `out` may be a device
         tensor of 2*nv doubles.  `stats["converged"]` says whether rtol was reached; if not, a
         `ConvergenceWarning` is issued (strict=True: ArithmeticError) -- the reference's direct solve
-        never returns an inaccurate x silently."""
+        never returns an inaccurate x silently.
+
+        x0 (`phx_solve_from`): a starting vector in the full numbering, a numpy array or a device tensor of the kind
+        of `out` (a new numpy array / a new tensor on x0's device when `out` is None).  The solve then runs on the
+        correction b - A x0 and stops at ||b - A x|| <= rtol ||b||; an x0 that meets the tolerance already comes back
+        unchanged with 0 iterations.  None: the solve from zero."""
         nfull = self.info()["n_full"]
+        x0_dev = x0 is not None and hasattr(x0, "data_ptr") and x0.is_cuda
         if out is None:
-            out = np.empty(nfull, dtype=np.float64)
+            if x0_dev:
+                import torch
+                out = torch.empty(nfull, dtype=torch.float64, device=x0.device)
+            else:
+                out = np.empty(nfull, dtype=np.float64)
         elif hasattr(out, "data_ptr"):
             import torch
             if out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != nfull:
@@ -300,7 +310,14 @@ class PhiFEMSolver:
         st = (C.c_double * 8)()
         self._apply_options()
         L.check(L.lib.phx_set_option(self.mesh._h, L.OPT_PROFILE_SPMV, int(profile_spmv)))
-        L.check(L.lib.phx_solve(self._sys, 0, float(rtol), int(max_iter), p, loc, st))
+        if x0 is None:
+            L.check(L.lib.phx_solve(self._sys, 0, float(rtol), int(max_iter), p, loc, st))
+        else:
+            x0 = self._arr(x0, nfull)
+            p0, loc0 = L.ptr(x0)
+            if loc0 != loc:
+                raise ValueError("x0 and out must both live on the host or both on the device")
+            L.check(L.lib.phx_solve_from(self._sys, 0, float(rtol), int(max_iter), p0, p, loc, st))
         self.stats = {"iterations": int(st[0]), "relres": st[1], "seconds": st[2],
                       "spmv": int(st[3]), "spmv_avg_s": st[4], "spmv_timed": int(st[5]),
                       "converged": bool(st[6]), "restarts": int(st[7])}
@@ -651,3 +668,172 @@ class ElasticitySolver(PhiFEMSolver):
 
     def estimate(self, w, parts=False):
         raise NotImplementedError(_OTHER_RESIDUALS)
+
+
+class ReactionSolver(PhiFEMSolver):
+    """Reaction-diffusion c u - Lap u = f + c g on the level-set domain, u = u_D on {phi = 0}, c >= 0 a constant: the
+    P1 x P1 weak-Dirichlet scheme of `PhiFEMSolver` with a mass term (C ABI `phx_assemble_reaction_wd`)
+
+        a((u,p),(v,q)) = a_Poisson((u,p),(v,q)) + c (u, v)_{dx(1,2)} + stab c^2 h_T^2 (u, v)_{dx(2)}
+        L(v,q)         = L_Poisson(f + c g; u_D)(v,q) + stab c h_T^2 (f + c g, v)_{dx(2)}
+
+    on triangles and tetrahedra -- one implicit step of the heat equation (`HeatSolver`).  The mass is consistent.  DoF
+    layout, active set and "inactive DoFs exactly 0" are those of `PhiFEMSolver`; every row is stored (no stencil-coded
+    rows on a box), `solve`, `split`, `export_csr` and `spmv` work as in the base class.  `update_rhs` evaluates the
+    linear form for new data on the device and leaves the matrix alone: the per-step call of a time loop, or of a sweep
+    over load cases."""
+
+    def __init__(self, mesh, reaction, pen_coef=1.0, stab_coef=1.0, deterministic=False, degree=1):
+        if getattr(mesh, "cell_type", None) == "quadrilateral":
+            raise NotImplementedError("the reaction term is assembled on triangles and tetrahedra (no Q1 spaces)")
+        if degree != 1:
+            raise NotImplementedError("the reaction term: P1 x P1 is implemented (degree = 1)")
+        reaction = float(reaction)
+        if not (0.0 <= reaction < np.inf):
+            raise ValueError(f"reaction={reaction!r}: a finite value >= 0")
+        super().__init__(mesh, pen_coef=pen_coef, stab_coef=stab_coef, deterministic=deterministic)
+        self.reaction = reaction
+
+    def _nodal(self, arrays):
+        """The nodal arrays of one call as the C ABI takes them (None stays None), all on one side."""
+        nv = self.mesh.nv
+        arrays = [None if a is None else self._arr(a, nv) for a in arrays]
+        if len({L.ptr(a)[1] for a in arrays if a is not None}) != 1:
+            raise ValueError("the nodal arrays must all live on the host or all on the device")
+        return arrays
+
+    def assemble(self, phi_h, f_h, u_D, g_h=None):
+        """Matrix and right-hand side for nodal P1 data (numpy or device tensors); g_h = None counts as 0."""
+        self._free()
+        phi_h, f_h, u_D, g_h = self._nodal((phi_h, f_h, u_D, g_h))
+        self._keep = (phi_h, f_h, u_D, g_h)
+        self._tag_generation = self.mesh._tag_generation
+        self._apply_options()
+        h = C.c_void_p()
+        L.check(L.lib.phx_assemble_reaction_wd(self.mesh._h, self.pen_coef, self.stab_coef, self.reaction,
+                                               L.ptr(phi_h)[0], L.ptr(f_h)[0], L.ptr(g_h)[0], L.ptr(u_D)[0],
+                                               L.ptr(phi_h)[1], C.byref(h)))
+        self._sys = h
+        return self.info()
+
+    def update_rhs(self, f_h, u_D, g_h=None):
+        """Right-hand side for new f_h, u_D, g_h with the phi_h of `assemble` (`phx_system_update_rhs`): a gather per
+        active vertex on the device, bit-reproducible; the matrix and every solver format stay as they are."""
+        if self._sys is None:
+            raise RuntimeError("update_rhs: call assemble() first")
+        f_h, u_D, g_h = self._nodal((f_h, u_D, g_h))
+        phi_h = self._keep[0]
+        if L.ptr(phi_h)[1] != L.ptr(f_h)[1]:
+            raise ValueError("update_rhs: the data must live where the phi_h of assemble() lives")
+        self._keep = (phi_h, f_h, u_D, g_h)
+        L.check(L.lib.phx_system_update_rhs(self._sys, L.ptr(phi_h)[0], L.ptr(f_h)[0], L.ptr(g_h)[0], L.ptr(u_D)[0],
+                                            L.ptr(phi_h)[1]))
+
+    def estimate(self, w, parts=False):
+        raise NotImplementedError(_OTHER_RESIDUALS)
+
+
+class HeatSolver:
+    """Heat equation du/dt - Lap u = f on the level-set domain, u = u_D on {phi = 0}, by implicit time stepping on
+    `ReactionSolver`: backward Euler (scheme="bdf1": c = 1 / dt, g = u^n) or BDF2 (scheme="bdf2": c = 3 / (2 dt),
+    g = (4 u^n - u^{n-1}) / 3, the first step by backward Euler).  The matrix is assembled once per value of c; a step
+    refreshes the right-hand side on the device and solves, started from the previous solution.
+
+        heat = HeatSolver(mesh, dt); heat.assemble(phi_h); heat.set_state(u0)
+        for n in range(steps): w = heat.step(f_h(heat.t + dt), u_D(heat.t + dt))
+
+    With device tensors (phi_h, u0, f_h, u_D) the loop makes no host copy of a nodal field.  `u` is the u half of the
+    last w, `t` the time, `stats` the solve's stats plus `rhs_seconds`."""
+
+    def __init__(self, mesh, dt, scheme="bdf1", pen_coef=1.0, stab_coef=1.0, deterministic=False):
+        if getattr(mesh, "cell_type", None) == "quadrilateral":
+            raise NotImplementedError("the heat solver runs on triangles and tetrahedra (no Q1 spaces)")
+        dt = float(dt)
+        if not (0.0 < dt < np.inf):
+            raise ValueError(f"dt={dt!r}: a finite value > 0")
+        if scheme not in ("bdf1", "bdf2"):
+            raise ValueError(f"scheme={scheme!r}: 'bdf1' or 'bdf2'")
+        self.mesh, self.dt, self.scheme = mesh, dt, scheme
+        self._kw = dict(pen_coef=pen_coef, stab_coef=stab_coef, deterministic=deterministic)
+        self._solver = None
+        self._phi = None
+        self.u = self._u_prev = self._w = None
+        self.t = 0.0
+        self.stats = {}
+
+    def _zeros_like(self, a):
+        if hasattr(a, "data_ptr"):
+            import torch
+            return torch.zeros_like(a)
+        return np.zeros(self.mesh.nv)
+
+    def _system(self, c):
+        """The reaction system at coefficient c on the current tags (assembled when c or the tags changed)."""
+        if self._solver is None or self._solver.reaction != c:
+            solver = ReactionSolver(self.mesh, c, **self._kw)
+            zero = self._zeros_like(self._phi)
+            solver.assemble(self._phi, zero, zero)
+            self._solver = solver
+            self._w = None     # the previous solution belongs to another active set or system
+        return self._solver
+
+    def assemble(self, phi_h):
+        """Builds the system of the next step on the tags the mesh holds now.  Calling it again after re-tagging is the
+        moving-domain use: the state `u` is kept as it is, and its values on vertices that are newly active are the
+        caller's responsibility (set them with `set_state` before the next step)."""
+        self._solver = None
+        nv = self.mesh.nv
+        if hasattr(phi_h, "data_ptr"):
+            if phi_h.numel() != nv:
+                raise ValueError(f"phi_h has {phi_h.numel()} values, the mesh {nv} vertices")
+        else:
+            phi_h = np.ascontiguousarray(phi_h, dtype=np.float64)
+            if phi_h.shape != (nv,):
+                raise ValueError(f"phi_h has shape {phi_h.shape}, the mesh {nv} vertices")
+        self._phi = phi_h
+        bdf2 = self.scheme == "bdf2" and self._u_prev is not None
+        return self._system((1.5 if bdf2 else 1.0) / self.dt).info()
+
+    def set_state(self, u0, t=0.0):
+        """Initial (or corrected) state: nodal values of u at time t, of the kind (numpy / device tensor) of phi_h.
+        The multistep history starts again: the next BDF2 step is a backward Euler step."""
+        nv = self.mesh.nv
+        if hasattr(u0, "data_ptr"):
+            if u0.numel() != nv:
+                raise ValueError(f"u0 has {u0.numel()} values, the mesh {nv} vertices")
+            u0 = u0.detach().clone().reshape(nv)
+        else:
+            u0 = np.array(u0, dtype=np.float64)
+            if u0.shape != (nv,):
+                raise ValueError(f"u0 has shape {u0.shape}, the mesh {nv} vertices")
+        self.u, self._u_prev, self._w = u0, None, None
+        self.t = float(t)
+
+    def step(self, f_h, u_D, rtol=1e-8, max_iter=20000, warm_start=True):
+        """One step from t to t + dt with f_h, u_D at t + dt.  Returns the mixed solution w = [u, p] of the step
+        (full numbering, inactive DoFs 0; a tensor for tensor data) and advances `u`, `t`, `stats`."""
+        if self._phi is None:
+            raise RuntimeError("step: call assemble() first")
+        if self.u is None:
+            raise RuntimeError("step: call set_state() first")
+        import time
+        if self.scheme == "bdf2" and self._u_prev is not None:
+            c, g = 1.5 / self.dt, (4.0 * self.u - self._u_prev) / 3.0
+        else:
+            c, g = 1.0 / self.dt, self.u
+        solver = self._system(c)
+        t0 = time.perf_counter()
+        solver.update_rhs(f_h, u_D, g)
+        rhs_seconds = time.perf_counter() - t0
+        x0 = self._w if warm_start else None
+        out = None
+        if hasattr(self.u, "data_ptr") and self.u.is_cuda:
+            import torch
+            out = torch.empty(2 * self.mesh.nv, dtype=torch.float64, device=self.u.device)
+        w = solver.solve(rtol=rtol, max_iter=max_iter, out=out, x0=x0)
+        nv = self.mesh.nv
+        self._u_prev = self.u if self.scheme == "bdf2" else None
+        self.u, self._w = w[:nv], w
+        self.t += self.dt
+        self.stats = dict(solver.stats, rhs_seconds=rhs_seconds)
+        return w
