@@ -252,6 +252,10 @@ enum phx_option {
                                phx_box_facet_tables and the vertex coordinates, without atomics; 0: the facet kernel that scatters with f64
                                atomics runs there too.  Same matrix to round-off: 0 is the reference path of
                                tests/test_box_facet_rows.py                                                      */
+  PHX_OPT_RED_SPMV = 17, /* 1 (default): the two stored-row products of the reduced BiCGStab loop (phases 57 / 60) run
+                               k_spmv_red, a kernel that holds the stored-row branch of the SpMV alone; 0: k_spmv_sell
+                               runs there too.  Same y_B, bit for bit, and dot-product partials of the same composition:
+                               0 is the reference path of tests/test_hip_spmv_red.py                          */
   PHX_OPT_ALLOW_EMPTY = 6, /* 1: phx_assemble_poisson_wd returns an EMPTY system (n_active = 0) when no cell
                                is tagged 1 / 2 instead of PHX_ERR_VALUE: a slab of a partitioned box that
                                does not touch the domain still joins every collective of the solve          */
@@ -709,6 +713,14 @@ int phx_krylov_identity_loop(const phx_system *s, int *on);
  * x0 = M^-1 E_C b_C, so that every Krylov vector vanishes on the stencil rows).  PHX_KR_REDUCED=0 in the environment
  * keeps the full-length identity loop. */
 int phx_krylov_reduced_loop(const phx_system *s, int *on);
+/* Test aid, after a phx_solve that ran the reduced loop (PHX_ERR_VALUE otherwise): copies one buffer of that loop from
+ * (put != 0) or to `host`.  which 0 .. 6: the compact stored-row vectors r, rhat, p, v, s, t, u_B (16 doubles per SELL
+ * slice, indexed by SELL slot); 7: u in solver order (n_active); 8 / 9: phat / shat (n_active); 10: the scalars and
+ * dot-product slots (16 + 2 * 8 * 64 * 8 doubles; quantity q of parity par: slot k at 16 + ((8 par + q % 8) * 64 + k) * 8
+ * + q / 8).  count must be the length of the buffer.  While the loop stays in force phx_krylov_phase accepts its phases:
+ * 57 KR_RED_SPMV_P v_B = (A phat)_B with (v_B, rhat_B) into quantity 0, 60 KR_RED_SPMV_S t_B = (A shat)_B with
+ * (t_B, s_B), (t_B, t_B), (t_B, rhat_B) into quantities 1, 2, 8, parity 0, added to what the slots hold. */
+int phx_krylov_reduced_io(phx_system *s, int which, double *host, int64_t count, int put);
 /* Phases (the KrPhase names of phx_solve.hip): 0 KR_BEGIN, 1 KR_BEGIN2, 2 KR_SPMV_P v = A phat, 3 KR_UPDATE_S
  * s-update, 4 KR_SPMV_S t = A shat, 5 KR_UPDATE_XR x/r-update, 6 KR_UPDATE_P p-update + roll, 7 KR_PRECOND_P phat = P p,
  * 8 KR_PRECOND_S shat = P s (no-ops without a preconditioner); with the slab-exact preconditioner

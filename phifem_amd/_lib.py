@@ -29,8 +29,8 @@ CELL_NAMES = {v: k for k, v in CELL_TYPES.items()}
 PHI_NODAL_P1, PHI_POINTS, PHI_QUADRIC = 0, 1, 2
 (OPT_PROFILE_SPMV, OPT_HAS_EXTERIOR, OPT_SPMV_XCD_GROUP, OPT_SPMV_VALUE_INDEX, OPT_PRECOND, OPT_ALLOW_EMPTY,
  OPT_EXPORT_CSR, OPT_STRUCTURED, OPT_DETERMINISTIC, OPT_EL_COARSE, OPT_STENCIL_PLANE_ROWS, OPT_P2_COARSE,
- OPT_BOX_TAGS, OPT_MULTILEVEL, OPT_ELWD_COARSE, OPT_BOX_FACET_ROWS) = (
-    1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16)
+ OPT_BOX_TAGS, OPT_MULTILEVEL, OPT_ELWD_COARSE, OPT_BOX_FACET_ROWS, OPT_RED_SPMV) = (
+    1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17)
 (ARR_COORDS, ARR_CELLS, ARR_C2F, ARR_F2C, ARR_CELL_TAGS, ARR_FACET_TAGS, ARR_BFACETS, ARR_C2E,
  ARR_EDGES, ARR_PARENT_CELLS, ARR_CHILD_NODES) = range(11)
 
@@ -136,6 +136,7 @@ SIGNATURES = {
     "phx_solve_from": ([_vp, _i, _d, _i64, _vp, _vp, _i, _pd], _i),
     "phx_krylov_identity_loop": ([_vp, C.POINTER(C.c_int)], _i),
     "phx_krylov_reduced_loop": ([_vp, C.POINTER(C.c_int)], _i),
+    "phx_krylov_reduced_io": ([_vp, _i, _vp, _i64, _i], _i),
     "phx_spmv": ([_vp, _vp, _vp, _i], _i),
     "phx_spmv_bench": ([_vp, _i, _pd], _i),
     "phx_last_timings": ([_vp, _pd], _i),

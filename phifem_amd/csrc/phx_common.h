@@ -185,6 +185,7 @@ struct phx_mesh {
   int structured = 1;              // PHX_OPT_STRUCTURED: stencil-coded interior rows on Kuhn boxes (P1 weak Dirichlet)
   int box_tags = 1;                // PHX_OPT_BOX_TAGS: closed-form tag kernels on generated 3-D boxes (phx_tag_box.inc.hip)
   int box_facet_rows = 1;          // PHX_OPT_BOX_FACET_ROWS: ghost penalty as row gathers where box slots are in force (phx_assemble.hip)
+  int red_spmv = 1;                // PHX_OPT_RED_SPMV: k_spmv_red in the two SpMV phases of the reduced loop (phx_solve.hip)
   int allow_empty = 0;             // PHX_OPT_ALLOW_EMPTY: assembly returns an EMPTY system when no cell is tagged 1 / 2
   int el_coarse = -1;              // PHX_OPT_EL_COARSE
   int p2_coarse = 0;               // PHX_OPT_P2_COARSE: 0 off, -1 automatic, >= 5 the ratio H / h

@@ -1250,6 +1250,7 @@ extern "C" int phx_set_option(phx_mesh *m, int option, int64_t value) {
     case PHX_OPT_STRUCTURED: m->structured = value != 0; return PHX_OK;
     case PHX_OPT_BOX_TAGS: m->box_tags = value != 0; return PHX_OK;
     case PHX_OPT_BOX_FACET_ROWS: m->box_facet_rows = value != 0; return PHX_OK;
+    case PHX_OPT_RED_SPMV: m->red_spmv = value != 0; return PHX_OK;
     case PHX_OPT_DETERMINISTIC: m->deterministic = value != 0; return PHX_OK;
     case PHX_OPT_MULTILEVEL: m->multilevel = value != 0; return PHX_OK;
     case PHX_OPT_EL_COARSE:

@@ -1313,6 +1313,7 @@ k_spmv_sell(int64_t n, int64_t nslices, const int64_t *__restrict__ slice_ptr,
   }
 }
 
+#include "phx_spmv_red.inc.hip"
 
 // ---------------------------------------------------------------------------------------------
 // Multi-GPU overlap: rows whose columns include a halo entry (`isg[pos]` = 1: some neighbour sends this
@@ -2289,7 +2290,7 @@ static int kr_reduced(phx_system *s, bool *on) {
 // SpMV of the identity loop: the SELL-16 blocks of the stored rows alone (the rows of the stencil blocks are left
 // unwritten).  dots 1: o0 += (y, d0);  dots 3: o0 += (y, d0), o1 += (y, y), o2 += (y, d1).  PHX_OPT_DETERMINISTIC:
 // the partial sums are ADDED to slot 0 (R_RV already holds the C-row share there).  compact (reduced loop): y, d0 and d1
-// are compact stored-row vectors (k_spmv_sell<DOTS, true>); dots 0: no dot product.
+// are compact stored-row vectors (k_spmv_red<DOTS>, or k_spmv_sell<DOTS, true>); dots 0: no dot product.
 static int launch_spmv_stored(phx_system *s, const double *x, double *y, int dots, const double *d0, const double *d1,
                               double *o0, double *o1, double *o2, bool compact = false) {
   hipStream_t st = s->mesh->stream;
@@ -2299,7 +2300,16 @@ static int launch_spmv_stored(phx_system *s, const double *x, double *y, int dot
   const StencilArgs sa{0, nullptr, 0, nullptr, nullptr, 0, nullptr};
   // the operands a kernel does not accumulate (d1, o1, o2 with one dot product, all of them with none) are nullptr
   // here and never read there
+  // the two products of the reduced loop have a kernel of their own (PHX_OPT_RED_SPMV = 0: k_spmv_sell<DOTS, true>)
+  const bool red = compact && dots > 0 && s->mesh->red_spmv;
   const auto launch = [&](dim3 grid, DotPart dp) {
+    if (red) {
+      with_dots<1, 3>(dots, [&](auto D) {
+        k_spmv_red<decltype(D)::value><<<grid, dim3(256), 0, st>>>(s->nslices, s->slice_ptr, s->sell_col, s->sell_val, x, y,
+                                                                   s->sell_rows, d0, d1, o0, o1, o2, xg, nb, dp);
+      });
+      return;
+    }
     with_dots<0, 1, 3>(dots, [&](auto D) {
       const auto kernel = compact ? k_spmv_sell<decltype(D)::value, true> : k_spmv_sell<decltype(D)::value, false>;
       kernel<<<grid, dim3(256), 0, st>>>(s->n, s->nslices, s->slice_ptr, s->sell_col, s->sell_val, x, y, nullptr, d0, o0, o1, xg,
@@ -2657,6 +2667,24 @@ extern "C" int phx_krylov_identity_loop(const phx_system *s, int *on) {
 // 1 when the last phx_solve of `s` ran the identity loop on compact stored-row vectors (kr_reduced)
 extern "C" int phx_krylov_reduced_loop(const phx_system *s, int *on) {
   *on = s->kr_red_used ? 1 : 0;
+  return PHX_OK;
+}
+
+// Test aid: the buffers the reduced-loop phases read and write, copied from (put != 0) or to `host`.  which 0 .. 6: the
+// compact vectors r, rhat, p, v, s, t, u_B (nslices * 16 doubles each); 7: u (n); 8 / 9: phat / shat (n); 10: the scalars
+// and dot-product slots (PHX_SCAL_DOUBLES).  count must be the length of the buffer.
+extern "C" int phx_krylov_reduced_io(phx_system *s, int which, double *host, int64_t count, int put) {
+  PHX_HIP(hipSetDevice(s->mesh->device));
+  PHX_REQUIRE(s->kr_red_used, PHX_ERR_VALUE, "the reduced loop is not in force for this system");
+  PHX_REQUIRE(which >= 0 && which <= 10, PHX_ERR_VALUE, "reduced-loop buffer %d: 0 .. 10", which);
+  const KrVecs V = kr_vecs(s);
+  const int64_t m = s->nslices * SELL_S;
+  double *dev = which <= 7 ? s->kr_red + which * m : which == 8 ? V.phat : which == 9 ? V.shat : kr_scal(s);
+  const int64_t len = which <= 6 ? m : which <= 9 ? s->n : (int64_t)PHX_SCAL_DOUBLES;
+  PHX_REQUIRE(count == len, PHX_ERR_VALUE, "reduced-loop buffer %d holds %lld doubles, not %lld", which, (long long)len, (long long)count);
+  PHX_HIP(hipStreamSynchronize(s->mesh->stream));
+  if (put) PHX_HIP(hipMemcpy(dev, host, sizeof(double) * (size_t)len, hipMemcpyHostToDevice));
+  else PHX_HIP(hipMemcpy(host, dev, sizeof(double) * (size_t)len, hipMemcpyDeviceToHost));
   return PHX_OK;
 }
 

@@ -48,7 +48,8 @@ struct TriArgs {
 
 // NT = threads of the block (64 x chunks): with 512 threads the compiler may keep a chunk of 32 rows in registers
 // (__launch_bounds__(1024) capped it at 128 VGPRs: C = 32 spilled 36 registers, C = 48 145 -- the pass ran at 3.1 TB/s on the
-// 768 x 768 x 194 lattice and at 1.9 TB/s on 384 x 384 x 354 against 4.8 TB/s where C = 8)
+// 768 x 768 x 194 lattice and at 1.9 TB/s on 384 x 384 x 354 against 4.8 TB/s where C = 8; those counts are of the sweeps
+// with predicated row updates -- as written now C = 24 takes 78 registers, C = 32 98 and only C = 64 still spills)
 // CW = columns of a block (64, or 32: the two halves of a wavefront then take different chunks of the same 32 columns --
 // twice the chunks for long columns, rows of 256 bytes).
 template <typename T, int C, int MODE, int NT, int CW = 64>
@@ -56,7 +57,11 @@ __global__ void __launch_bounds__(NT)
 k_tri_z(TriArgs a, T *__restrict__ G) {
   extern __shared__ double tri_lds[];
   constexpr int SUB = 64 / CW;
-  const int lane = (int)(threadIdx.x & 63) % CW, c = (int)(threadIdx.x >> 6) * SUB + (int)(threadIdx.x & 63) / CW;
+  const int lane = (int)(threadIdx.x & 63) % CW;
+  // chunk of this lane; with 64 columns per block it is the wavefront's, and saying so keeps r0, len and the row
+  // predicates in scalar registers
+  const int c = SUB == 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))
+                         : (int)(threadIdx.x >> 6) * SUB + (int)(threadIdx.x & 63) / CW;
   const int P = (int)(blockDim.x >> 6) * SUB;
   const int64_t e = (int64_t)blockIdx.x * CW + lane;
   const int x = (int)(e % a.pitch), yy = (int)(e / a.pitch);
@@ -81,11 +86,15 @@ k_tri_z(TriArgs a, T *__restrict__ G) {
       gp += a.plane;
     }
   }
-  // ---- forward, chunk-local
+  // ---- forward, chunk-local.  Rows i >= len of a short chunk are never stored and never reach a carry: the sweeps
+  // update v[i] without a predicate and hold only the running value back (under `if (i < len)` the compiler kept the
+  // old and the new v[i] of every row live until a select, two register pairs per row: C = 24 spilled at the 128
+  // registers of a 1024-thread block)
   double acc = 0.0;
 #pragma unroll
   for (int i = 0; i < C; ++i) {
-    if (i < len) { acc = __builtin_fma(rho, acc, v[i]); v[i] = acc; }
+    v[i] = __builtin_fma(rho, acc, v[i]);
+    acc = i < len ? v[i] : acc;
   }
   sW[c * CW + lane] = acc;
   const double rhoC = dpow(rho, CL);
@@ -98,14 +107,15 @@ k_tri_z(TriArgs a, T *__restrict__ G) {
 #pragma unroll
     for (int i = 0; i < C; ++i) {
       pw *= rho;
-      if (i < len) v[i] += pw;
+      v[i] += pw;
     }
   }
   // ---- backward, chunk-local (on the true w)
   acc = 0.0;
 #pragma unroll
   for (int i = C - 1; i >= 0; --i) {
-    if (i < len) { acc = rho * (v[i] + acc); v[i] = acc; }
+    v[i] = rho * (v[i] + acc);
+    acc = i < len ? v[i] : acc;
   }
   sY[c * CW + lane] = acc;
   __syncthreads();
