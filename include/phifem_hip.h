@@ -705,6 +705,14 @@ int phx_coarse_info(phx_system *s, double *out);
  * i + m0 (j + m1 k), node (i, j, k) at the lattice point (i, j, k) * H) and ainv[nc * nc] = Ac^-1, row-major.  Either
  * pointer may be null.  PHX_ERR_VALUE when the system has no coarse correction. */
 int phx_coarse_export(phx_system *s, int32_t *node_of, double *ainv);
+/* Test aid: one application of the correction, out += D R Ac^-1 R^T in, through the functions the Krylov loop calls
+ * (restriction, dense product, prolongation with the scaling D), exactly as the loop adds it to phat.  in[n] and out[n]
+ * are in the solver's position order (phx_system_get_perm: position -> active row); nothing is permuted here.  out is
+ * read and accumulated into.  gc[nc] receives the restricted vector R^T in and zc[nc] the coarse solution Ac^-1 gc;
+ * either may be null.  The stream is synchronised before the call returns.  PHX_ERR_VALUE, before anything is launched:
+ * no coarse correction (not solved yet, or none built), no active row, the correction of a partitioned box (its
+ * restriction is all-reduced between phases 30-33), a null in or out. */
+int phx_coarse_apply(phx_system *s, const double *in, double *out, double *gc, double *zc, int loc);
 /* After phx_solve: *on = 1 when the solve ran the identity loop (structured P1 system with the f64 lattice
  * preconditioner: SpMVs over the stored rows only, A K_box^-1 = I on the stencil rows), 0 for the standard loop.
  * PHX_KR_IDENTITY=0 in the environment forces the standard loop. */

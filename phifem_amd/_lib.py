@@ -78,6 +78,7 @@ SIGNATURES = {
     "phx_coarse_info": ([_vp, _pd], _i),
     "phx_multilevel_setup": ([_vp], _i),
     "phx_coarse_export": ([_vp, _vp, _vp], _i),
+    "phx_coarse_apply": ([_vp, _vp, _vp, _vp, _vp, _i], _i),
     "phx_precond_local_bbox": ([_vp, _pi64], _i),
     "phx_precond_setup_global": ([_vp, _pi64, _i, _i, _pi64, _pi64], _i),
     "phx_precond_set_carry_buffers": ([_vp, _vp, _vp], _i),

@@ -2791,6 +2791,42 @@ extern "C" int phx_coarse_export(phx_system *s, int32_t *node_of, double *ainv) 
   return PHX_OK;
 }
 
+extern "C" int phx_coarse_apply(phx_system *s, const double *in, double *out, double *gc, double *zc, int loc) {
+  PHX_REQUIRE(s->cc && s->cc->nc > 0, PHX_ERR_VALUE, "the system has no coarse correction (solve it first, with the option set)");
+  PHX_REQUIRE(s->n > 0, PHX_ERR_VALUE, "phx_coarse_apply: the system has no active row");
+  PHX_REQUIRE(!s->cc->dist, PHX_ERR_VALUE, "phx_coarse_apply: the correction of a partitioned box needs its all-reduce (phases 30-33)");
+  PHX_REQUIRE(in && out, PHX_ERR_VALUE, "phx_coarse_apply: in and out must not be null");
+  PHX_HIP(hipSetDevice(s->mesh->device));
+  phx_coarse *c = s->cc;
+  hipStream_t st = s->mesh->stream;
+  const size_t nb = sizeof(double) * (size_t)s->n, ncb = sizeof(double) * (size_t)c->nc;
+  const bool dev = loc == PHX_DEVICE;
+  double *tmp = nullptr;   // host callers: in and out staged on the device
+  if (!dev) PHX_HIP(phx_malloc(&tmp, 2 * nb));
+  auto run = [&]() -> int {
+    const double *din = in;
+    double *dout = out;
+    if (!dev) {
+      PHX_HIP(hipMemcpyAsync(tmp, in, nb, hipMemcpyHostToDevice, st));
+      PHX_HIP(hipMemcpyAsync(tmp + s->n, out, nb, hipMemcpyHostToDevice, st));
+      din = tmp; dout = tmp + s->n;
+    }
+    const hipMemcpyKind k = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    PHX_CHECK(coarse_restrict(s, c, din));
+    if (gc) PHX_HIP(hipMemcpyAsync(gc, c->gc, ncb, k, st));
+    PHX_CHECK(coarse_apply_end(s, c, dout));
+    if (zc) PHX_HIP(hipMemcpyAsync(zc, c->zc, ncb, k, st));
+    if (!dev) PHX_HIP(hipMemcpyAsync(out, dout, nb, hipMemcpyDeviceToHost, st));
+    return PHX_OK;
+  };
+  const int rc = run();
+  const bool synced = hipStreamSynchronize(st) == hipSuccess;
+  (void)phx_free(tmp);
+  if (rc != PHX_OK) return rc;
+  PHX_REQUIRE(synced, PHX_ERR_HIP, "phx_coarse_apply: the stream failed to synchronise");
+  return PHX_OK;
+}
+
 #include "phx_dist.inc.hip"
 
 // The BiCGStab loop of phx_solve (d == nullptr: mode 0, the slot sets alternate with the parity of the iteration) and of

@@ -397,6 +397,22 @@ class PhiFEMSolver:
         L.check(L.lib.phx_coarse_export(self._sys, node_of.ctypes.data_as(C.c_void_p), ainv.ctypes.data_as(C.c_void_p)))
         return node_of, ainv
 
+    def coarse_apply(self, v, out0):
+        """One application of the coarse correction (phx_coarse_apply): (out, gc, zc) with out = out0 + D R Ac^-1 R^T v,
+        gc = R^T v and zc = Ac^-1 gc.  `v`, `out0` and `out` are numpy arrays in the solver's position order."""
+        if self._sys is None:
+            raise ValueError("coarse_apply: call assemble() and solve() first")
+        nc = self.coarse_info()["coarse_dofs"]
+        vp = None if v is None else np.ascontiguousarray(v, dtype=np.float64)
+        out = None if out0 is None else np.array(out0, dtype=np.float64, order="C")
+        n = self.info()["n_active"]
+        for a in (vp, out):
+            if a is not None and a.shape != (n,):
+                raise ValueError(f"coarse_apply: vectors of {n} values (the active rows, in position order) are expected")
+        gc, zc = np.empty(nc, dtype=np.float64), np.empty(nc, dtype=np.float64)
+        L.check(L.lib.phx_coarse_apply(self._sys, L.ptr(vp)[0], L.ptr(out)[0], L.ptr(gc)[0], L.ptr(zc)[0], L.HOST))
+        return out, gc, zc
+
     def spmv(self, x):
         y = np.empty_like(x)
         L.check(L.lib.phx_spmv(self._sys, x.ctypes.data_as(C.c_void_p),

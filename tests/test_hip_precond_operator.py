@@ -32,9 +32,9 @@ Vertex blocks: |x_v - B_v^-1 p_v|_inf <= 8 k eps cond_inf(B_v) |B_v^-1 p_v|_inf 
 from the reference block: Gaussian elimination with partial pivoting on a k x k block.  k_jacobi_u: 2 ulp per entry.
 Every case prints its worst ratio to its bound.
 
-Not covered: P2 with `coarse_space` (the two-level form is pinned by test_hip_p2_coarse.py through whole solves; its
-application under the phase API is left out here), the elasticity coarse correction (not built under the phase API)
-and the identity- and reduced-loop phases 52 - 63 (native loop only; the phase API refuses them).  `Applied.one_iteration`
+The coarse-space corrections (P2 with `coarse_space`, both elasticity solves with `coarse`) are applied through
+`phx_coarse_apply` and compared stage by stage with float64 references in tests/test_hip_coarse_apply.py.
+Not covered: the identity- and reduced-loop phases 52 - 63 (native loop only; the phase API refuses them).  `Applied.one_iteration`
 runs a real iteration only to obtain a second p: the vector phases and scalar recurrences themselves are pinned one phase
 at a time by tests/test_hip_krylov_phases.py, the native loops (the reduced application `box_precond_apply_red` among
 them) through truncated solves by tests/test_hip_krylov_loops.py."""
