@@ -303,6 +303,10 @@ int phx_overwrite_tags(phx_mesh *m, int entity_is_facet, int64_t n, const int32_
 /* Install externally computed dense tags (tests, multi-GPU ghost exchange). */
 int phx_set_tags(phx_mesh *m, int entity_is_facet, const int32_t *values, int loc);
 
+/* [host] The three selections whose per-chunk counts the tagging kernels leave behind, as the assembly and the entity
+ * collection make them: which = 0 cut cells (tag 2), 1 ghost-penalty facets (tag 2 / 3 with two cells), 2 facets tagged
+ * 3 / 4.  Ascending entity indices; out may be NULL to ask for *count alone (at most nc resp. nf entries). */
+int phx_mesh_selection(phx_mesh *m, int which, int32_t *out, int64_t *count);
 /* _compute_integration_entities (mesh_scripts.py:137-192) for the two one-sided measures of
  * compute_tags_measures (:617-626): which = 100 -> facets tagged 4 seen from cells {1,2};
  * which = 101 -> facets tagged 3 seen from cells {2,3}.  Flat [cell, local facet, ...] in the

@@ -101,6 +101,7 @@ SIGNATURES = {
     "phx_overwrite_tags": ([_vp, _i, _i64, _vp, _vp], _i),
     "phx_set_tags": ([_vp, _i, _vp, _i], _i),
     "phx_integration_entities": ([_vp, _i, _vp, _pi64], _i),
+    "phx_mesh_selection": ([_vp, _i, _vp, _pi64], _i),
     "phx_submesh_create": ([_vp, C.POINTER(_vp)], _i),
     "phx_submesh_maps": ([_vp, _vp, _vp], _i),
     "phx_partition_cells": ([_vp, _i, _vp, _vp, _i], _i),

@@ -459,21 +459,7 @@ __device__ __forceinline__ double mult4(int i, int j, int k, int l) {
 // facets) with one lane per entry of the element tensor, so a wavefront issues 64 independent
 // slot updates instead of one lane walking a whole element matrix.
 struct SelOmega { const int8_t *t; __host__ __device__ bool operator()(const int32_t &c) const { const int v = t[c] & PHX_TAG_MASK; return v == 1 || v == 2; } };
-struct SelCut {
-  const int8_t *t;
-  __host__ __device__ bool operator()(const int32_t &c) const { return (t[c] & PHX_TAG_MASK) == 2; }
-  __host__ __device__ const int8_t *bytes() const { return t; }           // byte fast path of phx_select.h
-  __host__ __device__ bool test(int tag, int32_t) const { return (tag & PHX_TAG_MASK) == 2; }
-};
-struct SelGhostFacet {
-  const int8_t *ft; const int32_t *f2c;
-  __host__ __device__ bool operator()(const int32_t &f) const {
-    const int t = ft[f];
-    return (t == 2 || t == 3) && f2c[2 * (int64_t)f + 1] >= 0;  // dS: interior facets only
-  }
-  __host__ __device__ const int8_t *bytes() const { return ft; }
-  __host__ __device__ bool test(int t, int32_t f) const { return (t == 2 || t == 3) && f2c[2 * (int64_t)f + 1] >= 0; }
-};
+// SelCut, SelGhostFacet: phx_select.h (the tagging kernels count them)
 
 // --- vertex -> cell adjacency (once per mesh) ---------------------------------------------------
 __global__ void k_v2c_count(int64_t nc, int nvpc, const int32_t *__restrict__ cells,

@@ -175,10 +175,17 @@ k_demote_isolated_cut(int64_t nc, const int32_t *__restrict__ cells, int8_t *__r
   }
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   uint32_t cnt[4] = {0, 0, 0, 0};
+  // all 256 cells of the wave carry one tag that is not 2 (away from the interface): one ballot instead of sixteen
+  const int u0 = __builtin_amdgcn_readfirstlane(tj[0]);
+  if (u0 != 2 && u0 < 4 && __all(tj[0] == u0 && tj[1] == u0 && tj[2] == u0 && tj[3] == u0)) {
 #pragma unroll
-  for (int j = 0; j < 4; ++j)
+    for (int b = 0; b < 4; ++b) cnt[b] = u0 == b ? 256u : 0u;
+  } else {
 #pragma unroll
-    for (int b = 0; b < 4; ++b) cnt[b] += (uint32_t)__popcll(__ballot(tj[j] == b));
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) cnt[b] += (uint32_t)__popcll(__ballot(tj[j] == b));
+  }
   if (lane == 0) {
     const int64_t wbase = (blockIdx.x * (int64_t)blockDim.x + (threadIdx.x & ~63)) * 4;
     if (wbase < nc && cnt[2]) atomicAdd(&sel_cut[wbase / PHX_SEL_CHUNK], (int32_t)cnt[2]);
@@ -282,14 +289,14 @@ __global__ void k_boundary_cell_cut(int64_t nbf, DetTab tab, FacetVerts fvs, int
 
 // --- a4: facet tags; per-facet predicates equivalent to the set algebra of :454-496 ----------
 // the tag of one facet from the tags of its two cells; returns how many of the reference's facet sets hold it
-__device__ __forceinline__ int facet_rule(int2 cc, const int8_t *__restrict__ ctags, int no_ext, int8_t *tag) {
-  const int b0 = (int)(uint8_t)ctags[cc.x];
+// b0: the tag byte of the first cell (boundary-cut bit included), b1: the tag byte of the second cell (any value where
+// there is none), B: the facet has one cell
+__device__ __forceinline__ int facet_rule_bytes(int b0, int b1, bool B, int no_ext, int8_t *tag) {
   const int t0 = b0 & PHX_TAG_MASK;
-  const int t1 = cc.y >= 0 ? (ctags[cc.y] & PHX_TAG_MASK) : 0;
+  const int t1 = B ? 0 : (b1 & PHX_TAG_MASK);
   const bool I = (t0 == 1) || (t1 == 1);
   const bool C = (t0 == 2) || (t1 == 2);
   const bool E = (t0 == 3) || (t1 == 3);
-  const bool B = cc.y < 0;
   const bool cellcut = (b0 & PHX_BCUT_BIT) != 0;
   const bool CB = B && cellcut;                       // :454-456
   const bool UB = B && !cellcut && !E && !I;          // :457-461
@@ -310,31 +317,54 @@ __device__ __forceinline__ int facet_rule(int2 cc, const int8_t *__restrict__ ct
   *tag = t;
   return (int)ext + (int)inte + (int)IB + (int)cut + (int)BF + (int)DI;
 }
+__device__ __forceinline__ int facet_rule(int2 cc, const int8_t *__restrict__ ctags, int no_ext, int8_t *tag) {
+  return facet_rule_bytes((int)(uint8_t)ctags[cc.x], cc.y >= 0 ? (int)(uint8_t)ctags[cc.y] : 0, cc.y < 0, no_ext, tag);
+}
 
-// four facets per thread: two 16-byte loads of f2c, one 4-byte store of the tags (a byte per lane and store left the
-// kernel at 1.9 TB/s of its 11 B per facet)
+// four facets per thread: two 16-byte loads of f2c, one 4-byte store of the tags (a byte
+// per lane and store left the kernel at 1.9 TB/s of its 11 B per facet)
 // The kernel that writes the tags also counts them: hist_part[bin][block] (7 bins, summed by k_hist_fold: the separate
 // histogram pass re-read 2e8 tag bytes) and, per chunk of PHX_SEL_CHUNK facets, how many facets the two selections every
 // assembly starts with will keep (sel0: ghost-penalty facets = tag 2 / 3 with two cells; sel1: tags 3 / 4) -- their
 // counting passes re-read the tags (and f2c) as well.  A wavefront covers 256 consecutive facets of ONE chunk.
+// Away from the interface all 256 facets of a wavefront carry one tag and agree on having two cells: its counts are then
+// 256 or 0 from one ballot; the 36 ballots of the general path are left to the wavefronts near the interface, at a
+// boundary face and at the tail.
 __global__ void __launch_bounds__(256)
 k_tag_facets(int64_t nf, const int32_t *__restrict__ f2c, const int8_t *__restrict__ ctags,
              int no_ext, const uint8_t *__restrict__ exempt, int8_t *__restrict__ ftags,
              unsigned long long *__restrict__ bad, uint32_t *__restrict__ hist_part,
              int32_t *__restrict__ sel0, int32_t *__restrict__ sel1) {
   __shared__ uint32_t lh[4][9];
-  const int64_t f0 = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) * 4;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  // first facet of the wave, as a scalar
+  const int64_t wbase = (blockIdx.x * (int64_t)blockDim.x + __builtin_amdgcn_readfirstlane((int)(threadIdx.x & ~63u))) * 4;
+  const int64_t f0 = wbase + 4 * lane;
   int nbad = 0;
   int8_t tj[4] = {0x7f, 0x7f, 0x7f, 0x7f};   // 0x7f: no facet here
   bool two[4] = {false, false, false, false};
-  if (f0 + 3 < nf) {
+  uint32_t w = 0x7f7f7f7fu;
+  const bool full = f0 + 3 < nf;
+  if (full) {
     const int4 a = *reinterpret_cast<const int4 *>(f2c + 2 * f0), b = *reinterpret_cast<const int4 *>(f2c + 2 * f0 + 4);
     const int2 cc[4] = {make_int2(a.x, a.y), make_int2(a.z, a.w), make_int2(b.x, b.y), make_int2(b.z, b.w)};
-    uint32_t w = 0u;
+    // The eight tag bytes (and the four exempt flags, one dword: f0 is a multiple of 4) are asked for before any of
+    // them is used, without a branch: a facet with one cell reads its first cell twice.  Loaded where the rule needs
+    // them -- the second byte, the flag and the next facet each behind a branch -- the wavefront waited for eight
+    // dependent round trips, and that wait, not the ballots or the f2c stream, was most of the kernel.
+    int b0[4], b1[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      int8_t t = 0;
-      if (!(exempt && exempt[f0 + j])) nbad += facet_rule(cc[j], ctags, no_ext, &t) != 1;   // exempt: cut through the global mesh, no tag
+      b0[j] = (int)(uint8_t)ctags[cc[j].x];
+      b1[j] = (int)(uint8_t)ctags[cc[j].y >= 0 ? cc[j].y : cc[j].x];
+    }
+    const uint32_t ex = exempt ? *reinterpret_cast<const uint32_t *>(exempt + f0) : 0u;
+    w = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      int8_t t = 0, tr = 0;
+      const int sets = facet_rule_bytes(b0[j], b1[j], cc[j].y < 0, no_ext, &tr);
+      if (!((ex >> (8 * j)) & 0xffu)) { nbad += sets != 1; t = tr; }   // exempt: cut through the global mesh, no tag
       w |= (uint32_t)(uint8_t)t << (8 * j);
       tj[j] = t;
       two[j] = cc[j].y >= 0;
@@ -352,17 +382,25 @@ k_tag_facets(int64_t nf, const int32_t *__restrict__ f2c, const int8_t *__restri
   }
   if (nbad) atomicAdd(bad, (unsigned long long)nbad);
   // ---- counts (wave-uniform: every lane of the block takes part in the ballots)
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   uint32_t cnt[7] = {0, 0, 0, 0, 0, 0, 0}, c0 = 0, c1 = 0;
+  const uint32_t tb = (uint32_t)two[0] | (uint32_t)two[1] << 1 | (uint32_t)two[2] << 2 | (uint32_t)two[3] << 3;
+  const uint32_t w0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)w), tb0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)tb);
+  const uint32_t t0 = w0 & 0xffu;
+  if (w0 == 0x01010101u * t0 && t0 < 7u && (tb0 == 0u || tb0 == 15u) && __all(full && w == w0 && tb == tb0)) {
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
+    for (int b = 0; b < 7; ++b) cnt[b] = t0 == (uint32_t)b ? 256u : 0u;
+    c0 = ((t0 == 2u || t0 == 3u) && tb0 == 15u) ? 256u : 0u;
+    c1 = (t0 == 3u || t0 == 4u) ? 256u : 0u;
+  } else {
 #pragma unroll
-    for (int b = 0; b < 7; ++b) cnt[b] += (uint32_t)__popcll(__ballot(tj[j] == b));
-    c0 += (uint32_t)__popcll(__ballot((tj[j] == 2 || tj[j] == 3) && two[j]));
-    c1 += (uint32_t)__popcll(__ballot(tj[j] == 3 || tj[j] == 4));
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int b = 0; b < 7; ++b) cnt[b] += (uint32_t)__popcll(__ballot(tj[j] == b));
+      c0 += (uint32_t)__popcll(__ballot((tj[j] == 2 || tj[j] == 3) && two[j]));
+      c1 += (uint32_t)__popcll(__ballot(tj[j] == 3 || tj[j] == 4));
+    }
   }
   if (lane == 0) {
-    const int64_t wbase = (blockIdx.x * (int64_t)blockDim.x + (threadIdx.x & ~63)) * 4;   // first facet of the wave
     if (wbase < nf) {
       const int64_t chunk = wbase / PHX_SEL_CHUNK;
       if (c0) atomicAdd(&sel0[chunk], (int32_t)c0);
@@ -403,13 +441,6 @@ __global__ void __launch_bounds__(256) k_hist_fold(int64_t nblocks, const uint32
 // serialises: the matches are ~1 per wavefront, 4 ms at 2*10^8 facets).
 //   which 0 -> ds(100): facets tagged 4 seen from cells {1,2}   (mesh_scripts.py:619-622)
 //   which 1 -> ds(101): facets tagged 3 seen from cells {2,3}   (mesh_scripts.py:623-626)
-struct SelTag34 {
-  const int8_t *ft;
-  __host__ __device__ bool operator()(const int32_t &f) const { return ft[f] == 3 || ft[f] == 4; }
-  __host__ __device__ const int8_t *bytes() const { return ft; }
-  __host__ __device__ bool test(int t, int32_t) const { return t == 3 || t == 4; }
-};
-
 template <bool FILL>
 __global__ void k_entities(int64_t nlist, const int32_t *__restrict__ list,
                            const int32_t *__restrict__ f2c, const int32_t *__restrict__ c2f,
@@ -630,10 +661,9 @@ static int run_facet_rule(phx_mesh *m) {
     if (!m->sel_counts[w]) PHX_HIP(phx_malloc(&m->sel_counts[w], sizeof(int32_t) * (size_t)(nchunks + 1)));
     PHX_HIP(hipMemsetAsync(m->sel_counts[w], 0, sizeof(int32_t) * (size_t)(nchunks + 1), m->stream));
   }
+  const int no_ext = m->has_exterior_override >= 0 ? (m->has_exterior_override ? 0 : 1) : (m->tag_hist[3] == 0 ? 1 : 0);
   k_tag_facets<<<dim3((unsigned)nblocks), dim3(256), 0, m->stream>>>(
-      m->nf, m->f2c, m->cell_tags,
-      m->has_exterior_override >= 0 ? (m->has_exterior_override ? 0 : 1) : (m->tag_hist[3] == 0 ? 1 : 0),
-      m->facet_exempt, m->facet_tags, dbad, part, m->sel_counts[0], m->sel_counts[1]);
+      m->nf, m->f2c, m->cell_tags, no_ext, m->facet_exempt, m->facet_tags, dbad, part, m->sel_counts[0], m->sel_counts[1]);
   k_hist_fold<<<dim3(64, 9), dim3(256), 0, m->stream>>>(nblocks, part, dbad + 1);
   PHX_HIP(hipGetLastError());
   PHX_CHECK(phx_end_timing_mark(m));
@@ -861,6 +891,31 @@ extern "C" int phx_integration_entities(phx_mesh *m, int which, int32_t *out, in
     return a.first != b.first ? a.first < b.first : a.lf < b.lf;
   });
   for (int64_t i = 0; i < n; ++i) { out[2 * i] = r[i].cell; out[2 * i + 1] = r[i].lf; }
+  return PHX_OK;
+}
+
+// The three selections the tagging kernels count, as the assembly and phx_collect_entities make them (with the known
+// per-chunk counts while they are valid), copied to the host.
+extern "C" int phx_mesh_selection(phx_mesh *m, int which, int32_t *out, int64_t *count) {
+  PHX_HIP(hipSetDevice(m->device));
+  PHX_REQUIRE(which >= 0 && which <= 2, PHX_ERR_VALUE, "which must be 0 (cut cells), 1 (ghost-penalty facets) or 2 (facets tagged 3 / 4)");
+  PHX_REQUIRE(which == 0 ? m->have_cell_tags : m->have_facet_tags, PHX_ERR_VALUE, "the tags must be computed first");
+  int32_t *list = nullptr;
+  int64_t n = 0;
+  DevTemps tmp(m->stream);
+  if (which == 0)
+    PHX_CHECK(phx_select_indices(m->stream, m->nc, SelCut{m->cell_tags}, &list, &n, &tmp.blocks,
+                                 m->sel_cut_valid ? m->sel_counts_cut : nullptr, m->sel_cut_valid ? m->tag_hist[2] : -1));
+  else if (which == 1)
+    PHX_CHECK(phx_select_indices(m->stream, m->nf, SelGhostFacet{m->facet_tags, m->f2c}, &list, &n, &tmp.blocks,
+                                 m->sel_counts_valid ? m->sel_counts[0] : nullptr, m->sel_counts_valid ? m->sel_total[0] : -1));
+  else
+    PHX_CHECK(phx_select_indices(m->stream, m->nf, SelTag34{m->facet_tags}, &list, &n, &tmp.blocks,
+                                 m->sel_counts_valid ? m->sel_counts[1] : nullptr, m->sel_counts_valid ? m->sel_total[1] : -1));
+  tmp.adopt(list);
+  PHX_HIP(hipStreamSynchronize(m->stream));
+  if (out && n > 0) PHX_HIP(hipMemcpy(out, list, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+  *count = n;
   return PHX_OK;
 }
 

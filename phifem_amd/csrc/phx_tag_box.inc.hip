@@ -215,11 +215,19 @@ k_box_demote_count(BoxTagGeo g, int8_t *__restrict__ tags, const uint8_t *__rest
   const int64_t wbase = 6 * (row + wi0);                                          // first cell of the wave
   const int64_t bnd = (wbase / PHX_SEL_CHUNK + 1) * (int64_t)PHX_SEL_CHUNK;       // first cell of the next chunk
   uint32_t cnt[4] = {0, 0, 0, 0}, lo = 0;
+  // all 384 cells of the wave carry one tag that is not 2 (away from the interface): one ballot instead of thirty
+  const int u0 = __builtin_amdgcn_readfirstlane(t[0]);
+  if (u0 != 2 && u0 < 4 &&
+      __all(t[0] == u0 && t[1] == u0 && t[2] == u0 && t[3] == u0 && t[4] == u0 && t[5] == u0)) {
 #pragma unroll
-  for (int s = 0; s < 6; ++s) {
+    for (int b = 0; b < 4; ++b) cnt[b] = u0 == b ? 384u : 0u;
+  } else {
 #pragma unroll
-    for (int b = 0; b < 4; ++b) cnt[b] += (uint32_t)__popcll(__ballot(t[s] == b));
-    lo += (uint32_t)__popcll(__ballot(t[s] == 2 && 6 * cube + s < bnd));
+    for (int s = 0; s < 6; ++s) {
+#pragma unroll
+      for (int b = 0; b < 4; ++b) cnt[b] += (uint32_t)__popcll(__ballot(t[s] == b));
+      lo += (uint32_t)__popcll(__ballot(t[s] == 2 && 6 * cube + s < bnd));
+    }
   }
   if (lane == 0) {
     if (wi0 < g.n0) {
