@@ -593,9 +593,27 @@ int phx_assemble_reaction_wd(phx_mesh *m, double pen_coef, double stab_coef, dou
                              const double *f_h, const double *g_h, const double *u_D, int loc, phx_system **out);
 /* Overwrites the right-hand side of a phx_assemble_reaction_wd system with L above for new data (on the tags the mesh
  * holds) and leaves the matrix alone: one lane per active vertex gathers its u and p row over the vertex star in a
- * fixed order, no atomics -- the same data give the same bytes.  Any other system: PHX_ERR_VALUE. */
+ * fixed order, no atomics -- the same data give the same bytes.  Serves phx_assemble_diffusion_wd systems too (with the
+ * kappa_h of their assembly).  Any other system: PHX_ERR_VALUE. */
 int phx_system_update_rhs(phx_system *s, const double *phi_h, const double *f_h, const double *g_h,
                           const double *u_D, int loc);
+/* Variable-coefficient diffusion c u - div(kappa grad u) = f + c g in the same P1 x P1 weak-Dirichlet setting (tags,
+ * DoF layout, active set, "inactive DoFs = 0" of phx_assemble_poisson_wd / phx_assemble_reaction_wd).  kappa_h is a
+ * nodal P1 field, finite and > 0 (checked on the device before anything is built: PHX_ERR_VALUE), c = `reaction` >= 0 a
+ * constant, F = f + c g, kb_T / kb_F the mean of kappa_h over the vertices of a cell / facet:
+ *   a = (kappa grad u, grad v)_{dx(1,2)} + c (u, v)_{dx(1,2)} - (kappa d_n u, v)_{ds(100)}
+ *     + pen kb_T h_T^-2 (u - phi p / h_T, v - phi q / h_T)_{dx(2)}
+ *     + stab h_T^2 / kb_T (c u - grad kappa . grad u, c v - grad kappa . grad v)_{dx(2)}
+ *     + stab avg(h) (kappa [d_n u], [d_n v])_{dS(2,3)}
+ *   L = (F, v)_{dx(1,2)} + pen kb_T h_T^-2 (u_D, v - phi q / h_T)_{dx(2)}
+ *     + stab h_T^2 / kb_T (F, c v - grad kappa . grad v)_{dx(2)}
+ * kappa_h = 1 gives the system of phx_assemble_reaction_wd.  g_h may be NULL (= 0).  Every row is stored; the system
+ * keeps a device copy of kappa_h (released with it) and serves phx_system_update_rhs, which also produced its
+ * right-hand side.  phx_solve: lattice preconditioner (plain lattice Laplacian) where the mesh has a lattice and
+ * max kappa_h / min kappa_h <= 50, else Jacobi.  Quadrilaterals, slabs and partitioned ranks: PHX_ERR_NOT_IMPLEMENTED. */
+int phx_assemble_diffusion_wd(phx_mesh *m, double pen_coef, double stab_coef, double reaction, const double *kappa_h,
+                              const double *phi_h, const double *f_h, const double *g_h, const double *u_D, int loc,
+                              phx_system **out);
 int phx_system_destroy(phx_system *s);
 /* info[14] = {n_active, n_active_u, nnz (structural, CSR), n_full (= 2*nv), sell_padded_nnz,
  *             slot_capacity, sell_nnz (explicit zeros dropped), n_slices, value-indexed slices,

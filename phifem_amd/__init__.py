@@ -14,6 +14,8 @@ Host side (this package) mirrors the reference's interface for the path:
     displacement prescribed on {phi = 0}, the vector analogue of the weak-Dirichlet scheme (P1^d x P1^d)
   * `phifem_amd.solver.ReactionSolver`, `phifem_amd.solver.HeatSolver`  <- no counterpart: c u - Lap u = f + c g in the
     weak-Dirichlet scheme, and backward Euler / BDF2 time stepping of the heat equation on top of it
+  * `phifem_amd.solver.DiffusionSolver`          <- no counterpart: c u - div(kappa grad u) = f + c g with a nodal P1
+    conductivity kappa_h > 0 in the same scheme (`HeatSolver(..., kappa=kappa_h)` steps the heat equation with it)
   * `phifem_amd.partition_cells`, `phifem_amd.distributed.PartitionedProblem`  <- no counterpart: unstructured
     background meshes partitioned over the ranks (the reference is serial, src/phifem/mesh_scripts.py:264)
   * `phifem_amd.refine`, `phifem_amd.prolongate`     <- dolfinx.mesh.refine (demo/interface-elasticity/main.py:390),
@@ -39,5 +41,5 @@ from .mesh_scripts import (DeviceExpression, NodalFunction, Quadric, compute_tag
                            interpolate)
 from .partition import partition_cells, partition_layout  # noqa: F401
 from .distributed import PartitionedProblem  # noqa: F401
-from .solver import (ElasticitySolver, HeatSolver, InterfaceElasticitySolver, NeumannRobinSolver,  # noqa: F401
-                     PhiFEMSolver, ReactionSolver, StrongDirichletSolver)
+from .solver import (DiffusionSolver, ElasticitySolver, HeatSolver, InterfaceElasticitySolver,  # noqa: F401
+                     NeumannRobinSolver, PhiFEMSolver, ReactionSolver, StrongDirichletSolver)

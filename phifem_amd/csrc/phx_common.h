@@ -356,6 +356,9 @@ struct phx_system {
   // reaction system (phx_assemble_react.inc.hip): what phx_system_update_rhs needs to evaluate the linear form again
   bool react = false;
   double react_c = 0.0, react_pen = 0.0, react_stab = 0.0;
+  // diffusion system (phx_assemble_diff.inc.hip): a reaction system with a conductivity -- the system's own copy of kappa_h
+  double *diff_kappa = nullptr;        // [nv] or NULL
+  double diff_contrast = 0.0;          // max kappa_h / min kappa_h (0: no conductivity)
 };
 
 // helpers implemented in phx_mesh.hip

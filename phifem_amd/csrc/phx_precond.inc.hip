@@ -1199,10 +1199,13 @@ static int box_precond_build(phx_system *s, bool p2, const int L[3], const int l
   return PHX_OK;
 }
 
+// Diffusion systems (phx_assemble_diff.inc.hip) are preconditioned with the PLAIN lattice Laplacian, which knows nothing of
+// kappa: above this contrast max kappa_h / min kappa_h Jacobi, which does, needs fewer iterations (measured)
+#define PHX_DIFF_LATTICE_MAX_CONTRAST 50.0
 static inline bool box_precond_kinds(const phx_system *s, bool *p2) {
   const phx_mesh *m = s->mesh;
   *p2 = s->u_p2_block && m->is_box && m->edges != nullptr;
-  const bool p1 = (m->is_box || m->on_box_lattice) && s->u_vertex_block;
+  const bool p1 = (m->is_box || m->on_box_lattice) && s->u_vertex_block && !(s->diff_contrast > PHX_DIFF_LATTICE_MAX_CONTRAST);
   return m->precond != 0 && (p1 || *p2);
 }
 

@@ -749,6 +749,48 @@ class ReactionSolver(PhiFEMSolver):
         raise NotImplementedError(_OTHER_RESIDUALS)
 
 
+class DiffusionSolver(ReactionSolver):
+    """Variable-coefficient diffusion c u - div(kappa grad u) = f + c g on the level-set domain, u = u_D on {phi = 0}:
+    kappa_h a nodal P1 field, finite and > 0, c = `reaction` >= 0 a constant (C ABI `phx_assemble_diffusion_wd`;
+    DESIGN.md 7j).  With F = f + c g and kb_T / kb_F the mean of kappa_h over the vertices of a cell / facet
+
+        a((u,p),(v,q)) = (kappa grad u, grad v)_{dx(1,2)} + c (u, v)_{dx(1,2)} - (kappa d_n u, v)_{ds(100)}
+                       + pen kb_T h_T^-2 (u - phi p / h_T, v - phi q / h_T)_{dx(2)}
+                       + stab h_T^2 / kb_T (c u - grad kappa . grad u, c v - grad kappa . grad v)_{dx(2)}
+                       + stab avg(h) (kappa [d_n u], [d_n v])_{dS(2,3)}
+        L(v,q)         = (F, v)_{dx(1,2)} + pen kb_T h_T^-2 (u_D, v - phi q / h_T)_{dx(2)}
+                       + stab h_T^2 / kb_T (F, c v - grad kappa . grad v)_{dx(2)}
+
+    on triangles and tetrahedra (boxes, `Mesh.from_arrays` meshes, sub-meshes).  kappa_h = 1 is `ReactionSolver`'s
+    system.  DoF layout, active set and "inactive DoFs exactly 0" are those of `PhiFEMSolver`; every row is stored;
+    `solve`, `split`, `export_csr`, `spmv`, `info` come from the base class, `update_rhs` refreshes the right-hand side
+    with the kappa_h of `assemble` (the system keeps its own device copy).  A kappa_h with an entry that is not finite
+    and > 0 raises ValueError before anything is built.  `estimate` refuses; `estimate_zz` serves for marking.  On a
+    lattice mesh `solve` uses the plain lattice preconditioner while max kappa_h / min kappa_h <= 50 and Jacobi above
+    (measured: DESIGN.md 7j)."""
+
+    def __init__(self, mesh, reaction=0.0, pen_coef=1.0, stab_coef=1.0, deterministic=False):
+        if getattr(mesh, "cell_type", None) == "quadrilateral":
+            raise NotImplementedError("variable-coefficient diffusion is assembled on triangles and tetrahedra (no Q1 "
+                                      "spaces)")
+        super().__init__(mesh, reaction, pen_coef=pen_coef, stab_coef=stab_coef, deterministic=deterministic)
+
+    def assemble(self, kappa_h, phi_h, f_h, u_D, g_h=None):
+        """Matrix and right-hand side for nodal P1 data (numpy arrays or device tensors, all on one side); g_h = None
+        counts as 0."""
+        self._free()
+        kappa_h, phi_h, f_h, u_D, g_h = self._nodal((kappa_h, phi_h, f_h, u_D, g_h))
+        self._keep = (phi_h, f_h, u_D, g_h)      # the library copies kappa_h
+        self._tag_generation = self.mesh._tag_generation
+        self._apply_options()
+        h = C.c_void_p()
+        L.check(L.lib.phx_assemble_diffusion_wd(self.mesh._h, self.pen_coef, self.stab_coef, self.reaction,
+                                                L.ptr(kappa_h)[0], L.ptr(phi_h)[0], L.ptr(f_h)[0], L.ptr(g_h)[0],
+                                                L.ptr(u_D)[0], L.ptr(phi_h)[1], C.byref(h)))
+        self._sys = h
+        return self.info()
+
+
 class HeatSolver:
     """Heat equation du/dt - Lap u = f on the level-set domain, u = u_D on {phi = 0}, by implicit time stepping on
     `ReactionSolver`: backward Euler (scheme="bdf1": c = 1 / dt, g = u^n) or BDF2 (scheme="bdf2": c = 3 / (2 dt),
@@ -759,9 +801,12 @@ class HeatSolver:
         for n in range(steps): w = heat.step(f_h(heat.t + dt), u_D(heat.t + dt))
 
     With device tensors (phi_h, u0, f_h, u_D) the loop makes no host copy of a nodal field.  `u` is the u half of the
-    last w, `t` the time, `stats` the solve's stats plus `rhs_seconds`."""
+    last w, `t` the time, `stats` the solve's stats plus `rhs_seconds`.
 
-    def __init__(self, mesh, dt, scheme="bdf1", pen_coef=1.0, stab_coef=1.0, deterministic=False):
+    kappa (a nodal P1 conductivity, finite and > 0, of the kind of phi_h): du/dt - div(kappa grad u) = f, stepped on
+    `DiffusionSolver` instead; nothing else in the stepper changes.  None (default): the Laplacian, as above."""
+
+    def __init__(self, mesh, dt, scheme="bdf1", pen_coef=1.0, stab_coef=1.0, deterministic=False, kappa=None):
         if getattr(mesh, "cell_type", None) == "quadrilateral":
             raise NotImplementedError("the heat solver runs on triangles and tetrahedra (no Q1 spaces)")
         dt = float(dt)
@@ -771,6 +816,15 @@ class HeatSolver:
             raise ValueError(f"scheme={scheme!r}: 'bdf1' or 'bdf2'")
         self.mesh, self.dt, self.scheme = mesh, dt, scheme
         self._kw = dict(pen_coef=pen_coef, stab_coef=stab_coef, deterministic=deterministic)
+        if kappa is not None:
+            if hasattr(kappa, "data_ptr"):
+                if kappa.numel() != mesh.nv:
+                    raise ValueError(f"kappa has {kappa.numel()} values, the mesh {mesh.nv} vertices")
+            else:
+                kappa = np.ascontiguousarray(kappa, dtype=np.float64)
+                if kappa.shape != (mesh.nv,):
+                    raise ValueError(f"kappa has shape {kappa.shape}, the mesh {mesh.nv} vertices")
+        self.kappa = kappa
         self._solver = None
         self._phi = None
         self.u = self._u_prev = self._w = None
@@ -784,11 +838,16 @@ class HeatSolver:
         return np.zeros(self.mesh.nv)
 
     def _system(self, c):
-        """The reaction system at coefficient c on the current tags (assembled when c or the tags changed)."""
+        """The reaction (with kappa: diffusion) system at coefficient c on the current tags (assembled when c or the
+        tags changed)."""
         if self._solver is None or self._solver.reaction != c:
-            solver = ReactionSolver(self.mesh, c, **self._kw)
             zero = self._zeros_like(self._phi)
-            solver.assemble(self._phi, zero, zero)
+            if self.kappa is None:
+                solver = ReactionSolver(self.mesh, c, **self._kw)
+                solver.assemble(self._phi, zero, zero)
+            else:
+                solver = DiffusionSolver(self.mesh, c, **self._kw)
+                solver.assemble(self.kappa, self._phi, zero, zero)
             self._solver = solver
             self._w = None     # the previous solution belongs to another active set or system
         return self._solver
