@@ -593,8 +593,8 @@ int phx_assemble_reaction_wd(phx_mesh *m, double pen_coef, double stab_coef, dou
                              const double *f_h, const double *g_h, const double *u_D, int loc, phx_system **out);
 /* Overwrites the right-hand side of a phx_assemble_reaction_wd system with L above for new data (on the tags the mesh
  * holds) and leaves the matrix alone: one lane per active vertex gathers its u and p row over the vertex star in a
- * fixed order, no atomics -- the same data give the same bytes.  Serves phx_assemble_diffusion_wd systems too (with the
- * kappa_h of their assembly).  Any other system: PHX_ERR_VALUE. */
+ * fixed order, no atomics -- the same data give the same bytes.  Serves phx_assemble_diffusion_wd and phx_assemble_convection_wd systems too
+ * (with the kappa_h / beta_h of their assembly).  Any other system: PHX_ERR_VALUE. */
 int phx_system_update_rhs(phx_system *s, const double *phi_h, const double *f_h, const double *g_h,
                           const double *u_D, int loc);
 /* Variable-coefficient diffusion c u - div(kappa grad u) = f + c g in the same P1 x P1 weak-Dirichlet setting (tags,
@@ -614,6 +614,29 @@ int phx_system_update_rhs(phx_system *s, const double *phi_h, const double *f_h,
 int phx_assemble_diffusion_wd(phx_mesh *m, double pen_coef, double stab_coef, double reaction, const double *kappa_h,
                               const double *phi_h, const double *f_h, const double *g_h, const double *u_D, int loc,
                               phx_system **out);
+/* Convection-diffusion c u + beta . grad u - div(kappa grad u) = f + c g in the same P1 x P1 weak-Dirichlet setting (tags,
+ * DoF layout, active set, "inactive DoFs = 0" of phx_assemble_diffusion_wd).  beta_h[nv][d] is a nodal P1 vector field,
+ * vertex-major like the coordinates, finite (checked on the device before anything is built: PHX_ERR_VALUE); kappa_h as
+ * for phx_assemble_diffusion_wd; c = `reaction` >= 0 and supg_coef >= 0 constants (else PHX_ERR_VALUE).  With
+ * L u = c u + beta . grad u - grad kappa . grad u, bb_T / bb_F the mean of beta_h over the vertices of a cell / facet,
+ * ks_T = kb_T + h_T |bb_T|, ks_F = kb_F + avg(h) |bb_F| and tau_T = h_T^2 / ks_T:
+ *   a = (kappa grad u, grad v)_{dx(1,2)} + c (u, v)_{dx(1,2)} + (beta . grad u, v)_{dx(1,2)} - (kappa d_n u, v)_{ds(100)}
+ *     + supg tau_T (L u, beta . grad v)_{dx(1,2)}
+ *     + pen ks_T h_T^-2 (u - phi p / h_T, v - phi q / h_T)_{dx(2)} + stab tau_T (L u, L v)_{dx(2)}
+ *     + stab avg(h) |F| ks_F ([d_n u], [d_n v])_{dS(2,3)}
+ *   L = (F, v)_{dx(1,2)} + supg tau_T (F, beta . grad v)_{dx(1,2)} + pen ks_T h_T^-2 (u_D, v - phi q / h_T)_{dx(2)}
+ *     + stab tau_T (F, L v)_{dx(2)}
+ * beta_h = 0 gives the system of phx_assemble_diffusion_wd for any supg_coef.  g_h may be NULL (= 0).  Every row is
+ * stored; the system keeps device copies of kappa_h and beta_h (released with it) and serves phx_system_update_rhs, which
+ * also produced its right-hand side.  phx_solve: lattice preconditioner where the mesh has a lattice,
+ * max kappa_h / min kappa_h <= 50 and pe_max = max_T h_T |bb_T| / kb_T <= PHX_CD_LATTICE_MAX_PECLET, else Jacobi.
+ * Quadrilaterals, slabs and partitioned ranks: PHX_ERR_NOT_IMPLEMENTED. */
+int phx_assemble_convection_wd(phx_mesh *m, double pen_coef, double stab_coef, double supg_coef, double reaction,
+                               const double *kappa_h, const double *beta_h, const double *phi_h, const double *f_h,
+                               const double *g_h, const double *u_D, int loc, phx_system **out);
+/* out[4] = {pe_max, max |beta_v|, supg_coef, max kappa_h / min kappa_h} of a phx_assemble_convection_wd system; any other
+ * system: PHX_ERR_VALUE. */
+int phx_convection_info(const phx_system *s, double *out);
 int phx_system_destroy(phx_system *s);
 /* info[14] = {n_active, n_active_u, nnz (structural, CSR), n_full (= 2*nv), sell_padded_nnz,
  *             slot_capacity, sell_nnz (explicit zeros dropped), n_slices, value-indexed slices,

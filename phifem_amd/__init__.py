@@ -16,6 +16,8 @@ Host side (this package) mirrors the reference's interface for the path:
     weak-Dirichlet scheme, and backward Euler / BDF2 time stepping of the heat equation on top of it
   * `phifem_amd.solver.DiffusionSolver`          <- no counterpart: c u - div(kappa grad u) = f + c g with a nodal P1
     conductivity kappa_h > 0 in the same scheme (`HeatSolver(..., kappa=kappa_h)` steps the heat equation with it)
+  * `phifem_amd.solver.ConvectionDiffusionSolver` <- no counterpart: c u + beta . grad u - div(kappa grad u) = f + c g with
+    a nodal P1 velocity beta_h and optional SUPG (`HeatSolver(..., velocity=beta_h)` steps the transport equation with it)
   * `phifem_amd.partition_cells`, `phifem_amd.distributed.PartitionedProblem`  <- no counterpart: unstructured
     background meshes partitioned over the ranks (the reference is serial, src/phifem/mesh_scripts.py:264)
   * `phifem_amd.refine`, `phifem_amd.prolongate`     <- dolfinx.mesh.refine (demo/interface-elasticity/main.py:390),
@@ -41,5 +43,5 @@ from .mesh_scripts import (DeviceExpression, NodalFunction, Quadric, compute_tag
                            interpolate)
 from .partition import partition_cells, partition_layout  # noqa: F401
 from .distributed import PartitionedProblem  # noqa: F401
-from .solver import (DiffusionSolver, ElasticitySolver, HeatSolver, InterfaceElasticitySolver,  # noqa: F401
-                     NeumannRobinSolver, PhiFEMSolver, ReactionSolver, StrongDirichletSolver)
+from .solver import (ConvectionDiffusionSolver, DiffusionSolver, ElasticitySolver, HeatSolver,  # noqa: F401
+                     InterfaceElasticitySolver, NeumannRobinSolver, PhiFEMSolver, ReactionSolver, StrongDirichletSolver)

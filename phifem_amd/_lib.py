@@ -126,6 +126,8 @@ SIGNATURES = {
     "phx_assemble_reaction_wd": ([_vp, _d, _d, _d, _vp, _vp, _vp, _vp, _i, C.POINTER(_vp)], _i),
     "phx_system_update_rhs": ([_vp, _vp, _vp, _vp, _vp, _i], _i),
     "phx_assemble_diffusion_wd": ([_vp, _d, _d, _d, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_vp)], _i),
+    "phx_assemble_convection_wd": ([_vp, _d, _d, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.POINTER(_vp)], _i),
+    "phx_convection_info": ([_vp, _pd], _i),
     "phx_reference_nodes": ([_i, _i, _vp, C.POINTER(C.c_int)], _i),
     "phx_cell_errors": ([_vp, _i, _i, _vp, _vp, _i64, _vp, _i, _vp, _vp, _pd], _i),
     "phx_estimate_poisson_wd": ([_vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _pd], _i),

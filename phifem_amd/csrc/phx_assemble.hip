@@ -1594,7 +1594,7 @@ extern "C" int phx_system_destroy(phx_system *s) {
                   s->val, s->rhs, s->diag, s->slice_ptr, s->sell_col, s->sell_val,
                   s->sell_val_raw, s->sell_kind, s->perm, s->iperm, s->work, s->scal, s->row_nz,
                   s->c0, s->stencil, s->seg, s->slice_seg, s->sell_rows, s->cscale, s->pvec, s->bnd, s->bnd_rec, s->dpart, s->st_map,
-                  s->kr_cmask, s->kr_red, s->diff_kappa};
+                  s->kr_cmask, s->kr_red, s->diff_kappa, s->cd_beta};
   for (void *p : ptrs) (void)phx_free(p);
   if (s->p2s) {
     (void)phx_free(s->p2s->coef); (void)phx_free(s->p2s->mask); (void)phx_free(s->p2s->runs);
@@ -2500,3 +2500,4 @@ extern "C" int phx_system_export(phx_system *s, int64_t *rowptr, int32_t *col, d
 #include "phx_recover.inc.hip"
 #include "phx_assemble_react.inc.hip"
 #include "phx_assemble_diff.inc.hip"
+#include "phx_assemble_cd.inc.hip"

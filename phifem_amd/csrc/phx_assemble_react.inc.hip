@@ -104,11 +104,14 @@ static int react_update_rhs(phx_system *s, const double *dphi, const double *df,
 
 // systems with a conductivity (phx_assemble_diff.inc.hip, included after this file)
 static int diff_update_rhs(phx_system *s, const double *dphi, const double *df, const double *dg, const double *dud);
+// systems with a conductivity and a velocity (phx_assemble_cd.inc.hip)
+static int cd_update_rhs(phx_system *s, const double *dphi, const double *df, const double *dg, const double *dud);
 
 extern "C" int phx_system_update_rhs(phx_system *s, const double *phi_h, const double *f_h, const double *g_h,
                                      const double *u_D, int loc) {
   PHX_REQUIRE(s != nullptr && s->react, PHX_ERR_VALUE,
-              "phx_system_update_rhs: the system was not built by phx_assemble_reaction_wd or phx_assemble_diffusion_wd");
+              "phx_system_update_rhs: the system was not built by phx_assemble_reaction_wd, phx_assemble_diffusion_wd or "
+              "phx_assemble_convection_wd");
   phx_mesh *m = s->mesh;
   PHX_HIP(hipSetDevice(m->device));
   PHX_REQUIRE(m->have_cell_tags, PHX_ERR_VALUE, "cell tags must be computed before the right-hand side");
@@ -118,7 +121,9 @@ extern "C" int phx_system_update_rhs(phx_system *s, const double *phi_h, const d
   PHX_CHECK(to_device(m, f_h, loc, m->nv, &df, staged));
   if (g_h) PHX_CHECK(to_device(m, g_h, loc, m->nv, &dg, staged));
   PHX_CHECK(to_device(m, u_D, loc, m->nv, &dud, staged));
-  PHX_CHECK(s->diff_kappa ? diff_update_rhs(s, dphi, df, dg, dud) : react_update_rhs(s, dphi, df, dg, dud));
+  PHX_CHECK(s->cd_beta      ? cd_update_rhs(s, dphi, df, dg, dud)
+            : s->diff_kappa ? diff_update_rhs(s, dphi, df, dg, dud)
+                            : react_update_rhs(s, dphi, df, dg, dud));
   PHX_HIP(hipStreamSynchronize(m->stream));   // the caller may overwrite its arrays when this returns
   return PHX_OK;
 }

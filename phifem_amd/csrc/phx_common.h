@@ -359,6 +359,11 @@ struct phx_system {
   // diffusion system (phx_assemble_diff.inc.hip): a reaction system with a conductivity -- the system's own copy of kappa_h
   double *diff_kappa = nullptr;        // [nv] or NULL
   double diff_contrast = 0.0;          // max kappa_h / min kappa_h (0: no conductivity)
+  // convection-diffusion system (phx_assemble_cd.inc.hip): a diffusion system with a velocity -- the system's own copy of beta_h
+  double *cd_beta = nullptr;           // [nv][gdim] or NULL
+  double cd_supg = 0.0;                // SUPG coefficient
+  double cd_peclet = 0.0;              // max over the cells of Omega_h of h_T |mean beta| / mean kappa (0: no velocity)
+  double cd_beta_max = 0.0;            // max |beta_v|
 };
 
 // helpers implemented in phx_mesh.hip

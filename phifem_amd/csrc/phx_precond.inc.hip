@@ -1202,10 +1202,15 @@ static int box_precond_build(phx_system *s, bool p2, const int L[3], const int l
 // Diffusion systems (phx_assemble_diff.inc.hip) are preconditioned with the PLAIN lattice Laplacian, which knows nothing of
 // kappa: above this contrast max kappa_h / min kappa_h Jacobi, which does, needs fewer iterations (measured)
 #define PHX_DIFF_LATTICE_MAX_CONTRAST 50.0
+// Convection-diffusion systems (phx_assemble_cd.inc.hip): the lattice Laplacian knows nothing of beta either.  Above this
+// cell Peclet number max_T h_T |mean beta| / mean kappa the system is solved with Jacobi: 1 is the largest measured value at
+// which the lattice solve was ahead in time at 256^3 both without and with SUPG (single runs)
+#define PHX_CD_LATTICE_MAX_PECLET 1.0
 static inline bool box_precond_kinds(const phx_system *s, bool *p2) {
   const phx_mesh *m = s->mesh;
   *p2 = s->u_p2_block && m->is_box && m->edges != nullptr;
-  const bool p1 = (m->is_box || m->on_box_lattice) && s->u_vertex_block && !(s->diff_contrast > PHX_DIFF_LATTICE_MAX_CONTRAST);
+  const bool p1 = (m->is_box || m->on_box_lattice) && s->u_vertex_block && !(s->diff_contrast > PHX_DIFF_LATTICE_MAX_CONTRAST) &&
+                  !(s->cd_peclet > PHX_CD_LATTICE_MAX_PECLET);
   return m->precond != 0 && (p1 || *p2);
 }
 

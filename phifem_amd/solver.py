@@ -791,6 +791,83 @@ class DiffusionSolver(ReactionSolver):
         return self.info()
 
 
+class ConvectionDiffusionSolver(DiffusionSolver):
+    """Convection-diffusion c u + beta . grad u - div(kappa grad u) = f + c g on the level-set domain, u = u_D on
+    {phi = 0}: beta_h a nodal P1 vector field of shape (nv, d), finite; kappa_h as for `DiffusionSolver`; c = `reaction`
+    >= 0 and `supg_coef` >= 0 constants (C ABI `phx_assemble_convection_wd`).  With F = f + c g,
+    L u = c u + beta . grad u - grad kappa . grad u, bb_T / bb_F the mean of beta_h over the vertices of a cell / facet,
+    ks_T = kb_T + h_T |bb_T|, ks_F = kb_F + avg(h) |bb_F| and tau_T = h_T^2 / ks_T
+
+        a((u,p),(v,q)) = (kappa grad u, grad v)_{dx(1,2)} + c (u, v)_{dx(1,2)} + (beta . grad u, v)_{dx(1,2)}
+                       - (kappa d_n u, v)_{ds(100)} + supg tau_T (L u, beta . grad v)_{dx(1,2)}
+                       + pen ks_T h_T^-2 (u - phi p / h_T, v - phi q / h_T)_{dx(2)} + stab tau_T (L u, L v)_{dx(2)}
+                       + stab avg(h) |F| ks_F ([d_n u], [d_n v])_{dS(2,3)}
+        L(v,q)         = (F, v)_{dx(1,2)} + supg tau_T (F, beta . grad v)_{dx(1,2)}
+                       + pen ks_T h_T^-2 (u_D, v - phi q / h_T)_{dx(2)} + stab tau_T (F, L v)_{dx(2)}
+
+    on triangles and tetrahedra.  supg_coef > 0 adds streamline diffusion (SUPG) on all of Omega_h; 0.25 removes most of
+    the overshoot at outflow layers.  Dirichlet data are imposed on all of {phi = 0}, inflow and outflow alike.  beta_h = 0
+    is `DiffusionSolver`'s system.  The matrix is not symmetric; `solve` is BiCGStab as everywhere.  `update_rhs`, `solve`,
+    `split`, `export_csr`, `spmv` come from the base classes; `info()` and `stats` carry `peclet_max` = max over the cells
+    of Omega_h of h_T |bb_T| / kb_T.  On a lattice mesh `solve` uses the plain lattice preconditioner while the contrast
+    of kappa_h is <= 50 and peclet_max is below the threshold of DESIGN.md 7k, and Jacobi above.  `estimate` refuses;
+    `estimate_zz` serves for marking."""
+
+    def __init__(self, mesh, reaction=0.0, pen_coef=1.0, stab_coef=1.0, supg_coef=0.0, deterministic=False):
+        supg_coef = float(supg_coef)
+        if not (0.0 <= supg_coef < np.inf):
+            raise ValueError(f"supg_coef={supg_coef!r}: a finite value >= 0")
+        super().__init__(mesh, reaction, pen_coef=pen_coef, stab_coef=stab_coef, deterministic=deterministic)
+        self.supg_coef = supg_coef
+
+    def _velocity(self, beta_h):
+        """beta_h as the C ABI takes it: (nv, d), float64, contiguous."""
+        nv, d = self.mesh.nv, self.mesh.gdim
+        if not hasattr(beta_h, "data_ptr"):
+            beta_h = np.ascontiguousarray(beta_h, dtype=np.float64)
+        if tuple(beta_h.shape) != (nv, d):
+            raise ValueError(f"beta_h has shape {tuple(beta_h.shape)}, the mesh needs ({nv}, {d})")
+        return self._arr(beta_h, nv * d) if hasattr(beta_h, "data_ptr") else beta_h
+
+    def assemble(self, beta_h, phi_h, f_h, u_D, g_h=None, kappa_h=None):
+        """Matrix and right-hand side for nodal P1 data (numpy arrays or device tensors, all on one side); g_h = None
+        counts as 0, kappa_h = None as ones."""
+        self._free()
+        beta_h = self._velocity(beta_h)
+        if kappa_h is None:
+            if hasattr(beta_h, "data_ptr"):
+                import torch
+                kappa_h = torch.ones(self.mesh.nv, dtype=torch.float64, device=beta_h.device)
+            else:
+                kappa_h = np.ones(self.mesh.nv)
+        kappa_h, phi_h, f_h, u_D, g_h = self._nodal((kappa_h, phi_h, f_h, u_D, g_h))
+        if L.ptr(beta_h)[1] != L.ptr(phi_h)[1]:
+            raise ValueError("the nodal arrays must all live on the host or all on the device")
+        self._keep = (phi_h, f_h, u_D, g_h)      # the library copies kappa_h and beta_h
+        self._tag_generation = self.mesh._tag_generation
+        self._apply_options()
+        h = C.c_void_p()
+        L.check(L.lib.phx_assemble_convection_wd(self.mesh._h, self.pen_coef, self.stab_coef, self.supg_coef, self.reaction,
+                                                 L.ptr(kappa_h)[0], L.ptr(beta_h)[0], L.ptr(phi_h)[0], L.ptr(f_h)[0],
+                                                 L.ptr(g_h)[0], L.ptr(u_D)[0], L.ptr(phi_h)[1], C.byref(h)))
+        self._sys = h
+        return self.info()
+
+    def convection_info(self):
+        """`peclet_max`, `beta_max` = max |beta_v| and `kappa_contrast` of the assembled system (phx_convection_info)."""
+        o = (C.c_double * 4)()
+        L.check(L.lib.phx_convection_info(self._sys, o))
+        return {"peclet_max": o[0], "beta_max": o[1], "kappa_contrast": o[3]}
+
+    def info(self):
+        return dict(super().info(), **self.convection_info())
+
+    def solve(self, *args, **kwargs):
+        out = super().solve(*args, **kwargs)
+        self.stats["peclet_max"] = self.convection_info()["peclet_max"]
+        return out
+
+
 class HeatSolver:
     """Heat equation du/dt - Lap u = f on the level-set domain, u = u_D on {phi = 0}, by implicit time stepping on
     `ReactionSolver`: backward Euler (scheme="bdf1": c = 1 / dt, g = u^n) or BDF2 (scheme="bdf2": c = 3 / (2 dt),
@@ -804,9 +881,14 @@ class HeatSolver:
     last w, `t` the time, `stats` the solve's stats plus `rhs_seconds`.
 
     kappa (a nodal P1 conductivity, finite and > 0, of the kind of phi_h): du/dt - div(kappa grad u) = f, stepped on
-    `DiffusionSolver` instead; nothing else in the stepper changes.  None (default): the Laplacian, as above."""
+    `DiffusionSolver` instead; nothing else in the stepper changes.  None (default): the Laplacian, as above.
 
-    def __init__(self, mesh, dt, scheme="bdf1", pen_coef=1.0, stab_coef=1.0, deterministic=False, kappa=None):
+    velocity (a nodal P1 vector field of shape (nv, d), of the kind of phi_h): du/dt + beta . grad u - div(kappa grad u)
+    = f, stepped on `ConvectionDiffusionSolver` with `supg_coef` (kappa = None: ones).  None (default): no transport,
+    and `supg_coef` is not used."""
+
+    def __init__(self, mesh, dt, scheme="bdf1", pen_coef=1.0, stab_coef=1.0, deterministic=False, kappa=None,
+                 velocity=None, supg_coef=0.0):
         if getattr(mesh, "cell_type", None) == "quadrilateral":
             raise NotImplementedError("the heat solver runs on triangles and tetrahedra (no Q1 spaces)")
         dt = float(dt)
@@ -825,6 +907,16 @@ class HeatSolver:
                 if kappa.shape != (mesh.nv,):
                     raise ValueError(f"kappa has shape {kappa.shape}, the mesh {mesh.nv} vertices")
         self.kappa = kappa
+        if velocity is not None:
+            d = mesh.gdim
+            if not hasattr(velocity, "data_ptr"):
+                velocity = np.ascontiguousarray(velocity, dtype=np.float64)
+            if tuple(velocity.shape) != (mesh.nv, d):
+                raise ValueError(f"velocity has shape {tuple(velocity.shape)}, the mesh needs ({mesh.nv}, {d})")
+            supg_coef = float(supg_coef)
+            if not (0.0 <= supg_coef < np.inf):
+                raise ValueError(f"supg_coef={supg_coef!r}: a finite value >= 0")
+        self.velocity, self.supg_coef = velocity, supg_coef
         self._solver = None
         self._phi = None
         self.u = self._u_prev = self._w = None
@@ -842,7 +934,10 @@ class HeatSolver:
         tags changed)."""
         if self._solver is None or self._solver.reaction != c:
             zero = self._zeros_like(self._phi)
-            if self.kappa is None:
+            if self.velocity is not None:
+                solver = ConvectionDiffusionSolver(self.mesh, c, supg_coef=self.supg_coef, **self._kw)
+                solver.assemble(self.velocity, self._phi, zero, zero, kappa_h=self.kappa)
+            elif self.kappa is None:
                 solver = ReactionSolver(self.mesh, c, **self._kw)
                 solver.assemble(self._phi, zero, zero)
             else:
